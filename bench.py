@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — encode throughput of BRIEF's SIREN fit loop on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json metric: "voxels/sec encode (512^3 vol, 4x256 SIREN)"):
@@ -427,6 +427,14 @@ def rate_point(F, tgt, vol, clean, vmin, vmax, steps, seed=42):
             **q, "seconds": time.perf_counter() - t0}
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: one float32 DIR/<name>.npy per device tensor (the 8x512 net's parameters and gradients, the largest
+    case, are 15 MB together)"""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+
+
 def encode_decode_wall(vol_host, steps, precision="fp32"):
     """SURVEY 8d's encode figure, measured: wall clock around NFGR.compress of the HOST-resident volume (preprocess, the
     reference's `_preprocessed` dump, loss-weight map, normalise, H2D, net init, `steps` optimizer steps, weight files +
@@ -489,9 +497,15 @@ def main():
     ap.add_argument("--divide", action="store_true", help="run the DivideTask product path also at world size 1 (one block, process group initialised)")
     ap.add_argument("--block", type=int, default=512, help="edge of the cubic block (tests only; the metric is quoted on 512)")
     ap.add_argument("--no-extras", action="store_true", help="skip configs / psnr_at_bitrate_sweep / the NFGR wall clocks (headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (loss, parameters, "
+                                                         "gradients) as DIR/<name>.npy in float32; single-rank path only")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus > 1 or args.divide):
+        ap.error("--dump-outputs: only the single-rank path (--gpus 1 without --divide) dumps its outputs")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args)                              # does not return
 
@@ -580,8 +594,12 @@ def main():
     tgt += np.float32(0.0)
     torch.manual_seed(42)
     net = SIREN(coords_channel=3, data_channel=1, features=FEATURES, layers=LAYERS, w0=W0, precision=args.precision).to(dev)
-    fit = Fitter(net, tgt, BLOCK, sampler="randompoint", sample_size=SAMPLE, optimizer="Adamax", lr=1e-3,
-                 scheduler={"name": "MultiStepLR", "milestones": [50000, 60000, 70000], "gamma": 0.2}, seed=42 + rank)
+    params0 = net.params.clone()
+
+    def new_fit():
+        return Fitter(net, tgt, BLOCK, sampler="randompoint", sample_size=SAMPLE, optimizer="Adamax", lr=1e-3,
+                      scheduler={"name": "MultiStepLR", "milestones": [50000, 60000, 70000], "gamma": 0.2}, seed=42 + rank)
+    fit = new_fit()
 
     def barrier():
         if dist is not None:
@@ -603,6 +621,11 @@ def main():
         pre += 1
         if pre % 50 == 0:
             torch.cuda.synchronize()
+    # the pre-roll's step count follows the clock: the counted steps start again from the initial net and a fresh optimizer
+    # state, so that what they compute depends on the arguments alone (--dump-outputs compares it across builds)
+    net.params.copy_(params0)
+    net.sync_packed()
+    fit = new_fit()
     for _ in range(args.warmup):
         fit.step()
     L = _lib.lib()
@@ -620,11 +643,13 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss, "params": net.params, "grads": net.grads})
 
     # ---- end-to-end figures: continue the SAME fit to --encode-steps optimizer steps in one C-ABI call,
     #      decode the whole block with the forward kernel (de-normalise + cast fused), PSNR from the GPU SSE
     psnr, extra, q2k = None, {}, {}
-    steps_done = pre + args.warmup + args.steps
+    steps_done = fit.t
     if not args.no_psnr:
         more = max(args.encode_steps - steps_done, 0)
         torch.cuda.synchronize()

@@ -645,6 +645,31 @@ def test_bench_four_ranks_share_the_gpu_like_a_scale_run():
     assert 10.0 < out["psnr_at_bitrate"]["psnr_db"] < 100.0 and 0.0 < out["psnr_at_bitrate"]["ssim"] <= 1.0
 
 
+def test_bench_dump_outputs_do_not_depend_on_the_preroll(tmp_path):
+    """bench.py --dump-outputs DIR: the last timed step's loss, parameters and gradients as float32 .npy files, bit for bit the same
+    after two pre-roll lengths (the pre-roll's length follows the clock in a default run), and the line reports --steps timed steps"""
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for pre in (2, 30):
+        d = tmp_path / ("pre%d" % pre)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--block", "64", "--steps", "3", "--warmup", "1",
+                            "--preroll", str(pre), "--preroll-seconds", "0", "--no-extras", "--no-cpu-baseline", "--no-psnr", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["steps"] == 3 and out["preroll_steps"] == pre and out["ms_per_step"] > 0
+        dumps.append({n: np.load(str(d / (n + ".npy"))) for n in ("loss", "params", "grads")})
+    a, b = dumps
+    pcount = SIREN.calc_param_count(3, 1, 256, 5)
+    assert a["loss"].shape == (1,) and a["params"].shape == a["grads"].shape == (pcount,)
+    for n in a:
+        assert a[n].dtype == np.float32 and np.array_equal(a[n], b[n]), n
+    assert float(a["loss"][0]) == out["loss"] and np.all(np.isfinite(a["grads"])) and np.any(a["grads"] != 0)
+
+
 def test_adaptive_octree_device_statistics_choose_the_pinned_partition():
     """volumes of 2^24 voxels or more take their octree variances and FFT features from the GPU (torch float64 reductions,
     rocFFT) instead of numpy, whose arithmetic tests/golden/adaptive.npz pins: on a 128^3 volume with an all-zero octant

@@ -261,3 +261,17 @@ def test_multitask_expansion(tmp_path):
     finally:
         import shutil
         shutil.rmtree(temp_dir, ignore_errors=True)
+
+
+def test_bench_refuses_bad_step_counts_and_a_dump_off_the_single_rank_path(tmp_path):
+    """bench.py checks these before it touches a device: fewer than one timed step, a negative warm-up, and --dump-outputs on the
+    multi-rank or DivideTask path (whose fits run inside NFGR.compress_divide) are usage errors"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dump = str(tmp_path / "dump")
+    for args in (["--steps", "0"], ["--warmup", "-1"], ["--gpus", "2", "--dump-outputs", dump], ["--divide", "--dump-outputs", dump]):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args, capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 2 and "bench.py: error:" in r.stderr, (args, r.stderr[-1000:])
+    assert not os.path.exists(dump)
