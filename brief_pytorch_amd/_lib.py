@@ -31,6 +31,10 @@ class GridDesc(C.Structure):
     _fields_ = [("ndim", C.c_int32), ("reserved", C.c_int32), ("dims", C.c_int64 * 3), ("lo", C.c_float), ("hi", C.c_float)]
 
 
+class GridBox(C.Structure):        # brief_grid_box
+    _fields_ = [("grid", GridDesc), ("start", C.c_int64 * 3), ("step", C.c_int64 * 3), ("extent", C.c_int64 * 3)]
+
+
 class BatchDesc(C.Structure):
     _fields_ = [("coords", C.c_void_p), ("targets", C.c_void_p), ("weights", C.c_void_p), ("idx", C.c_void_p),
                 ("offset", C.c_int64), ("n", C.c_int64), ("rng_pop", C.c_int64), ("rng_seed", C.c_uint64), ("rng_step", C.c_uint64)]
@@ -54,7 +58,7 @@ OUT_F32, OUT_U8, OUT_U16 = 0, 1, 2
 PRECISION = {"fp32": 0, "f32": 0, "bf16": 1, "bf16x3": 2}
 
 EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_packed_count",
-           "brief_train_workspace_bytes", "brief_siren_repack", "brief_siren_forward", "brief_forward_workspace_bytes", "brief_siren_forward_ws", "brief_siren_train_step", "brief_siren_fit_step",
+           "brief_train_workspace_bytes", "brief_siren_repack", "brief_siren_forward", "brief_forward_workspace_bytes", "brief_siren_forward_ws", "brief_siren_forward_box", "brief_siren_train_step", "brief_siren_fit_step",
            "brief_siren_fit", "brief_multi_fit",
            "brief_optim_step", "brief_sample_indices", "brief_sse_u16", "brief_profile_enable", "brief_profile_fused", "brief_deblock_edge", "brief_ssim_u16", "brief_ssim_partial_count",
            "brief_sincos_probe", "brief_cu_count"]
@@ -122,6 +126,8 @@ def lib():
     L.brief_forward_workspace_bytes.restype = C.c_int64
     L.brief_forward_workspace_bytes.argtypes = [dp, C.c_int64]
     L.brief_siren_forward_ws.argtypes = [dp, vp, gp, bp, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp, C.c_int64, vp]
+    L.brief_siren_forward_box.argtypes = [dp, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double,
+                                          vp, C.c_int64, vp]
     L.brief_siren_train_step.argtypes = [dp, vp, gp, bp, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, C.c_int64, vp]
     L.brief_siren_fit_step.argtypes = [dp, vp, vp, gp, bp, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp,
                                        C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, vp, vp, vp, C.c_int64, vp]

@@ -321,9 +321,11 @@ __device__ __forceinline__ void write_image16(uint4 *IMG, const f32x16 (&h)[MTW_
     }
 }
 
-template <int NT, bool TRAIN, int CO /* 1: data_channel == 1; 4: any */, int NS /* 32-sample tiles per workgroup tile */, int NW = 8>
-__global__ __launch_bounds__(64 * NW, 1) void k16(const FusedArgs a)
+template <int NT, bool TRAIN, int CO /* 1: data_channel == 1; 4: any */, int NS /* 32-sample tiles per workgroup tile */, int NW = 8,
+          bool BOX = false /* inference over a box of the grid (box_coords) */>
+__global__ __launch_bounds__(64 * NW, 1) void k16(const typename KArgsT<BOX>::type a)
 {
+    static_assert(!(TRAIN && BOX), "the box mapping is an inference instantiation");
 #ifdef BRIEF_STAMPS
     float st_acc[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     long long st_last = clock64();
@@ -376,7 +378,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k16(const FusedArgs a)
         // ---- inputs of the tile's samples, once per workgroup
         if (tid < TS) {
             float4 xi, yi, wi;
-            small_inputs((kargs_t)__builtin_amdgcn_kernarg_segment_ptr(), a.idx, a.rng_step, cin, cout, n0 + tid, xi, yi, wi);
+            small_inputs<BOX>((kargs_t)__builtin_amdgcn_kernarg_segment_ptr(), a.idx, a.rng_step, cin, cout, n0 + tid, xi, yi, wi);
             INX[tid] = xi; INY[tid] = yi; INW[tid] = wi;
             if (TRAIN) {
                 // coordinates as the B operand of the first-layer gradient job: rows x0, x1, x2, 1

@@ -30,6 +30,14 @@ struct GridArgs {
     uint64_t magic[3];      // floor(2^64 / dims[a]) + 1   (exact quotients for every 32-bit numerator)
 };
 
+// a strided box of a grid (brief_siren_forward_box): box voxel (i0, i1, i2), in (d,h,w) order, is grid voxel start + step * i on
+// every axis; box-linear index b = (i0 * extent[1] + i1) * extent[2] + i2.  Axes past cin are unused.
+struct BoxArgs {
+    int64_t start[3], step[3], extent[3];
+    uint64_t magic[3];      // floor(2^64 / extent[a]) + 1
+    int fast;               // the box has fewer than 2^32 voxels: 32-bit split (every grid dim is below 2^31, whatever the grid's size)
+};
+
 // n / dv for a loop-invariant divisor (Lemire's fastdiv: one 64-bit multiply-high instead of ~100 VALU
 // instructions of 64-bit division; the VALU is what the f32 MFMA competes with)
 __device__ __forceinline__ uint32_t fast_div(uint32_t nn, uint64_t magic, uint32_t dv)
@@ -69,6 +77,16 @@ struct FusedArgs {
     int diag;            // timing diagnostics only (BRIEF_DIAG): bit 0 = stash descriptors with zero records (the range check then
                          // drops every stash load and store: results are wrong, the instruction stream is unchanged)
 };
+// The argument of the box instantiations (<.., BOX = true>, inference only): sample j = offset + n is box voxel j (box_coords).  The box
+// lives in a struct of its own behind FusedArgs, so that every other instantiation keeps its kernel-argument segment (and with it the
+// offsets of the hidden arguments behind it) exactly as it was.
+struct FusedBoxArgs : FusedArgs {
+    BoxArgs box;
+};
+template <bool BOX> struct KArgsT { using type = FusedArgs; };
+template <> struct KArgsT<true> { using type = FusedBoxArgs; };
+// the kernel's only argument, read through the constant address space (what the BOX instantiations read the box from)
+typedef const __attribute__((address_space(4))) FusedBoxArgs *kargs_box;
 
 // Workgroup barrier for LDS hand-offs only.  __syncthreads() also emits s_waitcnt vmcnt(0), which
 // drains every global load / store still in flight (register prefetches, stash stores) at each
@@ -131,6 +149,49 @@ __device__ __forceinline__ void grid_coords(const GridArgs &g, int cin, int64_t 
         x0 = lin_coord(g, 0, ih);
         x1 = lin_coord(g, 1, iw);
     }
+}
+
+// box-linear index b -> coordinates of grid voxel start + step * i (the box of the kernel argument, see BoxArgs).  The full index on
+// each axis is below 2^31, so the coordinate is lin_coord32 of it: the same float the whole-grid decode gives that voxel, bit for bit.
+__device__ __forceinline__ void box_coords(const GridArgs &g, int cin, int64_t b, float &x0, float &x1, float &x2)
+{
+    kargs_box ap = (kargs_box)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ap));
+    uint32_t i0, i1, i2 = 0u;
+    if (cin == 3) {
+        const uint32_t e2 = (uint32_t)ap->box.extent[2], e1 = (uint32_t)ap->box.extent[1];
+        if (ap->box.fast) {
+            const uint32_t bu = (uint32_t)b;
+            const uint32_t t2 = fast_div(bu, ap->box.magic[2], e2);
+            const uint32_t t1 = fast_div(t2, ap->box.magic[1], e1);
+            i0 = t1; i1 = t2 - t1 * e1; i2 = bu - t2 * e2;
+        } else {
+            const int64_t t2 = b / (int64_t)e2, t1 = t2 / (int64_t)e1;
+            i0 = (uint32_t)t1; i1 = (uint32_t)(t2 - t1 * e1); i2 = (uint32_t)(b - t2 * e2);
+        }
+    } else {
+        const uint32_t e1 = (uint32_t)ap->box.extent[1];
+        if (ap->box.fast) {
+            const uint32_t bu = (uint32_t)b;
+            const uint32_t t1 = fast_div(bu, ap->box.magic[1], e1);
+            i0 = t1; i1 = bu - t1 * e1;
+        } else {
+            const int64_t t1 = b / (int64_t)e1;
+            i0 = (uint32_t)t1; i1 = (uint32_t)(b - t1 * e1);
+        }
+    }
+    x0 = lin_coord32(g, 0, (uint32_t)ap->box.start[0] + (uint32_t)ap->box.step[0] * i0);
+    x1 = lin_coord32(g, 1, (uint32_t)ap->box.start[1] + (uint32_t)ap->box.step[1] * i1);
+    if (cin == 3) x2 = lin_coord32(g, 2, (uint32_t)ap->box.start[2] + (uint32_t)ap->box.step[2] * i2);
+}
+
+// the coordinate synthesis of a kernel instantiation: the whole flattened grid, or (BOX, inference only) a box of it.  BOX = false compiles
+// to grid_coords alone, so the instantiations without the box (every TRAIN one) carry no instruction of it.
+template <bool BOX>
+__device__ __forceinline__ void sample_coords(const GridArgs &g, int cin, int64_t j, float &x0, float &x1, float &x2)
+{
+    if constexpr (BOX) box_coords(g, cin, j, x0, x1, x2);
+    else grid_coords(g, cin, j, x0, x1, x2);
 }
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));

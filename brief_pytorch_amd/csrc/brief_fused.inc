@@ -24,9 +24,10 @@ struct FusedLds {
 #endif
 constexpr bool fused_lean(int NT) { return BRIEF_LEAN && (NT == 8 || NT == BRIEF_LEAN7); }
 constexpr int fused_train_wpe(int NT) { return NT > 8 ? 1 : (NT <= 4 || fused_lean(NT) ? (BRIEF_TRAIN_WPE > 3 ? BRIEF_TRAIN_WPE : 3) : BRIEF_TRAIN_WPE); }
-template <int NT, bool TRAIN>
-__global__ __launch_bounds__(256, TRAIN ? fused_train_wpe(NT) : (NT > 8 ? 2 : 3)) void k_fused(const FusedArgs a)
+template <int NT, bool TRAIN, bool BOX = false>      // BOX: inference over a box of the grid (box_coords)
+__global__ __launch_bounds__(256, TRAIN ? fused_train_wpe(NT) : (NT > 8 ? 2 : 3)) void k_fused(const typename KArgsT<BOX>::type a)
 {
+    static_assert(!(TRAIN && BOX), "the box mapping is an inference instantiation");
 #ifdef BRIEF_STAMPS
     float st_acc[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     long long st_last = clock64();
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(256, TRAIN ? fused_train_wpe(NT) : (NT > 8 ? 2 : 3)
                 x1 = k_co[j * cin + 1];
                 if (cin == 3) x2 = k_co[j * cin + 2];
             } else {
-                grid_coords(kg, cin, j, x0, x1, x2);
+                sample_coords<BOX>(kg, cin, j, x0, x1, x2);
             }
         }
         f32x16 acc[K::MTW];

@@ -614,22 +614,24 @@ static inline void launch_timed(KP kern, int grid, int block, size_t lds, hipStr
     else hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, st, arg);
 }
 
-template <bool TRAIN>
-static int launch_fused(const FusedArgs &fa, int grid, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr)
+// BOX (inference only): the box instantiations of the same kernels (brief_siren_forward_box)
+template <bool TRAIN, bool BOX = false>
+static int launch_fused(const typename KArgsT<BOX>::type &fa, int grid, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr)
 {
+    static_assert(!(TRAIN && BOX), "the box mapping is an inference path");
     const int nt = brief_nt(fa.d);
     if (fa.d.precision == BRIEF_PREC_BF16X3 && (TRAIN || g_x3_decode)) {
         // split precision: the 64-sample walk (k_fused_x3); BRIEF_X3_DECODE=0 evaluates such a net on the f32 forward kernel below
         const size_t lds = sizeof(float) * X3TLds::TOTAL;
-        if (int rc = dev_attr_once((const void *)k_fused_x3<TRAIN>, (int)lds)) return rc;
-        launch_timed(k_fused_x3<TRAIN>, grid, 256, lds, st, fa, e0, e1);
+        if (int rc = dev_attr_once((const void *)k_fused_x3<TRAIN, BOX>, (int)lds)) return rc;
+        launch_timed(k_fused_x3<TRAIN, BOX>, grid, 256, lds, st, fa, e0, e1);
         HIP_TRY(hipGetLastError());
         return 0;
     }
 #define BRIEF_CASE(NTV)                                                                                  \
     case NTV: {                                                                                          \
         const size_t lds = sizeof(float) * FusedLds<NTV, !TRAIN>::TOTAL;                                 \
-        launch_timed(k_fused<NTV, TRAIN>, grid, 256, lds, st, fa, e0, e1);                               \
+        launch_timed(k_fused<NTV, TRAIN, BOX>, grid, 256, lds, st, fa, e0, e1);                          \
         break;                                                                                           \
     }
 #if BRIEF_FUSED64
@@ -651,8 +653,8 @@ static int launch_fused(const FusedArgs &fa, int grid, hipStream_t st, hipEvent_
         if (!fa.Z) return fail(BRIEF_ERR_WORKSPACE, "widths above 1024 features evaluate through a scratch: call brief_siren_forward_ws with brief_forward_workspace_bytes() bytes");
 #define BRIEF_WIDE_CASE(MTWV)                                                                            \
     case MTWV:                                                                                           \
-        if (int rc = dev_attr_once((const void *)k_wide<MTWV, TRAIN>, (int)lds)) return rc;              \
-        launch_timed(k_wide<MTWV, TRAIN>, grid, 256, lds, st, fa, e0, e1);                               \
+        if (int rc = dev_attr_once((const void *)k_wide<MTWV, TRAIN, BOX>, (int)lds)) return rc;         \
+        launch_timed(k_wide<MTWV, TRAIN, BOX>, grid, 256, lds, st, fa, e0, e1);                          \
         break;
         switch (mtw) {
             BRIEF_WIDE_CASE(3) BRIEF_WIDE_CASE(4) BRIEF_WIDE_CASE(5) BRIEF_WIDE_CASE(6) BRIEF_WIDE_CASE(7) BRIEF_WIDE_CASE(8)
@@ -671,8 +673,8 @@ static int launch_fused(const FusedArgs &fa, int grid, hipStream_t st, hipEvent_
         const size_t lds = sizeof(float) * lean_lds(1, mtw, nt).total;
 #define BRIEF_WIDE_RM(MTWV, RMV)                                                                         \
     {                                                                                                    \
-        if (int rc = dev_attr_once((const void *)k_lean<1, MTWV, 0, TRAIN, RMV>, (int)(sizeof(float) * lean_lds(1, MTWV, 4 * MTWV).total))) return rc; \
-        launch_timed(k_lean<1, MTWV, 0, TRAIN, RMV>, grid, 256, lds, st, fa, e0, e1);                    \
+        if (int rc = dev_attr_once((const void *)k_lean<1, MTWV, 0, TRAIN, RMV, BOX>, (int)(sizeof(float) * lean_lds(1, MTWV, 4 * MTWV).total))) return rc; \
+        launch_timed(k_lean<1, MTWV, 0, TRAIN, RMV, BOX>, grid, 256, lds, st, fa, e0, e1);               \
     }
 #define BRIEF_WIDE(MTWV)                                                                                 \
     case MTWV:                                                                                           \
@@ -696,8 +698,8 @@ static int launch_fused(const FusedArgs &fa, int grid, hipStream_t st, hipEvent_
     case 16:
         if constexpr (!TRAIN) {      // inference only (their TRAIN steps run on k_lean)
             const size_t lds12 = sizeof(float) * FusedLds<12, true>::TOTAL, lds16 = sizeof(float) * FusedLds<16, true>::TOTAL;
-            if (nt == 12) launch_timed(k_fused<12, false>, grid, 256, lds12, st, fa, e0, e1);
-            else launch_timed(k_fused<16, false>, grid, 256, lds16, st, fa, e0, e1);
+            if (nt == 12) launch_timed(k_fused<12, false, BOX>, grid, 256, lds12, st, fa, e0, e1);
+            else launch_timed(k_fused<16, false, BOX>, grid, 256, lds16, st, fa, e0, e1);
             break;
         }
         return fail(BRIEF_ERR_INVALID, "unsupported width");
@@ -708,16 +710,16 @@ static int launch_fused(const FusedArgs &fa, int grid, hipStream_t st, hipEvent_
     return 0;
 }
 
-template <bool TRAIN>
-static int launch_k16(const FusedArgs &fa, int grid, hipStream_t st, int ns)
+template <bool TRAIN, bool BOX = false>
+static int launch_k16(const typename KArgsT<BOX>::type &fa, int grid, hipStream_t st, int ns)
 {
     const int nt = brief_nt(fa.d);
     bool launched = false;
 #define BRIEF_CASE(NTV, COV, NSV)                                                                        \
     if (!launched && nt == NTV && (fa.d.cout == 1) == (COV == 1) && ns == NSV) {                         \
         const size_t lds = sizeof(float) * Cfg16<NTV, NSV>::TOTAL;                                       \
-        if (int rc = dev_attr_once((const void *)k16<NTV, TRAIN, COV, NSV>, (int)lds)) return rc;          \
-        hipLaunchKernelGGL((k16<NTV, TRAIN, COV, NSV>), dim3(grid), dim3(512), lds, st, fa);             \
+        if (int rc = dev_attr_once((const void *)k16<NTV, TRAIN, COV, NSV, 8, BOX>, (int)lds)) return rc; \
+        hipLaunchKernelGGL((k16<NTV, TRAIN, COV, NSV, 8, BOX>), dim3(grid), dim3(512), lds, st, fa);    \
         launched = true;                                                                                 \
     }
     if (nt != 8 && nt != 16) return fail(BRIEF_ERR_INVALID, "unsupported width");
@@ -729,18 +731,18 @@ static int launch_k16(const FusedArgs &fa, int grid, hipStream_t st, int ns)
     return 0;
 }
 
-template <bool TRAIN>
-static int launch_k16_split(FusedArgs &fa, hipStream_t st)
+template <bool TRAIN, bool BOX = false>
+static int launch_k16_split(typename KArgsT<BOX>::type &fa, hipStream_t st)
 {
     const int64_t np = npad16(fa.n);
     const Split16 sp = split16(fa.d, fa.n);
     if (sp.g_body > 0) {
         fa.n_begin = 0; fa.n_end = sp.g_tail > 0 ? sp.n_body : np; fa.rec_base = 0;
-        if (int rc = launch_k16<TRAIN>(fa, sp.g_body, st, 4)) return rc;
+        if (int rc = launch_k16<TRAIN, BOX>(fa, sp.g_body, st, 4)) return rc;
     }
     if (sp.g_tail > 0) {
         fa.n_begin = sp.n_body; fa.n_end = np; fa.rec_base = sp.g_body;
-        if (int rc = launch_k16<TRAIN>(fa, sp.g_tail, st, sp.ns_tail)) return rc;
+        if (int rc = launch_k16<TRAIN, BOX>(fa, sp.g_tail, st, sp.ns_tail)) return rc;
     }
     return 0;
 }
@@ -761,6 +763,64 @@ static int check_batch(const brief_siren_desc *d, const brief_grid_desc *grid, c
     }
     if (train && !b->targets) return fail(BRIEF_ERR_INVALID, "targets required");
     return 0;
+}
+
+// a box of brief_siren_forward_box: ndim == cin, every dim 1 .. 2^31 - 1, and on every axis extent >= 1, step >= 1, start >= 0 and
+// start + step (extent - 1) < dims.  *voxels: the box's voxel count (saturated at 2^63 - 1; every axis is below 2^31)
+static int check_box(const brief_siren_desc *d, const brief_grid_box *box, int64_t *voxels)
+{
+    if (!box) return fail(BRIEF_ERR_INVALID, "null box");
+    if (box->grid.ndim != d->cin) return fail(BRIEF_ERR_INVALID, "box grid.ndim must equal coords_channel");
+    unsigned __int128 total = 1;
+    for (int a = 0; a < box->grid.ndim; ++a) {
+        const int64_t dim = box->grid.dims[a], st = box->start[a], sp = box->step[a], ex = box->extent[a];
+        if (dim < 1 || dim >= ((int64_t)1 << 31)) return fail(BRIEF_ERR_INVALID, "box grid dims must be 1 .. 2^31 - 1");
+        if (ex < 1) return fail(BRIEF_ERR_INVALID, "box extent must be >= 1 on every axis");
+        if (sp < 1) return fail(BRIEF_ERR_INVALID, "box step must be >= 1 on every axis");
+        if (st < 0 || st >= dim || (ex - 1) > (dim - 1 - st) / sp)
+            return fail(BRIEF_ERR_INVALID, "box exceeds the grid: start + step * (extent - 1) must be below dims on every axis");
+        total *= (unsigned __int128)ex;
+    }
+    *voxels = total > (unsigned __int128)INT64_MAX ? INT64_MAX : (int64_t)total;
+    return 0;
+}
+
+// what every inference entry checks besides its sample source: the output, and the scratch of the nets above 1024 features
+static int check_forward(const brief_siren_desc *d, int64_t n, const float *packed, void *out, int out_kind, void *workspace, int64_t workspace_bytes)
+{
+    if (brief_use_wide(*d)) {
+        if (!workspace || workspace_bytes < brief_forward_workspace_bytes(d, n))
+            return fail(BRIEF_ERR_WORKSPACE, "widths above 1024 features evaluate through a scratch of brief_forward_workspace_bytes() bytes");
+    }
+    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
+    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
+    return 0;
+}
+
+// the kernel arguments of an inference launch of n samples, without their source (coordinates / indices / grid / box)
+static void forward_args(FusedArgs &fa, const brief_siren_desc *d, const float *packed, int64_t n, void *out, int out_kind,
+                         float scale_min, float scale_max, double vmin, double vmax, void *workspace)
+{
+    memset(&fa, 0, sizeof(fa));
+    fa.d = *d; fa.pk = packed;
+    fa.n = n;
+    fa.npad = brief_npad(brief_nt(*d), n);
+    fa.out = out; fa.out_kind = out_kind;
+    fa.scale_min = scale_min;
+    fa.den = (float)((double)scale_max - (double)scale_min);
+    fa.span = (float)(vmax - vmin);
+    fa.vmin = (float)vmin;
+    fa.stagger_cus = kCUs; fa.stagger = 0;
+    if (brief_use_wide(*d)) fa.Z = (float *)workspace;      // k_wide<.., false>: the ping-pong planes
+}
+
+template <bool BOX>
+static int launch_forward(typename KArgsT<BOX>::type &fa, hipStream_t st)
+{
+    if (fa.d.precision == BRIEF_PREC_BF16) return launch_k16_split<false, BOX>(fa, st);
+    const FusedPlan fp = fused_plan(fa.d, fa.n, false);
+    fa.pers_wgs = fp.pers_wgs; fa.pers_tiles = fp.pers_tiles;
+    return launch_fused<false, BOX>(fa, fp.grid, st);
 }
 
 extern "C" {
@@ -786,29 +846,39 @@ int brief_siren_forward_ws(const brief_siren_desc *d, const float *packed, const
 {
     if (int rc = check_desc(d)) return rc;
     if (int rc = check_batch(d, grid, batch, false)) return rc;
-    if (brief_use_wide(*d)) {
-        if (!workspace || workspace_bytes < brief_forward_workspace_bytes(d, batch->n))
-            return fail(BRIEF_ERR_WORKSPACE, "widths above 1024 features evaluate through a scratch of brief_forward_workspace_bytes() bytes");
-    }
-    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
-    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
+    if (int rc = check_forward(d, batch->n, packed, out, out_kind, workspace, workspace_bytes)) return rc;
     FusedArgs fa;
-    memset(&fa, 0, sizeof(fa));
-    fa.d = *d; fa.pk = packed;
-    fa.coords = batch->coords; fa.idx = batch->idx; fa.offset = batch->offset; fa.n = batch->n;
+    forward_args(fa, d, packed, batch->n, out, out_kind, scale_min, scale_max, vmin, vmax, workspace);
+    fa.coords = batch->coords; fa.idx = batch->idx; fa.offset = batch->offset;
     fill_grid(fa.grid, grid);
-    fa.npad = brief_npad(brief_nt(*d), batch->n);
-    fa.out = out; fa.out_kind = out_kind;
-    fa.scale_min = scale_min;
-    fa.den = (float)((double)scale_max - (double)scale_min);
-    fa.span = (float)(vmax - vmin);
-    fa.vmin = (float)vmin;
-    fa.stagger_cus = kCUs; fa.stagger = 0;
-    if (brief_use_wide(*d)) fa.Z = (float *)workspace;      // k_wide<.., false>: the ping-pong planes
-    if (d->precision == BRIEF_PREC_BF16) return launch_k16_split<false>(fa, (hipStream_t)stream);
-    const FusedPlan fp = fused_plan(*d, batch->n, false);
-    fa.pers_wgs = fp.pers_wgs; fa.pers_tiles = fp.pers_tiles;
-    return launch_fused<false>(fa, fp.grid, (hipStream_t)stream);
+    return launch_forward<false>(fa, (hipStream_t)stream);
+}
+
+int brief_siren_forward_box(const brief_siren_desc *d, const float *packed, const brief_grid_box *box,
+                            int64_t offset, int64_t n, void *out, int out_kind,
+                            float scale_min, float scale_max, double vmin, double vmax,
+                            void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (int rc = check_desc(d)) return rc;
+    int64_t voxels = 0;
+    if (int rc = check_box(d, box, &voxels)) return rc;
+    if (n < 1) return fail(BRIEF_ERR_INVALID, "empty batch");
+    if (offset < 0 || offset > voxels - n) return fail(BRIEF_ERR_INVALID, "offset + n exceeds the box's voxel count");
+    if (int rc = check_forward(d, n, packed, out, out_kind, workspace, workspace_bytes)) return rc;
+    FusedBoxArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    forward_args(fa, d, packed, n, out, out_kind, scale_min, scale_max, vmin, vmax, workspace);
+    fa.offset = offset;
+    fill_grid(fa.grid, &box->grid);
+    for (int a = 0; a < 3; ++a) {
+        const bool used = a < box->grid.ndim;
+        fa.box.start[a] = used ? box->start[a] : 0;
+        fa.box.step[a] = used ? box->step[a] : 1;
+        fa.box.extent[a] = used ? box->extent[a] : 1;
+        fa.box.magic[a] = ~(uint64_t)0 / (uint64_t)fa.box.extent[a] + 1;
+    }
+    fa.box.fast = voxels < ((int64_t)1 << 32);
+    return launch_forward<true>(fa, (hipStream_t)stream);
 }
 
 struct UpdatePayload { OptimScalars opt; float *params, *s1, *s2, *pk; };

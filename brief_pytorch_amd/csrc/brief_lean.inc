@@ -289,9 +289,10 @@ __device__ __forceinline__ void lean_chain_ct(f32x16 (&acc)[SH][MTW], __amdgpu_b
 constexpr int lean_wpe(int SH, int MTW) { return SH == 1 && MTW <= 2 ? BRIEF_LEAN_WPE2 : (SH == 2 || MTW <= 4 ? 2 : 1); }
 
 // RM: how the tiles left over by nt % 4 are dealt (lean_chain_rt, lean_chain_rt3): the host picks the instantiation nt % 4
-template <int SH, int MTW, int NTC, bool TRAIN, int RM = 0>
-__global__ __launch_bounds__(256, lean_wpe(SH, MTW)) void k_lean(const FusedArgs a)
+template <int SH, int MTW, int NTC, bool TRAIN, int RM = 0, bool BOX = false>      // BOX: inference over a box of the grid (box_coords)
+__global__ __launch_bounds__(256, lean_wpe(SH, MTW)) void k_lean(const typename KArgsT<BOX>::type a)
 {
+    static_assert(!(TRAIN && BOX), "the box mapping is an inference instantiation");
     static_assert(SH == 1 || SH == 2, "one or two 32-sample halves per tile");
     static_assert(RM == 0 || (NTC == 0 && SH == 1 && (MTW >= 2 || RM == 3)), "shared left-over tiles: run-time widths only (MTW = 1: the three tiles of a 3-tile net)");
     constexpr int TROWS = 32 * MTW;                    // local features one wave owns
@@ -388,7 +389,7 @@ __global__ __launch_bounds__(256, lean_wpe(SH, MTW)) void k_lean(const FusedArgs
                     c1 = k_co[j * cin + 1];
                     if (cin == 3) c2 = k_co[j * cin + 2];
                 } else {
-                    grid_coords(kg, cin, j, c0, c1, c2);
+                    sample_coords<BOX>(kg, cin, j, c0, c1, c2);
                 }
             }
             if (SH == 2) {

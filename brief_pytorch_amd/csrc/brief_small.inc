@@ -19,7 +19,7 @@
 typedef const __attribute__((address_space(4))) FusedArgs *kargs_t;
 // AP: where the job's FusedArgs live — the kernarg segment (k_small: the kernel's only argument) or a table entry in global memory
 // (k_small_group: one entry per co-trained job); k_idx / rng_step: this step's index set and Philox step (per-step values)
-template <typename AP>
+template <bool BOX = false, typename AP>      // BOX: k16's box instantiations (the kernarg segment holds the box)
 __device__ __forceinline__ void small_inputs(AP ap, const int64_t *k_idx, uint64_t rng_step, int cin, int cout, int64_t n, float4 &xo, float4 &yo, float4 &wo)
 {
     asm volatile("" : "+s"(ap));
@@ -52,7 +52,7 @@ __device__ __forceinline__ void small_inputs(AP ap, const int64_t *k_idx, uint64
             kg.ndim = ap->grid.ndim; kg.lo = ap->grid.lo; kg.hi = ap->grid.hi; kg.fast = ap->grid.fast;
 #pragma unroll
             for (int ax = 0; ax < 3; ++ax) { kg.dims[ax] = ap->grid.dims[ax]; kg.step[ax] = ap->grid.step[ax]; kg.magic[ax] = ap->grid.magic[ax]; }
-            grid_coords(kg, cin, j, x0, x1, x2);
+            sample_coords<BOX>(kg, cin, j, x0, x1, x2);
         }
     }
     xo = make_float4(x0, x1, x2, 0.f);

@@ -93,9 +93,10 @@ __device__ __forceinline__ void wide_store_image(float4 *plane, int mt, int lane
     asm volatile("s_nop 2" ::: "memory");
 }
 
-template <int MTW, bool TRAIN>
-__global__ __launch_bounds__(256, 1) void k_wide(const FusedArgs a)
+template <int MTW, bool TRAIN, bool BOX = false>      // BOX: inference over a box of the grid (box_coords)
+__global__ __launch_bounds__(256, 1) void k_wide(const typename KArgsT<BOX>::type a)
 {
+    static_assert(!(TRAIN && BOX), "the box mapping is an inference instantiation");
     constexpr int TROWS = 32 * MTW;                    // local features of one wave in one pass
     constexpr int RS = (TROWS + 63) / 64;
     const brief_siren_desc &d = a.d;
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(256, 1) void k_wide(const FusedArgs a)
                 kg.ndim = ap->grid.ndim; kg.lo = ap->grid.lo; kg.hi = ap->grid.hi; kg.fast = ap->grid.fast;
 #pragma unroll
                 for (int ax = 0; ax < 3; ++ax) { kg.dims[ax] = ap->grid.dims[ax]; kg.step[ax] = ap->grid.step[ax]; kg.magic[ax] = ap->grid.magic[ax]; }
-                grid_coords(kg, cin, j, x0, x1, x2);
+                sample_coords<BOX>(kg, cin, j, x0, x1, x2);
             }
         }
         // this tile's block of plane l: TRAIN — the stash planes (Z: phases of layers 0 .. L-2, D: deltas of layers 1 .. L-2);

@@ -204,9 +204,11 @@ __device__ __forceinline__ void x3_chain2(f32x16 (&acc)[2][2], const X3Pre<8> &p
     }
 }
 
-template <bool TRAIN>      // false: inference (forward / decode_grid) — the forward half of the same walk, output written by the head
-__global__ __launch_bounds__(256, 2) void k_fused_x3(const FusedArgs a)
+template <bool TRAIN, bool BOX = false>      // false: inference (forward / decode_grid) — the forward half of the same walk, output written by the head;
+                                             // BOX: inference over a box of the grid (box_coords)
+__global__ __launch_bounds__(256, 2) void k_fused_x3(const typename KArgsT<BOX>::type a)
 {
+    static_assert(!(TRAIN && BOX), "the box mapping is an inference instantiation");
 #ifdef BRIEF_STAMPS
     float st_acc[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     long long st_last = clock64();
@@ -290,7 +292,7 @@ __global__ __launch_bounds__(256, 2) void k_fused_x3(const FusedArgs a)
                     c1 = k_co[j * cin + 1];
                     if (cin == 3) c2 = k_co[j * cin + 2];
                 } else {
-                    grid_coords(kg, cin, j, c0, c1, c2);
+                    sample_coords<BOX>(kg, cin, j, c0, c1, c2);
                 }
             }
             const int jl = (int)(uint32_t)(uint64_t)j, jh = (int)(uint32_t)((uint64_t)j >> 32);

@@ -19,8 +19,10 @@ import numpy as np
 import torch
 
 from . import _lib, config
+from . import region as region_mod
 from .fit import Fitter
-from .io import get_folder_size, get_type_max, invnormalize_data, minmaxany_range, normalize_data, normalize_data_device, save_yaml, load_yaml
+from .io import (get_folder_size, get_type_max, invnormalize_data, minmaxany_range, normalize_data, normalize_data_device, range_limit, save_yaml,
+                 load_yaml)
 from .metrics import cal_ssim, eval_performance, gpu_eval_u16, gpu_ssim_u16, psnr_from_sse
 from .misc import (alloc_param, cal_divide_num, divide_data, merge_divided_data, mip_ops, save_mips, parse_checkpoints,
                    parse_chunk_name, parse_weight, preprocess, preprocess_is_identity, weight_is_unit)
@@ -183,6 +185,54 @@ class NFGR:
             dec = NFGR.decompress(opt, opj(module_save_dir, chunk_name, "module"), opj(sideinfos_save_dir, chunk_name, "sideinfos.yaml"), self.device)
             parts.append({"data": dec, "name": chunk_name, **parse_chunk_name(chunk_name)})
         return merge_divided_data(parts, data_shape)
+
+    # ---- region decode: a box of the volume without evaluating the rest (brief_siren_forward_box)
+    @staticmethod
+    def decompress_region(opt, module_path, sideinfos, region, step=1, shape=None, device="cuda"):
+        """NFGR.decompress(opt, module_path, sideinfos)[region] evaluated on the region alone.  region: a tuple of slices of the
+        spatial axes (or 'z0:z1,y0:y1,x0:x1'), numpy semantics, nothing clipped (brief_pytorch_amd/region.py); `step` is the
+        stride of the axes whose slice has none.  shape: evaluate the net on the linspace grid of that spatial shape instead of
+        the fitted one (a resampled view); region and step then index that grid.  Normalisation, dtype and the pointwise
+        Decompress.postprocess are decompress's; a denoise through a binary opening (not local to a voxel) raises."""
+        if isinstance(opt, str):
+            opt = config.load(opt)
+        if isinstance(sideinfos, str):
+            sideinfos = load_yaml(sideinfos)
+        cf = copy.deepcopy(opt.CompressFramework)
+        pp = cf.Decompress.postprocess
+        dtype = np.dtype(sideinfos["dtype"])
+        _region_postprocess_check(dtype, pp)
+        data_shape = list(sideinfos["data_shape"])
+        dims = data_shape[:-1]
+        if shape is not None:
+            shape = [int(v) for v in shape]
+            if len(shape) != len(dims) or any(v < 1 for v in shape):
+                raise ValueError("shape %s does not fit the %d spatial axes of the artefact" % (shape, len(dims)))
+            dims = shape
+        start, stop, stp = region_mod.normalize_region(dims, region, step)
+        cf.Module.phi.features = sideinfos["phi_features"]
+        cf.Module.phi.name = sideinfos["phi_name"]
+        phi = init_phi({**dict(cf.Module.phi), "precision": str(sideinfos.get("phi_precision", cf.Compress.get("precision", "fp32")))})
+        load_model(phi, module_path, "cpu")
+        phi.to(device)
+        lo, hi = _coords_range(cf.Compress.coords_mode)
+        rng = minmaxany_range(cf.Normalize.name)
+        if rng is not None and sideinfos["dtype"] in ("uint8", "uint16"):
+            kind = "u8" if sideinfos["dtype"] == "uint8" else "u16"
+            data = phi.decode_box(dims, start, stop, stp, lo, hi, out_kind=kind, scale=rng, vrange=(sideinfos["min"], sideinfos["max"])).cpu().numpy()
+        else:
+            yhat = phi.decode_box(dims, start, stop, stp, lo, hi).cpu()
+            data = invnormalize_data(yhat, sideinfos, cf.Normalize.name)
+        return preprocess(data, pp.denoise.level, False, pp.clip)
+
+    def decompress_divide_region(self, orig_sideinfos_path, module_save_dir, sideinfos_save_dir, region, step=1, opt=None, shape=None):
+        """decompress_divide(...)[region] evaluated on the region alone: only the blocks whose inclusive ranges meet it are decoded,
+        each on its own grid over its part of the region (the stride stays on the region's lattice across block faces), and merged
+        with merge_divided_data's arithmetic (float32 +=, clip to the dtype's max, cast); voxels no block covers are 0."""
+        if shape is not None:
+            raise ValueError("resampling (shape) is not defined for a DivideTask artefact: every block has its own linspace grid")
+        return decompress_divide_region(opt if opt is not None else _wrap(self.opt), orig_sideinfos_path, module_save_dir, sideinfos_save_dir,
+                                        region, step, self.device)
 
     # ---- SingleTask encode (main.py:322-454)
     def prepare_fit(self, data_path, data=None, logdir=None):
@@ -652,6 +702,46 @@ class NFGR:
 
 
 # ------------------------------------------------------------------------------------------ helpers
+def _region_postprocess_check(dtype, pp):
+    """a region equals the slice of the whole decode only where Decompress.postprocess is local to a voxel: the clip and a plain
+    threshold are; a denoise through a binary opening (denoise.close) of a non-zero level is not.  (At level <= 0 the opening
+    only zeroes voxels the clip, whose floor is >= 0, sends to the same value, so a threshold gives the same result.)"""
+    if pp.denoise.level > 0 and pp.denoise.close is not False:
+        raise ValueError("Decompress.postprocess.denoise (level %s through a binary opening) is not local to a voxel: a region "
+                         "cannot equal the slice of the whole decode; decode the whole volume instead" % pp.denoise.level)
+    range_limit(np.zeros(1, dtype), pp.clip)      # the clip's own checks, before any decode
+
+
+def decompress_divide_region(opt, orig_sideinfos_path, module_save_dir, sideinfos_save_dir, region, step=1, device="cuda"):
+    """the region of a stored DivideTask artefact (NFGR.decompress_divide_region); opt: the whole option tree"""
+    if isinstance(opt, str):
+        opt = config.load(opt)
+    orig = load_yaml(orig_sideinfos_path) if isinstance(orig_sideinfos_path, str) else orig_sideinfos_path
+    data_shape = list(orig["data_shape"])
+    dims, cout = data_shape[:-1], data_shape[-1]
+    start, stop, stp = region_mod.normalize_region(dims, region, step)
+    ext = region_mod.extents(start, stop, stp)
+    axes = "dhw" if len(dims) == 3 else "hw"
+    names = sorted(os.listdir(module_save_dir))
+    out = np.zeros(ext + [cout], dtype=np.float32)
+    dtype = None
+    for name in names:
+        side = load_yaml(opj(sideinfos_save_dir, name, "sideinfos.yaml"))
+        dtype = dtype or np.dtype(side["dtype"])        # merge_divided_data casts to the first block's dtype
+        _region_postprocess_check(np.dtype(side["dtype"]), opt.CompressFramework.Decompress.postprocess)
+        r = parse_chunk_name(name)
+        hit = region_mod.block_intersection(start, stp, ext, [r[a][0] for a in axes], [r[a][1] for a in axes])
+        if hit is None:
+            continue
+        o_lo, o_hi, l_start, l_stop = hit
+        dec = NFGR.decompress_region(opt, opj(module_save_dir, name, "module"), side,
+                                     tuple(slice(b, e) for b, e in zip(l_start, l_stop)), stp, device=device)
+        out[tuple(slice(b, e) for b, e in zip(o_lo, o_hi))] += dec
+    if dtype is None:
+        raise ValueError("no blocks under %s" % module_save_dir)
+    return out.clip(None, get_type_max(np.zeros(1, dtype))).astype(dtype)
+
+
 def _coords_range(mode):
     if mode == "n11":
         return -1.0, 1.0

@@ -15,7 +15,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, region
 
 __all__ = ["SIREN", "init_phi", "ALLPHI", "ALL_CALC_PHI_FEATURES", "ALL_CALC_PHI_PARAM_COUNT",
            "ALL_CHECK_PARAM_COUNT", "get_nnmodule_param_count"]
@@ -339,6 +339,49 @@ class SIREN:
         _lib.check(_lib.lib().brief_siren_forward_ws(C.byref(self.desc), _lib.ptr(self.packed), C.byref(g), C.byref(b), _lib.ptr(out),
                                                      kind, float(scale[0]), float(scale[1]), float(vrange[0]), float(vrange[1]),
                                                      ws, ws_bytes, _lib.stream_ptr()))
+        return out
+
+    # voxels per brief_siren_forward_box call of decode_box: bounds one launch's length and the scratch request of a wide net
+    BOX_CHUNK = 1 << 27
+
+    def decode_box(self, dims, start=None, stop=None, step=1, lo=-1.0, hi=1.0, out_kind="f32", scale=(0.0, 100.0), vrange=(0.0, 1.0),
+                   out=None, chunk=None):
+        """forward over the box start:stop:step (numpy slice semantics per spatial axis) of the linspace grid `dims`, without
+        evaluating the rest of it: equals decode_grid(dims).view(*dims, cout)[slices] bit for bit.  Returns [*extent, cout].
+        start / stop / step: an int, None or one entry per axis; out-of-range bounds, empty boxes and steps below 1 raise
+        ValueError.  `dims` may differ from the fitted shape (a resampled view).  The box runs in calls of at most `chunk` voxels
+        (default BOX_CHUNK) through brief_siren_forward_box's offset / n."""
+        self._require_gpu()
+        self.sync_packed()
+        nd = len(dims)
+        per = (lambda v: [v] * nd if v is None or np.isscalar(v) else list(v))
+        b, e = per(start), per(stop)
+        if len(b) != nd or len(e) != nd:
+            raise ValueError("start / stop need one entry per axis of dims")
+        b0, e0, st = region.normalize_region(dims, tuple(slice(x, y) for x, y in zip(b, e)), step)
+        ext = region.extents(b0, e0, st)
+        total = int(np.prod(ext))
+        kind = {"f32": _lib.OUT_F32, "u8": _lib.OUT_U8, "u16": _lib.OUT_U16}[out_kind]
+        dt = {"f32": torch.float32, "u8": torch.uint8, "u16": torch.uint16}[out_kind]
+        if out is None:
+            out = torch.empty((*ext, self.data_channel), dtype=dt, device=self.params.device)
+        elif out.dtype != dt or out.numel() != total * self.data_channel or not out.is_contiguous():
+            raise ValueError("out must be a contiguous %s tensor of %d elements" % (dt, total * self.data_channel))
+        box = _lib.GridBox()
+        box.grid = self._grid(dims, lo, hi)
+        for a in range(nd):
+            box.start[a], box.step[a], box.extent[a] = b0[a], st[a], ext[a]
+        chunk = int(chunk or self.BOX_CHUNK)
+        if chunk < 1:
+            raise ValueError("chunk must be >= 1")
+        flat = out.view(total, self.data_channel)
+        L = _lib.lib()
+        for off in range(0, total, chunk):
+            cnt = min(chunk, total - off)
+            ws, ws_bytes = self._forward_scratch(cnt)
+            _lib.check(L.brief_siren_forward_box(C.byref(self.desc), _lib.ptr(self.packed), C.byref(box), off, cnt, _lib.ptr(flat[off:off + cnt]),
+                                                 kind, float(scale[0]), float(scale[1]), float(vrange[0]), float(vrange[1]),
+                                                 ws, ws_bytes, _lib.stream_ptr()))
         return out
 
     def train_step(self, n, targets, idx=None, coords=None, weights=None, grid=None, offset=0,

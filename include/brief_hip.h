@@ -115,6 +115,23 @@ int brief_siren_forward_ws(const brief_siren_desc *d, const float *packed, const
                            const brief_batch_desc *batch, void *out, int out_kind,
                            float scale_min, float scale_max, double vmin, double vmax, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* A strided box of a grid: box voxel (i0, i1, i2), in (d,h,w) order ((h,w) for ndim 2), is grid voxel start[a] + step[a] * i[a] on every
+ * axis; its coordinates are the grid's (create_flattened_coords on grid.dims), bit for bit.  grid.dims may differ from the shape the net
+ * was fitted on (a resampled view).  Entries past grid.ndim are ignored. */
+typedef struct {
+    brief_grid_desc grid;
+    int64_t start[3], step[3], extent[3];
+} brief_grid_box;
+/* Inference over a box without evaluating the rest of the grid (region of interest, strided preview, resampling): sample n of the call
+ * is box voxel b = offset + n in box-linear order ((i0 * extent[1] + i1) * extent[2] + i2), and out row n holds it, with the out_kind
+ * epilogue of brief_siren_forward.  Refused with BRIEF_ERR_INVALID: grid.ndim != cin, a dim outside 1 .. 2^31 - 1, extent < 1,
+ * step < 1, start < 0 or start + step (extent - 1) >= dims on an axis, n < 1, offset < 0 or offset + n beyond the box's voxel count.
+ * Scratch as brief_siren_forward_ws: brief_forward_workspace_bytes(d, n) bytes (BRIEF_ERR_WORKSPACE above 1024 features without). */
+int brief_siren_forward_box(const brief_siren_desc *d, const float *packed, const brief_grid_box *box,
+                            int64_t offset, int64_t n, void *out, int out_kind,
+                            float scale_min, float scale_max, double vmin, double vmax,
+                            void *workspace, int64_t workspace_bytes, void *stream);
+
 /* zero_grad + forward + loss + backward of main.py:385-396 for one batch.
  * grads: canonical packed layout, fully overwritten.  loss_out: one float (mean loss).
  * yhat_out: optional [n,cout].  thr: normalised weight_thres (0 disables, main.py:178-179). */
