@@ -52,6 +52,15 @@ class FitJob(C.Structure):          # brief_fit_job
                 ("lr_table", C.POINTER(C.c_double)), ("beta1_table", C.POINTER(C.c_double)), ("idx_stride", C.c_int64)]
 
 
+class FfnDesc(C.Structure):         # brief_ffn_desc
+    _fields_ = [("cin", C.c_int32), ("cout", C.c_int32), ("layers", C.c_int32), ("features", C.c_int32),
+                ("embsize", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FfnFitJob(C.Structure):       # brief_ffn_fit_job: brief_fit_job's fields after the desc
+    _fields_ = [("desc", FfnDesc)] + FitJob._fields_[1:]
+
+
 LOSS_KIND = {"datal2": 0, "datasmoothl1": 1, "external": 2}
 OPT_KIND = {"Adamax": 0, "Adam": 1, "SGD": 2}
 OUT_F32, OUT_U8, OUT_U16 = 0, 1, 2
@@ -61,7 +70,9 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_train_workspace_bytes", "brief_siren_repack", "brief_siren_forward", "brief_forward_workspace_bytes", "brief_siren_forward_ws", "brief_siren_forward_box", "brief_siren_train_step", "brief_siren_fit_step",
            "brief_siren_fit", "brief_multi_fit",
            "brief_optim_step", "brief_sample_indices", "brief_sse_u16", "brief_profile_enable", "brief_profile_fused", "brief_deblock_edge", "brief_ssim_u16", "brief_ssim_partial_count",
-           "brief_sincos_probe", "brief_cu_count"]
+           "brief_sincos_probe", "brief_cu_count",
+           "brief_ffn_param_count", "brief_ffn_packed_count", "brief_ffn_train_workspace_bytes", "brief_ffn_repack", "brief_ffn_forward",
+           "brief_ffn_forward_box", "brief_ffn_train_step", "brief_ffn_fit"]
 
 
 def needs_build():
@@ -144,6 +155,17 @@ def lib():
     L.brief_cu_count.restype = C.c_int
     L.brief_profile_enable.argtypes = [C.c_int]
     L.brief_profile_fused.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    fp = C.POINTER(FfnDesc)
+    for name in ("brief_ffn_param_count", "brief_ffn_packed_count"):
+        getattr(L, name).restype = C.c_int64
+        getattr(L, name).argtypes = [fp]
+    L.brief_ffn_train_workspace_bytes.restype = C.c_int64
+    L.brief_ffn_train_workspace_bytes.argtypes = [fp, C.c_int64]
+    L.brief_ffn_repack.argtypes = [fp, vp, vp, vp]
+    L.brief_ffn_forward.argtypes = [fp, vp, gp, bp, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
+    L.brief_ffn_forward_box.argtypes = [fp, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
+    L.brief_ffn_train_step.argtypes = [fp, vp, gp, bp, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, C.c_int64, vp]
+    L.brief_ffn_fit.argtypes = [C.POINTER(FfnFitJob), C.c_int64, vp]
     _LIB = L
     return L
 

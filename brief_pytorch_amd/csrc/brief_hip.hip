@@ -53,6 +53,7 @@
 #include "brief_reduce.inc"     // optimizer, k_reduce, k_reduce_group
 #include "brief_bf16.inc"       // bf16: k16, k_wgrad16, k_reduce16
 #include "brief_aux.inc"        // k_repack, index stream, metrics, deblocking filter
+#include "brief_ffn.inc"        // FFN: k_ffn_fwd, k_ffn_wgrad, k_ffn_reduce, k_ffn_repack
 
 // =============================================================================================
 // C-ABI
@@ -1519,6 +1520,305 @@ int brief_sse_u16(const uint16_t *a, const uint16_t *b, int64_t n, double *sse_o
     hipLaunchKernelGGL(k_sse_u16, dim3(1024), dim3(256), 0, st, a, b, n, acc);
     hipLaunchKernelGGL(k_u64_to_double, dim3(1), dim3(1), 0, st, acc, sse_out);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}   // extern "C"
+
+// =============================================================================================
+// FFN (Fourier-feature network, brief_ffn.inc): train step = k_ffn_fwd<TRAIN> + k_ffn_wgrad + k_ffn_reduce (+ k_ffn_repack after an update)
+static int check_ffn_desc(const brief_ffn_desc *d)
+{
+    if (!d) return fail(BRIEF_ERR_INVALID, "null desc");
+    if (d->cin != 2 && d->cin != 3) return fail(BRIEF_ERR_INVALID, "FFN: coords_channel must be 2 or 3");
+    if (d->cout < 1 || d->cout > 4) return fail(BRIEF_ERR_INVALID, "FFN: data_channel must be 1..4");
+    if (d->layers < 2) return fail(BRIEF_ERR_INVALID, "FFN: layers must be >= 2");
+    if (d->features < 1 || d->features > 1024) return fail(BRIEF_ERR_INVALID, "FFN: features must be 1..1024 on the fused path");
+    if (d->embsize < 1 || d->embsize > 512) return fail(BRIEF_ERR_INVALID, "FFN: embsize must be 1..512 on the fused path");
+    if (d->reserved != 0) return fail(BRIEF_ERR_INVALID, "FFN: reserved must be 0 (skip connections are not supported)");
+    return 0;
+}
+
+static int ffn_lds_bytes(const brief_ffn_desc &d)
+{
+    const FfnLayout l = ffn_layout(d);
+    return (int)sizeof(float) * (32 * (l.K0 > l.FP ? l.K0 : l.FP) + 128);
+}
+// persistent grid: up to two workgroups per CU (one wave per SIMD each), fewer when the LDS image does not fit twice
+static int ffn_grid(const brief_ffn_desc &d, int64_t n)
+{
+    const int64_t tiles = (n + 31) / 32;
+    const int by_lds = (160 * 1024) / ffn_lds_bytes(d);
+    const int64_t cap = (int64_t)kCUs * (by_lds < 2 ? (by_lds > 0 ? by_lds : 1) : 2);
+    return (int)(tiles < cap ? tiles : cap);
+}
+static const int64_t kFfnLossParts = 4096;      // >= any ffn_grid
+struct FfnWs { int64_t npad, H, D, EMB, G, lpart, slabs, total, chunk; int nsplit, waves; };
+static void ffn_wgrad_layer_shape(const brief_ffn_desc &d, int l, int &arows, int &brows)
+{
+    const FfnLayout lay = ffn_layout(d);
+    arows = l == d.layers - 1 ? d.cout : d.features;
+    brows = l == 0 ? lay.K0 : d.features;
+}
+static FfnWs ffn_ws_layout(const brief_ffn_desc &d, int64_t n)
+{
+    const FfnLayout lay = ffn_layout(d);
+    FfnWs w;
+    w.npad = (n + 31) / 32 * 32;
+    const int64_t plane = (int64_t)lay.FP * w.npad;
+    w.H = 0;
+    w.D = w.H + (int64_t)(d.layers - 1) * plane;
+    w.EMB = w.D + (int64_t)(d.layers - 1) * plane;
+    w.G = w.EMB + (int64_t)lay.K0 * w.npad;
+    w.lpart = w.G + 4 * w.npad;
+    w.slabs = w.lpart + kFfnLossParts;
+    w.waves = 0;
+    for (int l = 0; l < d.layers; ++l) {
+        int ar, br;
+        ffn_wgrad_layer_shape(d, l, ar, br);
+        w.waves += ((ar + 63) / 64) * ((br + 63) / 64);
+    }
+    const int64_t wgs = (w.waves + 3) / 4;
+    int64_t ns = (8 * (int64_t)kCUs + wgs - 1) / wgs;      // K-splits: about eight workgroups per CU (the latency of the plane loads needs waves in flight)
+    if (ns > 64) ns = 64;
+    if (ns > w.npad / 256) ns = w.npad / 256;
+    if (ns < 1) ns = 1;
+    w.chunk = (w.npad / ns + 31) / 32 * 32;
+    w.nsplit = (int)((w.npad + w.chunk - 1) / w.chunk);
+    const int64_t mlp = ffn_canon_count(d) - ffn_canon_w0(d);
+    w.total = w.slabs + (int64_t)w.nsplit * mlp;
+    return w;
+}
+
+template <bool TRAIN, bool BOX>
+static int launch_ffn_fwd(const FfnArgs &fa, int grid, hipStream_t st)
+{
+    const int mtw = (fa.nt + 3) / 4;
+    const int lds = ffn_lds_bytes(fa.d);
+    const void *fn = nullptr;
+    switch (mtw) {
+#define FFN_CASE(M) case M: fn = (const void *)k_ffn_fwd<M, TRAIN, BOX>; break;
+        FFN_CASE(1) FFN_CASE(2) FFN_CASE(3) FFN_CASE(4) FFN_CASE(5) FFN_CASE(6) FFN_CASE(7) FFN_CASE(8)
+#undef FFN_CASE
+        default: return fail(BRIEF_ERR_INVALID, "FFN: features must be 1..1024 on the fused path");
+    }
+    if (int rc = dev_attr_once(fn, lds)) return rc;
+    switch (mtw) {
+#define FFN_CASE(M) case M: hipLaunchKernelGGL((k_ffn_fwd<M, TRAIN, BOX>), dim3(grid), dim3(256), lds, st, fa); break;
+        FFN_CASE(1) FFN_CASE(2) FFN_CASE(3) FFN_CASE(4) FFN_CASE(5) FFN_CASE(6) FFN_CASE(7) FFN_CASE(8)
+#undef FFN_CASE
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static void ffn_forward_args(FfnArgs &fa, const brief_ffn_desc *d, const float *packed, int64_t n, void *out, int out_kind,
+                             float scale_min, float scale_max, double vmin, double vmax)
+{
+    memset(&fa, 0, sizeof(fa));
+    const FfnLayout lay = ffn_layout(*d);
+    fa.d = *d; fa.nt = lay.nt; fa.EP = lay.EP; fa.pk = packed;
+    fa.n = n; fa.npad = (n + 31) / 32 * 32;
+    fa.out = out; fa.out_kind = out_kind;
+    fa.scale_min = scale_min;
+    fa.den = (float)((double)scale_max - (double)scale_min);
+    fa.span = (float)(vmax - vmin);
+    fa.vmin = (float)vmin;
+}
+
+struct FfnUpdate { OptimScalars opt; float *params, *s1, *s2, *pk; };
+
+static int ffn_train_impl(const brief_ffn_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                          int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
+                          void *workspace, int64_t workspace_bytes, void *stream, const FfnUpdate *upd)
+{
+    if (int rc = check_ffn_desc(d)) return rc;
+    brief_siren_desc sd;      // check_batch reads cin only
+    memset(&sd, 0, sizeof(sd));
+    sd.cin = d->cin;
+    if (int rc = check_batch(&sd, grid, batch, true)) return rc;
+    if (!packed || !grads || !loss_out || !workspace) return fail(BRIEF_ERR_INVALID, "null buffer");
+    if (loss_kind < BRIEF_LOSS_L2 || loss_kind > BRIEF_LOSS_EXTERNAL) return fail(BRIEF_ERR_INVALID, "bad loss_kind");
+    const FfnWs w = ffn_ws_layout(*d, batch->n);
+    if (workspace_bytes < w.total * (int64_t)sizeof(float)) return fail(BRIEF_ERR_WORKSPACE, "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    float *ws = (float *)workspace;
+    const FfnLayout lay = ffn_layout(*d);
+    FfnArgs fa;
+    ffn_forward_args(fa, d, packed, batch->n, nullptr, 0, 0.f, 1.f, 0.0, 1.0);
+    fa.coords = batch->coords; fa.targets = batch->targets; fa.weights = batch->weights;
+    fa.idx = batch->idx; fa.offset = batch->offset;
+    if (!batch->idx && batch->rng_pop > 0) { fa.rng_pop = (uint64_t)batch->rng_pop; fa.rng_seed = batch->rng_seed; fa.rng_step = batch->rng_step; }
+    fill_grid(fa.grid, grid);
+    fa.loss_kind = loss_kind; fa.thr = thr; fa.beta = beta;
+    fa.inv_count = (float)(1.0 / ((double)batch->n * d->cout));
+    fa.H = ws + w.H; fa.D = ws + w.D; fa.EMB = ws + w.EMB; fa.G = ws + w.G; fa.lpart = ws + w.lpart;
+    fa.npad = w.npad; fa.yhat_out = yhat_out;
+    const int grid1 = ffn_grid(*d, batch->n);
+    const bool prof = prof_live();
+    hipEvent_t *pev = prof ? dev_state()->prof_ev : nullptr;
+    if (prof) HIP_TRY(hipEventRecord(pev[2 * g_prof_n], st));
+    if (int rc = launch_ffn_fwd<true, false>(fa, grid1, st)) return rc;
+    if (prof) { HIP_TRY(hipEventRecord(pev[2 * g_prof_n + 1], st)); ++g_prof_n; }
+    // weight gradients, at most FFN_WGRAD_LAYERS layers per launch
+    const int64_t bv = ffn_canon_w0(*d), mlp = ffn_canon_count(*d) - bv;
+    const int64_t plane = (int64_t)lay.FP * w.npad;
+    for (int l0 = 0; l0 < d->layers; l0 += FFN_WGRAD_LAYERS) {
+        FfnWgradArgs wa;
+        memset(&wa, 0, sizeof(wa));
+        wa.EP = lay.EP; wa.E = d->embsize; wa.npad = w.npad; wa.chunk = w.chunk; wa.mlp = mlp; wa.slabs = ws + w.slabs;
+        int waves = 0;
+        for (int l = l0; l < d->layers && l < l0 + FFN_WGRAD_LAYERS; ++l) {
+            FfnWgradLayer &Ly = wa.lay[l - l0];
+            ffn_wgrad_layer_shape(*d, l, Ly.arows, Ly.brows);
+            Ly.mb = (Ly.arows + 63) / 64; Ly.nb = (Ly.brows + 63) / 64;
+            Ly.wave_begin = waves;
+            waves += Ly.mb * Ly.nb;
+            if (l == d->layers - 1) {
+                Ly.A = ws + w.G;
+                Ly.B = ws + w.H + (int64_t)(d->layers - 2) * plane;
+                Ly.w_off = ffn_canon_head(*d) - bv; Ly.ldw = d->features;
+                Ly.b_off = Ly.w_off + (int64_t)d->cout * d->features;
+            } else if (l == 0) {
+                Ly.A = ws + w.D; Ly.B = ws + w.EMB; Ly.emb = 1;
+                Ly.w_off = 0; Ly.ldw = 2 * d->embsize;
+                Ly.b_off = 2 * (int64_t)d->embsize * d->features;
+            } else {
+                Ly.A = ws + w.D + (int64_t)l * plane;
+                Ly.B = ws + w.H + (int64_t)(l - 1) * plane;
+                Ly.w_off = ffn_canon_hidden(*d, l) - bv; Ly.ldw = d->features;
+                Ly.b_off = Ly.w_off + (int64_t)d->features * d->features;
+            }
+        }
+        wa.nlayers = (d->layers - l0) < FFN_WGRAD_LAYERS ? (d->layers - l0) : FFN_WGRAD_LAYERS;
+        wa.waves = waves;
+        hipLaunchKernelGGL(k_ffn_wgrad, dim3((unsigned)((waves + 3) / 4), (unsigned)w.nsplit), dim3(256), 0, st, wa);
+        HIP_TRY(hipGetLastError());
+    }
+    const int64_t nred = mlp > bv ? mlp : bv;
+    OptimScalars o;
+    memset(&o, 0, sizeof(o));
+    if (upd) o = upd->opt;
+    hipLaunchKernelGGL(k_ffn_reduce, dim3((unsigned)((nred + 255) / 256)), dim3(256), 0, st, (const float *)(ws + w.slabs), w.nsplit, mlp, bv, grads,
+                       (const float *)(ws + w.lpart), grid1, loss_kind == BRIEF_LOSS_EXTERNAL ? 0.f : fa.inv_count, loss_out,
+                       upd ? 1 : 0, o, upd ? upd->params : nullptr, upd ? upd->s1 : nullptr, upd ? upd->s2 : nullptr);
+    HIP_TRY(hipGetLastError());
+    if (upd) {
+        hipLaunchKernelGGL(k_ffn_repack, dim3((unsigned)((lay.total + 255) / 256)), dim3(256), 0, st, *d, (const float *)upd->params, upd->pk);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" {
+
+int64_t brief_ffn_param_count(const brief_ffn_desc *d) { return check_ffn_desc(d) ? -1 : ffn_canon_count(*d); }
+int64_t brief_ffn_packed_count(const brief_ffn_desc *d) { return check_ffn_desc(d) ? -1 : ffn_layout(*d).total; }
+int64_t brief_ffn_train_workspace_bytes(const brief_ffn_desc *d, int64_t n)
+{
+    if (check_ffn_desc(d)) return -1;
+    if (n < 1) { fail(BRIEF_ERR_INVALID, "empty batch"); return -1; }
+    return ffn_ws_layout(*d, n).total * (int64_t)sizeof(float);
+}
+
+int brief_ffn_repack(const brief_ffn_desc *d, const float *params, float *packed, void *stream)
+{
+    if (int rc = check_ffn_desc(d)) return rc;
+    if (!params || !packed) return fail(BRIEF_ERR_INVALID, "null buffer");
+    const int64_t total = ffn_layout(*d).total;
+    hipLaunchKernelGGL(k_ffn_repack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *d, params, packed);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_ffn_forward(const brief_ffn_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                      void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream)
+{
+    if (int rc = check_ffn_desc(d)) return rc;
+    brief_siren_desc sd;
+    memset(&sd, 0, sizeof(sd));
+    sd.cin = d->cin;
+    if (int rc = check_batch(&sd, grid, batch, false)) return rc;
+    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
+    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
+    FfnArgs fa;
+    ffn_forward_args(fa, d, packed, batch->n, out, out_kind, scale_min, scale_max, vmin, vmax);
+    fa.coords = batch->coords; fa.idx = batch->idx; fa.offset = batch->offset;
+    fill_grid(fa.grid, grid);
+    return launch_ffn_fwd<false, false>(fa, ffn_grid(*d, batch->n), (hipStream_t)stream);
+}
+
+int brief_ffn_forward_box(const brief_ffn_desc *d, const float *packed, const brief_grid_box *box, int64_t offset, int64_t n,
+                          void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream)
+{
+    if (int rc = check_ffn_desc(d)) return rc;
+    brief_siren_desc sd;
+    memset(&sd, 0, sizeof(sd));
+    sd.cin = d->cin;
+    int64_t voxels = 0;
+    if (int rc = check_box(&sd, box, &voxels)) return rc;
+    if (n < 1) return fail(BRIEF_ERR_INVALID, "empty batch");
+    if (offset < 0 || offset > voxels - n) return fail(BRIEF_ERR_INVALID, "offset + n exceeds the box's voxel count");
+    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
+    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
+    FfnArgs fa;
+    ffn_forward_args(fa, d, packed, n, out, out_kind, scale_min, scale_max, vmin, vmax);
+    fa.offset = offset;
+    fill_grid(fa.grid, &box->grid);
+    double total = 1.0;
+    for (int a = 0; a < 3; ++a) {
+        const bool on = a < box->grid.ndim;
+        fa.box.start[a] = on ? box->start[a] : 0;
+        fa.box.step[a] = on ? box->step[a] : 1;
+        fa.box.extent[a] = on ? box->extent[a] : 1;
+        fa.box.magic[a] = ~(uint64_t)0 / (uint64_t)fa.box.extent[a] + 1;
+        total *= (double)fa.box.extent[a];
+    }
+    fa.box.fast = total < 4294967296.0;
+    return launch_ffn_fwd<false, true>(fa, ffn_grid(*d, n), (hipStream_t)stream);
+}
+
+int brief_ffn_train_step(const brief_ffn_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                         int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
+                         void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return ffn_train_impl(d, packed, grid, batch, loss_kind, thr, beta, grads, loss_out, yhat_out, workspace, workspace_bytes, stream, nullptr);
+}
+
+int brief_ffn_fit(const brief_ffn_fit_job *j, int64_t steps, void *stream)
+{
+    if (!j) return fail(BRIEF_ERR_INVALID, "null job");
+    if (int rc = check_ffn_desc(&j->desc)) return rc;
+    if (steps < 0) return fail(BRIEF_ERR_INVALID, "bad step count");
+    if (j->batch.idx && j->idx_stride <= 0) return fail(BRIEF_ERR_INVALID, "brief_ffn_fit needs idx_stride > 0 with batch.idx (one index set per step)");
+    if (j->batch.idx && j->idx_stride < j->batch.n) return fail(BRIEF_ERR_INVALID, "idx_stride is smaller than the batch");
+    if (!j->params || !j->packed || !j->grads || !j->loss_out || !j->workspace) return fail(BRIEF_ERR_INVALID, "null buffer");
+    if (j->t0 < 0) return fail(BRIEF_ERR_INVALID, "bad step count");
+    if (j->n_milestones < 0 || (j->n_milestones > 0 && !j->milestones)) return fail(BRIEF_ERR_INVALID, "bad lr milestones");
+    if (j->optim_kind < BRIEF_OPT_ADAMAX || j->optim_kind > BRIEF_OPT_SGD) return fail(BRIEF_ERR_INVALID, "bad optimizer kind");
+    if (j->optim_kind != BRIEF_OPT_SGD && (!j->state1 || !j->state2)) return fail(BRIEF_ERR_INVALID, "optimizer state required");
+    hipStream_t st = (hipStream_t)stream;
+    // the schedule fields mean what they mean in brief_fit_job: brief_siren_fit's rule (fit_job_lr) evaluates them
+    brief_fit_job sched;
+    memset(&sched, 0, sizeof(sched));
+    sched.milestones = j->milestones; sched.n_milestones = j->n_milestones; sched.gamma = j->gamma; sched.t0 = j->t0;
+    sched.lr_table = j->lr_table;
+    double lr = j->lr;
+    for (int64_t k = 0; k < steps; ++k) {
+        const int64_t t = j->t0 + 1 + k;
+        fit_job_lr(&sched, t, k, &lr);
+        brief_batch_desc b = j->batch;
+        if (b.idx) b.idx = b.idx + k * j->idx_stride;
+        else if (b.rng_pop > 0) b.rng_step = (uint64_t)t;
+        FfnUpdate up;
+        up.opt = optim_scalars(j->optim_kind, lr, j->beta1_table ? j->beta1_table[k] : j->beta1, j->beta2, j->eps, t);
+        up.params = j->params; up.s1 = j->state1; up.s2 = j->state2; up.pk = j->packed;
+        if (int rc = ffn_train_impl(&j->desc, j->packed, &j->grid, &b, j->loss_kind, j->thr, j->beta, j->grads,
+                                    j->loss_log ? j->loss_log + k : j->loss_out, nullptr, j->workspace, j->workspace_bytes, (void *)st, &up))
+            return rc;
+    }
+    if (j->loss_log && steps > 0)
+        HIP_TRY(hipMemcpyAsync(j->loss_out, j->loss_log + steps - 1, sizeof(float), hipMemcpyDeviceToDevice, st));
     return 0;
 }
 

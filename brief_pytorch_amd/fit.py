@@ -73,6 +73,10 @@ def cyclic_lr(base_lr, max_lr, step_size_up=2000, step_size_down=None, mode="tri
     return lr_at, beta1_at
 
 
+def _is_ffn(module):
+    return getattr(module, "kind", "SIREN") == "FFN"
+
+
 class Fitter:
     def __init__(self, module, targets, dims, coords_range=(-1.0, 1.0), weights=None, sampler="randompoint",
                  sample_size=100000, optimizer="Adamax", lr=1e-3, scheduler=None, loss="datal2", thr=0.0, beta=0.01,
@@ -159,7 +163,7 @@ class Fitter:
         b = _lib.BatchDesc(None, self.targets.data_ptr(), self.weights.data_ptr() if self.weights is not None else None,
                            idx.data_ptr() if idx is not None else None,
                            0, int(self.n), int(self.pop) if rnd else 0, int(self.seed) if rnd else 0, 0)
-        j = _lib.FitJob()
+        j = _lib.FfnFitJob() if _is_ffn(m) else _lib.FitJob()
         j.desc, j.grid, j.batch = m.desc, g, b
         j.params, j.packed = m.params.data_ptr(), m.packed.data_ptr()
         j.state1, j.state2 = self.s1.data_ptr(), self.s2.data_ptr()
@@ -190,7 +194,8 @@ class Fitter:
         while True:
             k = min(steps, self.max_steps_per_call())
             j, loss_log = self.job(k, log)
-            _lib.check(_lib.lib().brief_siren_fit(C.byref(j), k, _lib.stream_ptr()))
+            fit = _lib.lib().brief_ffn_fit if _is_ffn(self.m) else _lib.lib().brief_siren_fit
+            _lib.check(fit(C.byref(j), k, _lib.stream_ptr()))
             self.t += k
             steps -= k
             if log:
@@ -223,6 +228,16 @@ class MultiFitter:
         self.fitters = list(fitters)
 
     def run(self, steps, log=False):
+        """(brief_multi_fit co-trains SIREN fits only: FFN fits run one after another through their own Fitter.run)"""
+        if any(_is_ffn(f.m) for f in self.fitters):
+            res, sir = [None] * len(self.fitters), [i for i, f in enumerate(self.fitters) if not _is_ffn(f.m)]
+            if sir:
+                for i, r in zip(sir, MultiFitter([self.fitters[i] for i in sir]).run(steps, log)):
+                    res[i] = r
+            for i, f in enumerate(self.fitters):
+                if _is_ffn(f.m):
+                    res[i] = f.run(steps, log)
+            return res
         if not self.fitters:
             return []
         steps, logs = int(steps), [[] for _ in self.fitters]

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib, region
 
-__all__ = ["SIREN", "init_phi", "ALLPHI", "ALL_CALC_PHI_FEATURES", "ALL_CALC_PHI_PARAM_COUNT",
+__all__ = ["SIREN", "FFN", "init_phi", "ALLPHI", "ALL_CALC_PHI_FEATURES", "ALL_CALC_PHI_PARAM_COUNT",
            "ALL_CHECK_PARAM_COUNT", "get_nnmodule_param_count"]
 
 
@@ -259,7 +259,7 @@ class SIREN:
         """refresh the fragment-ordered weight copy after any change of self.params"""
         self._require_gpu()
         if self.packed is None:
-            n = _lib.lib().brief_packed_count(C.byref(self.desc))
+            n = self._abi_packed_count()
             if n < 0:      # (a shape the library refuses, e.g. precision = 'bf16' above 512 features: its message, not a torch allocation error)
                 raise _lib.BriefError(_lib.lib().brief_last_error().decode())
             self.packed = torch.empty(n, dtype=torch.float32, device=self.params.device)
@@ -267,7 +267,7 @@ class SIREN:
         if self.params._version != self._seen_version:      # torch changed the parameters in place (e.g. optimizer.step())
             self._stale = True
         if self._stale:
-            _lib.check(_lib.lib().brief_siren_repack(C.byref(self.desc), _lib.ptr(self.params), _lib.ptr(self.packed), _lib.stream_ptr()))
+            _lib.check(self._abi_repack())
             self._stale = False
             self._seen_version = self.params._version
 
@@ -300,9 +300,7 @@ class SIREN:
         if n == 0:
             return out.view(*lead, self.data_channel)
         b = _lib.BatchDesc(c.data_ptr(), None, None, None, 0, n, 0, 0, 0)
-        ws, ws_bytes = self._forward_scratch(n)
-        _lib.check(_lib.lib().brief_siren_forward_ws(C.byref(self.desc), _lib.ptr(self.packed), None, C.byref(b), _lib.ptr(out),
-                                                     _lib.OUT_F32, 0.0, 1.0, 0.0, 1.0, ws, ws_bytes, _lib.stream_ptr()))
+        _lib.check(self._abi_forward(None, b, out, _lib.OUT_F32, (0.0, 1.0), (0.0, 1.0), n))
         return out.view(*lead, self.data_channel)
 
     def _forward_scratch(self, n):
@@ -335,10 +333,7 @@ class SIREN:
             out = torch.empty((count, self.data_channel), dtype=dt, device=self.params.device)
         g = self._grid(dims, lo, hi)
         b = _lib.BatchDesc(None, None, None, None, int(offset), count, 0, 0, 0)
-        ws, ws_bytes = self._forward_scratch(count)
-        _lib.check(_lib.lib().brief_siren_forward_ws(C.byref(self.desc), _lib.ptr(self.packed), C.byref(g), C.byref(b), _lib.ptr(out),
-                                                     kind, float(scale[0]), float(scale[1]), float(vrange[0]), float(vrange[1]),
-                                                     ws, ws_bytes, _lib.stream_ptr()))
+        _lib.check(self._abi_forward(g, b, out, kind, scale, vrange, count))
         return out
 
     # voxels per brief_siren_forward_box call of decode_box: bounds one launch's length and the scratch request of a wide net
@@ -375,13 +370,9 @@ class SIREN:
         if chunk < 1:
             raise ValueError("chunk must be >= 1")
         flat = out.view(total, self.data_channel)
-        L = _lib.lib()
         for off in range(0, total, chunk):
             cnt = min(chunk, total - off)
-            ws, ws_bytes = self._forward_scratch(cnt)
-            _lib.check(L.brief_siren_forward_box(C.byref(self.desc), _lib.ptr(self.packed), C.byref(box), off, cnt, _lib.ptr(flat[off:off + cnt]),
-                                                 kind, float(scale[0]), float(scale[1]), float(vrange[0]), float(vrange[1]),
-                                                 ws, ws_bytes, _lib.stream_ptr()))
+            _lib.check(self._abi_forward_box(box, off, cnt, flat[off:off + cnt], kind, scale, vrange))
         return out
 
     def train_step(self, n, targets, idx=None, coords=None, weights=None, grid=None, offset=0,
@@ -394,7 +385,7 @@ class SIREN:
         if self.grads is None:
             self.grads = torch.zeros_like(self.params)
             self._loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        need = _lib.lib().brief_train_workspace_bytes(C.byref(self.desc), int(n))
+        need = self._abi_train_ws_bytes(n)
         if need < 0:
             raise _lib.BriefError(_lib.lib().brief_last_error().decode())
         if self._ws is None or self._ws.numel() * 4 < need:
@@ -407,10 +398,7 @@ class SIREN:
         b = _lib.BatchDesc(_dev_ptr(coords, torch.float32, "coords", dev), _dev_ptr(targets, torch.float32, "targets", dev),
                            _dev_ptr(weights, torch.float32, "weights", dev), _dev_ptr(idx, torch.int64, "idx", dev),
                            int(offset), int(n), 0, 0, 0)
-        _lib.check(_lib.lib().brief_siren_train_step(
-            C.byref(self.desc), _lib.ptr(self.packed), C.byref(g) if g is not None else None, C.byref(b),
-            _lib.LOSS_KIND[loss], float(thr), float(beta), _lib.ptr(self.grads), _lib.ptr(self._loss), _lib.ptr(yhat),
-            _lib.ptr(self._ws), self._ws.numel() * 4, _lib.stream_ptr()))
+        _lib.check(self._abi_train_step(g, b, _lib.LOSS_KIND[loss], thr, beta, yhat))
         return self._loss, yhat
 
     def fit_step(self, n, targets, opt_kind, s1, s2, lr, t, idx=None, weights=None, grid=None, offset=0,
@@ -440,11 +428,39 @@ class SIREN:
         if self.grads is None:
             self.grads = torch.zeros_like(self.params)
             self._loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        need = _lib.lib().brief_train_workspace_bytes(C.byref(self.desc), int(n))
+        need = self._abi_train_ws_bytes(n)
         if need < 0:
             raise _lib.BriefError(_lib.lib().brief_last_error().decode())
         if self._ws is None or self._ws.numel() * 4 < need:
             self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
+
+    # ---- the C-ABI entries of this net kind (FFN overrides them)
+    def _abi_packed_count(self):
+        return _lib.lib().brief_packed_count(C.byref(self.desc))
+
+    def _abi_repack(self):
+        return _lib.lib().brief_siren_repack(C.byref(self.desc), _lib.ptr(self.params), _lib.ptr(self.packed), _lib.stream_ptr())
+
+    def _abi_forward(self, grid, batch, out, kind, scale, vrange, n):
+        ws, ws_bytes = self._forward_scratch(n)
+        return _lib.lib().brief_siren_forward_ws(C.byref(self.desc), _lib.ptr(self.packed), C.byref(grid) if grid is not None else None,
+                                                 C.byref(batch), _lib.ptr(out), kind, float(scale[0]), float(scale[1]),
+                                                 float(vrange[0]), float(vrange[1]), ws, ws_bytes, _lib.stream_ptr())
+
+    def _abi_forward_box(self, box, off, cnt, out, kind, scale, vrange):
+        ws, ws_bytes = self._forward_scratch(cnt)
+        return _lib.lib().brief_siren_forward_box(C.byref(self.desc), _lib.ptr(self.packed), C.byref(box), off, cnt, _lib.ptr(out),
+                                                  kind, float(scale[0]), float(scale[1]), float(vrange[0]), float(vrange[1]),
+                                                  ws, ws_bytes, _lib.stream_ptr())
+
+    def _abi_train_ws_bytes(self, n):
+        return _lib.lib().brief_train_workspace_bytes(C.byref(self.desc), int(n))
+
+    def _abi_train_step(self, g, b, loss_kind, thr, beta, yhat):
+        return _lib.lib().brief_siren_train_step(
+            C.byref(self.desc), _lib.ptr(self.packed), C.byref(g) if g is not None else None, C.byref(b),
+            loss_kind, float(thr), float(beta), _lib.ptr(self.grads), _lib.ptr(self._loss), _lib.ptr(yhat),
+            _lib.ptr(self._ws), self._ws.numel() * 4, _lib.stream_ptr())
 
     # ---- budget -> width (utils/Networks.py:291-314)
     @staticmethod
@@ -470,6 +486,188 @@ class SIREN:
             raise NotImplementedError("SIREN(res=True) is unsupported on the fused path")
 
 
+class FFN(SIREN):
+    """reference: utils/Networks.py:138-207 (FourierFeatureEmbedding + FFN), skip=False.  Parameters live in one canonical buffer
+    [bvals | W0 b0 | hidden | head] (include/brief_hip.h, brief_ffn_desc); bvals is fixed: its gradient is zero and the optimizer
+    (brief_ffn_fit) updates the MLP span only."""
+
+    kind = "FFN"
+
+    def __init__(self, coords_channel=3, data_channel=1, embsize=256, scale=10, features=256, layers=5, skip=False,
+                 device=None, precision="fp32", **kwargs):
+        """w0 / output_act / res of a SIREN YAML are ignored, as FFN(**phi) ignores them.  precision: the fused path is fp32 only;
+        'bf16' / 'bf16x3' run in fp32 with a warning."""
+        if skip:
+            raise NotImplementedError("FFN(skip=True) is unsupported on the fused path")
+        if str(precision) not in ("fp32", "f32"):
+            # (an artefact's phi_precision, or NFGR's Compress.half / precision, names a low-precision mode: there are no such FFN kernels)
+            logging.warning("FFN: no %s kernels; the net runs in fp32" % precision)
+        self.coords_channel, self.data_channel = int(coords_channel), int(data_channel)
+        self.features, self.layers = int(features), int(layers)
+        self.embsize, self.scale = int(embsize), float(scale)
+        if self.layers < 2:
+            raise NotImplementedError("FFN: layers must be >= 2")
+        if not 1 <= self.features <= 1024:
+            raise NotImplementedError("FFN: features must be 1..1024 on the fused path (got %d)" % self.features)
+        if not 1 <= self.embsize <= 512:
+            raise NotImplementedError("FFN: embsize must be 1..512 on the fused path (got %d)" % self.embsize)
+        if self.coords_channel not in (2, 3) or not 1 <= self.data_channel <= 4:
+            raise NotImplementedError("FFN: coords_channel must be 2 or 3 and data_channel 1..4")
+        self.precision = "fp32"
+        self.w0, self.output_act = 0.0, False
+        self.desc = _lib.FfnDesc(self.coords_channel, self.data_channel, self.layers, self.features, self.embsize, 0)
+        F, E = self.features, self.embsize
+        self._shapes = [(F, 2 * E)] + [(F, F)] * (self.layers - 2) + [(self.data_channel, F)]
+        self.bv_count = E * self.coords_channel
+        self.param_count = self.bv_count + sum(o * i + o for o, i in self._shapes)
+        self.params = self._reference_init()
+        self.grads = None
+        self.packed = None
+        self._stale = True
+        self._seen_version = -1
+        self._autograd = False
+        self._anchor = None
+        self._ws = None
+        self._fws = None
+        self._loss = None
+        self.fourierfeature_embedding = _Embedding(_ParamView(self, 0, (E, self.coords_channel)))
+        net, off = [], self.bv_count
+        for (o, i) in self._shapes:
+            net.append(_Seq(_Linear(self, off, (o, i), off + o * i)))
+            off += o * i + o
+        self.net = net
+        if device is not None:
+            self.to(device)
+
+    def _reference_init(self):
+        """FourierFeatureEmbedding.__init__ reseeds the global generator with 0 and draws bvals = normal(0, 1) * scale; the
+        nn.Linear default inits (kaiming_uniform(a=sqrt 5) weight, then bias) follow in layer order.  Replayed with torch on the
+        CPU: the values AND the generator state afterwards equal the reference's, whatever the caller's seed was."""
+        torch.manual_seed(0)
+        bv = torch.normal(0, 1, size=(self.embsize, self.coords_channel)) * self.scale
+        parts = [bv.reshape(-1)]
+        for (o, i) in self._shapes:
+            w = torch.empty(o, i)
+            gain = math.sqrt(2.0 / (1 + math.sqrt(5) ** 2))
+            w.uniform_(-math.sqrt(3.0) * gain / math.sqrt(i), math.sqrt(3.0) * gain / math.sqrt(i))
+            b = torch.empty(o)
+            b.uniform_(-1 / math.sqrt(i), 1 / math.sqrt(i))
+            parts += [w.reshape(-1), b]
+        return torch.cat(parts).contiguous()
+
+    def state_dict(self):
+        sd = OrderedDict()
+        sd["fourierfeature_embedding.bvals"] = self.fourierfeature_embedding.bvals.data
+        sd.update(SIREN.state_dict(self))
+        return sd
+
+    def load_state_dict(self, sd):
+        if "fourierfeature_embedding.bvals" in sd:
+            self.fourierfeature_embedding.bvals.data = sd["fourierfeature_embedding.bvals"]
+        SIREN.load_state_dict(self, sd)
+
+    def _set_precision(self, precision):
+        return self
+
+    def float(self):
+        return self
+
+    def half(self):
+        """no low-precision FFN kernels: the net stays in fp32 (NFGR keeps the reference's 2-bytes-per-parameter budget and records
+        phi_precision: fp32)"""
+        if not getattr(FFN, "_warned_half", False):
+            FFN._warned_half = True
+            logging.warning("FFN.half(): there are no low-precision FFN kernels; the net stays in fp32")
+        return self
+
+    def _forward_scratch(self, n):
+        return None, 0
+
+    # ---- C-ABI entries
+    def _abi_packed_count(self):
+        return _lib.lib().brief_ffn_packed_count(C.byref(self.desc))
+
+    def _abi_repack(self):
+        return _lib.lib().brief_ffn_repack(C.byref(self.desc), _lib.ptr(self.params), _lib.ptr(self.packed), _lib.stream_ptr())
+
+    def _abi_forward(self, grid, batch, out, kind, scale, vrange, n):
+        return _lib.lib().brief_ffn_forward(C.byref(self.desc), _lib.ptr(self.packed), C.byref(grid) if grid is not None else None,
+                                            C.byref(batch), _lib.ptr(out), kind, float(scale[0]), float(scale[1]),
+                                            float(vrange[0]), float(vrange[1]), _lib.stream_ptr())
+
+    def _abi_forward_box(self, box, off, cnt, out, kind, scale, vrange):
+        return _lib.lib().brief_ffn_forward_box(C.byref(self.desc), _lib.ptr(self.packed), C.byref(box), off, cnt, _lib.ptr(out),
+                                                kind, float(scale[0]), float(scale[1]), float(vrange[0]), float(vrange[1]),
+                                                _lib.stream_ptr())
+
+    def _abi_train_ws_bytes(self, n):
+        return _lib.lib().brief_ffn_train_workspace_bytes(C.byref(self.desc), int(n))
+
+    def _abi_train_step(self, g, b, loss_kind, thr, beta, yhat):
+        return _lib.lib().brief_ffn_train_step(
+            C.byref(self.desc), _lib.ptr(self.packed), C.byref(g) if g is not None else None, C.byref(b),
+            loss_kind, float(thr), float(beta), _lib.ptr(self.grads), _lib.ptr(self._loss), _lib.ptr(yhat),
+            _lib.ptr(self._ws), self._ws.numel() * 4, _lib.stream_ptr())
+
+    def fit_step(self, n, targets, opt_kind, s1, s2, lr, t, idx=None, weights=None, grid=None, offset=0,
+                 loss="datal2", thr=0.0, beta=0.01, betas=(0.9, 0.999), eps=1e-8, rng=None):
+        """train_step + optimizer update of the MLP span + refresh of the packed copy: one step of brief_ffn_fit"""
+        self._require_gpu()
+        self.sync_packed()
+        self.ensure_train_buffers(n)
+        dims, lo, hi = grid
+        g = self._grid(dims, lo, hi)
+        pop, seed, step = rng if (rng is not None and idx is None) else (0, 0, 0)
+        dev = self.params.device
+        b = _lib.BatchDesc(None, _dev_ptr(targets, torch.float32, "targets", dev), _dev_ptr(weights, torch.float32, "weights", dev),
+                           _dev_ptr(idx, torch.int64, "idx", dev), int(offset), int(n), int(pop), int(seed), 0)
+        j = _lib.FfnFitJob()
+        j.desc, j.grid, j.batch = self.desc, g, b
+        j.params, j.packed, j.state1, j.state2 = self.params.data_ptr(), self.packed.data_ptr(), _lib.ptr(s1), _lib.ptr(s2)
+        j.grads, j.loss_out, j.loss_log = self.grads.data_ptr(), self._loss.data_ptr(), None
+        j.workspace, j.workspace_bytes = self._ws.data_ptr(), self._ws.numel() * 4
+        j.loss_kind, j.optim_kind, j.thr, j.beta = _lib.LOSS_KIND[loss], int(opt_kind), float(thr), float(beta)
+        j.lr, j.beta1, j.beta2, j.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
+        j.n_milestones, j.gamma, j.t0 = 0, 1.0, int(t) - 1
+        j.idx_stride = int(n) if idx is not None else 0      # (in-kernel draws of step t are keyed by rng_step = t0 + 1 = t)
+        _lib.check(_lib.lib().brief_ffn_fit(C.byref(j), 1, _lib.stream_ptr()))
+        return self._loss
+
+    # ---- budget -> width (utils/Networks.py:188-207)
+    @staticmethod
+    def calc_param_count(coords_channel, data_channel, features, embsize=256, layers=5, skip=False, **kwargs):
+        """the reference's formula: first layer 2E x F + F, (layers-2) hidden F x F + F, head F x cout + cout, plus bvals E x cin"""
+        FFN._no_skip(skip)
+        d = 2 * embsize
+        return int(d * features + features + (layers - 2) * (features ** 2 + features) + features * data_channel + data_channel
+                   + coords_channel * embsize)
+
+    @staticmethod
+    def calc_features(param_count, coords_channel, data_channel, embsize=256, layers=5, skip=False, **kwargs):
+        """the positive root of (layers-2) F^2 + (2E + 1 + layers-2 + cout) F + cout + cin E = P, rounded (the reference's formula)"""
+        FFN._no_skip(skip)
+        d = 2 * embsize
+        a = layers - 2
+        b = d + 1 + layers - 2 + data_channel
+        c = -param_count + data_channel + coords_channel * embsize
+        if a == 0:
+            return round(-c / b)
+        return round((-b + math.sqrt(b ** 2 - 4 * a * c)) / (2 * a))
+
+    @staticmethod
+    def _no_skip(skip):
+        if skip:
+            raise NotImplementedError("FFN(skip=True) is unsupported on the fused path")
+
+
+class _Embedding:
+    """stands for FourierFeatureEmbedding: `.bvals` is a window into the canonical buffer (requires_grad False)"""
+
+    def __init__(self, bvals):
+        self.bvals = bvals
+        self.requires_grad = False
+
+
 def _dev_ptr(t, dtype, what, device):
     """data_ptr() of a tensor the C-ABI will read as `dtype`: wrong dtype / layout / device is an error here, not
     silently reinterpreted bits in the kernel"""
@@ -489,11 +687,11 @@ def get_nnmodule_param_count(module):
     return sum(int(np.prod(p.shape)) for p in module.state_dict().values())
 
 
-# registry with the reference's names (utils/Networks.py:795-802).  Only SIREN exists on the fused
+# registry with the reference's names (utils/Networks.py:795-802).  SIREN and FFN exist on the fused
 # path; every other phi.name of the reference raises instead of silently running something else.
-ALLPHI = {"SIREN": SIREN}
-ALL_CALC_PHI_FEATURES = {"SIREN": SIREN.calc_features}
-ALL_CALC_PHI_PARAM_COUNT = {"SIREN": SIREN.calc_param_count}
+ALLPHI = {"SIREN": SIREN, "FFN": FFN}
+ALL_CALC_PHI_FEATURES = {"SIREN": SIREN.calc_features, "FFN": FFN.calc_features}
+ALL_CALC_PHI_PARAM_COUNT = {"SIREN": SIREN.calc_param_count, "FFN": FFN.calc_param_count}
 ALL_CHECK_PARAM_COUNT = {}
 
 
@@ -501,5 +699,5 @@ def init_phi(kwargs):
     kwargs = copy.deepcopy(dict(kwargs))
     name = kwargs.pop("name")
     if name not in ALLPHI:
-        raise NotImplementedError("Module.phi.name=%r is not available on the fused MI355X path (only SIREN)" % name)
+        raise NotImplementedError("Module.phi.name=%r is not available on the fused MI355X path (only SIREN and FFN)" % name)
     return ALLPHI[name](**kwargs)

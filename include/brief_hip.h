@@ -241,6 +241,66 @@ int brief_sincos_probe(const float *x, float *s, float *c, int64_t n, void *stre
 /* compute units of the current device as the library sized its grids and workspaces from (256 on a whole MI355X) */
 int brief_cu_count(void);
 
+/* ---- FFN: Fourier-feature network (Tancik et al.)  utils/Networks.py:138-207 --------------------------------------------
+ *   emb = [sin(2 pi x B^T), cos(2 pi x B^T)]  (B = bvals [embsize, cin], fixed: no gradient, no optimizer state)
+ *   Linear(2 embsize, F) + ReLU, (layers - 2) x (Linear(F, F) + ReLU), Linear(F, cout)  (no output activation; skip=False only)
+ * Limits (anything else: BRIEF_ERR_INVALID with a message naming the limit): fp32 only, cin 2 | 3, cout 1 .. 4, layers >= 2,
+ * features 1 .. 1024 and embsize 1 .. 512 (both padded internally to whole 32-wide tiles), reserved == 0.
+ * Canonical parameter buffer (== torch parameters() / state_dict() order):
+ *   bvals [embsize][cin] | W0 [F][2 embsize] b0 [F] | (W_l [F][F] b_l [F]) x (layers - 2) | Wh [cout][F] bh [cout]
+ * The gradient of the bvals span is written as zero; the optimizer (brief_ffn_fit) updates the MLP span only, and the optimizer
+ * state buffers have the canonical buffer's size (their bvals span is not touched). */
+typedef struct {
+    int32_t cin;         /* 2 | 3 */
+    int32_t cout;        /* 1 .. 4 */
+    int32_t layers;      /* >= 2 */
+    int32_t features;    /* 1 .. 1024 */
+    int32_t embsize;     /* 1 .. 512 */
+    int32_t reserved;    /* 0 */
+} brief_ffn_desc;
+
+/* floats of the canonical buffer (== FFN.calc_param_count, bvals included) / of the fragment-ordered copy / train-step scratch bytes */
+int64_t brief_ffn_param_count(const brief_ffn_desc *d);
+int64_t brief_ffn_packed_count(const brief_ffn_desc *d);
+int64_t brief_ffn_train_workspace_bytes(const brief_ffn_desc *d, int64_t n);
+/* canonical params -> fragment-ordered copy (call after every change of params made outside brief_ffn_fit) */
+int brief_ffn_repack(const brief_ffn_desc *d, const float *params, float *packed, void *stream);
+/* FFN.forward under no_grad, with the out_kind epilogue of brief_siren_forward (no scratch) */
+int brief_ffn_forward(const brief_ffn_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                      void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream);
+/* the box decode of brief_siren_forward_box (same box rules and refusals) */
+int brief_ffn_forward_box(const brief_ffn_desc *d, const float *packed, const brief_grid_box *box, int64_t offset, int64_t n,
+                          void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream);
+/* forward + loss + backward of one batch, as brief_siren_train_step (grads: canonical layout, bvals span zero) */
+int brief_ffn_train_step(const brief_ffn_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                         int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
+                         void *workspace, int64_t workspace_bytes, void *stream);
+/* brief_fit_job with an FFN desc: every field after `desc` means exactly what it means in brief_fit_job
+ * (workspace: brief_ffn_train_workspace_bytes(desc, batch.n)) */
+typedef struct brief_ffn_fit_job {
+    brief_ffn_desc desc;
+    brief_grid_desc grid;
+    brief_batch_desc batch;
+    float *params, *packed;
+    float *state1, *state2;
+    float *grads;
+    float *loss_out;
+    float *loss_log;
+    void *workspace;
+    int64_t workspace_bytes;
+    int32_t loss_kind, optim_kind;
+    float thr, beta;
+    double lr, beta1, beta2, eps;
+    const int64_t *milestones;
+    int32_t n_milestones, reserved;
+    double gamma;
+    int64_t t0;
+    const double *lr_table, *beta1_table;
+    int64_t idx_stride;
+} brief_ffn_fit_job;
+/* `steps` optimizer steps (train step + reduction + update + repack: four launches each, no host synchronisation) */
+int brief_ffn_fit(const brief_ffn_fit_job *job, int64_t steps, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
