@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — encode throughput of BRIEF's SIREN fit loop on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json metric: "voxels/sec encode (512^3 vol, 4x256 SIREN)"):
@@ -18,9 +18,14 @@ the volume resident in HBM when the timed region starts.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a child `python -m
 torch.distributed.run`, decided before anything touches the GPU) and exits with the child's code; under torchrun the
-world size must equal --gpus.  The N = 1 line also carries, all timed in this run: `configs` (BASELINE config 1 on
-k_small, config 3 on the bf16 kernels), a three-point `psnr_at_bitrate_sweep` on the 512^3 volume, and `encode` /
-`decode` as wall clocks around a real NFGR.compress / NFGR.decompress of the host-resident volume.
+world size must equal --gpus.
+
+A plain run does only what the headline needs: set up, pre-roll and warm up, time the K steps, write --dump-outputs, print
+the line.  Everything else is measured under --full only: the PSNR / SSIM of the fitted net (`psnr_at_bitrate`, the
+DivideTask path's evaluation), `decode_kernel` and `steady_state_fit`, and on the N = 1 path, all timed in that run:
+`configs` (BASELINE config 1 on k_small, config 3 on the bf16 kernels, ...), a `psnr_at_bitrate_sweep` on the 512^3
+volume, `encode` / `decode` as wall clocks around a real NFGR.compress / NFGR.decompress of the host-resident volume
+(SURVEY 8d), and the `cpu_baseline`.  --no-psnr / --no-extras / --no-cpu-baseline leave parts of --full out.
 """
 import argparse
 import ctypes as C
@@ -486,17 +491,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--preroll", type=int, default=200, help="untimed steps before the counted warm-up (clock ramp)")
     ap.add_argument("--preroll-seconds", type=float, default=0.5, help="... and at least this long")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: PSNR / SSIM, decode, the other configurations, "
+                                                        "the PSNR sweep, the NFGR wall clocks and the CPU baseline (a plain run skips them)")
     ap.add_argument("--encode-steps", type=int, default=2000, help="total optimizer steps of the end-to-end encode figure / psnr_at_bitrate (0: skip)")
     ap.add_argument("--long-steps", type=int, default=20000, help="the reference's own schedule length (default.yaml max_steps): PSNR / SSIM point after this many steps (0: skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-psnr", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-psnr", action="store_true", help="with --full: skip the PSNR / SSIM evaluation and everything after it")
     ap.add_argument("--precision", choices=["fp32", "bf16", "bf16x3"], default="fp32",
                     help="fp32 = the metric (exact f32 MFMA); bf16 = BASELINE config 3's arithmetic; bf16x3 = split-precision bf16 MFMAs that "
                          "meet the fp32 parity bands (extra lines, never the default)")
     ap.add_argument("--config", choices=["c2", "c3"], default="c2", help="c2: 4x256 SIREN (the metric); c3: 8x512 SIREN")
     ap.add_argument("--divide", action="store_true", help="run the DivideTask product path also at world size 1 (one block, process group initialised)")
     ap.add_argument("--block", type=int, default=512, help="edge of the cubic block (tests only; the metric is quoted on 512)")
-    ap.add_argument("--no-extras", action="store_true", help="skip configs / psnr_at_bitrate_sweep / the NFGR wall clocks (headline line only)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip configs / psnr_at_bitrate_sweep / the NFGR wall clocks")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (loss, parameters, "
                                                          "gradients) as DIR/<name>.npy in float32; single-rank path only")
     args = ap.parse_args()
@@ -506,6 +513,8 @@ def main():
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.dump_outputs and (args.gpus > 1 or args.divide):
         ap.error("--dump-outputs: only the single-rank path (--gpus 1 without --divide) dumps its outputs")
+    if not args.full:                                   # a plain run: the headline alone
+        args.no_psnr = args.no_extras = args.no_cpu_baseline = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args)                              # does not return
 

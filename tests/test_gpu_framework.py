@@ -596,7 +596,7 @@ def test_bench_dividetask_path_on_the_rccl_backend_world_size_one():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--divide", "--block", "128", "--steps", "4", "--warmup", "2", "--preroll", "4",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -619,7 +619,7 @@ def test_bench_dividetask_path_on_the_rccl_backend_world_size_one():
     # the self-launch itself, rehearsed with two gloo ranks sharing this GPU: bench.py starts `torch.distributed.run` as a child,
     # the two ranks run the DivideTask path on a 2 x 128^3 volume and rank 0 prints the one line
     r4 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--block", "128", "--steps", "4", "--warmup", "2", "--preroll", "4",
-                         "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env={**env, "BRIEF_DIST_BACKEND": "gloo", "BRIEF_SHARE_GPU": "1"})
+                         "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env={**env, "BRIEF_DIST_BACKEND": "gloo", "BRIEF_SHARE_GPU": "1"})
     assert r4.returncode == 0, r4.stderr[-3000:]
     out2 = json.loads([l for l in r4.stdout.splitlines() if l.startswith("{")][-1])
     assert out2["n_gpus"] == 2 and out2["config"]["volume"] == [256, 128, 128] and out2["value"] > 1e6 and 10.0 < out2["psnr_at_bitrate"]["psnr_db"] < 100.0
@@ -638,7 +638,7 @@ def test_bench_four_ranks_share_the_gpu_like_a_scale_run():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--block", "64", "--steps", "3", "--warmup", "1", "--preroll", "2",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env={**env, "BRIEF_DIST_BACKEND": "gloo", "BRIEF_SHARE_GPU": "1"})
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env={**env, "BRIEF_DIST_BACKEND": "gloo", "BRIEF_SHARE_GPU": "1"})
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 4 and out["config"]["volume"] == [256, 64, 64] and out["scaling"] == "weak" and out["value"] > 1e5
@@ -668,6 +668,31 @@ def test_bench_dump_outputs_do_not_depend_on_the_preroll(tmp_path):
     for n in a:
         assert a[n].dtype == np.float32 and np.array_equal(a[n], b[n]), n
     assert float(a["loss"][0]) == out["loss"] and np.all(np.isfinite(a["grads"])) and np.any(a["grads"] != 0)
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """a plain bench.py run sets up, warms up, times the steps and prints the headline; the PSNR / SSIM evaluation, the decode and
+    steady-state figures, the other configurations and the CPU baseline come only with --full (--no-extras / --no-cpu-baseline
+    leave parts of it out)"""
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--block", "64", "--steps", "3", "--warmup", "1",
+            "--preroll", "2", "--preroll-seconds", "0"]
+    outs = []
+    for extra in ([], ["--full", "--no-extras", "--no-cpu-baseline"]):
+        r = subprocess.run(base + extra, capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        outs.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    plain, full = outs
+    for out in outs:
+        assert out["metric"] == "encode_voxels_per_sec" and out["unit"] == "voxels/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and "configs" not in out and "cpu_baseline" not in out
+    assert plain["psnr_at_bitrate"]["psnr_db"] is None
+    assert not any(k in plain for k in ("decode_kernel", "steady_state_fit", "psnr_at_bitrate_sweep", "encode", "decode"))
+    assert 10.0 < full["psnr_at_bitrate"]["psnr_db"] < 100.0 and 0.0 < full["psnr_at_bitrate"]["ssim"] <= 1.0
+    assert full["psnr_at_bitrate"]["steps"] == 2000 and "decode_kernel" in full and "steady_state_fit" in full
 
 
 def test_adaptive_octree_device_statistics_choose_the_pinned_partition():
