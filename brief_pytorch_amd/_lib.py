@@ -61,6 +61,15 @@ class FfnFitJob(C.Structure):       # brief_ffn_fit_job: brief_fit_job's fields 
     _fields_ = [("desc", FfnDesc)] + FitJob._fields_[1:]
 
 
+class NerfDesc(C.Structure):        # brief_nerf_desc
+    _fields_ = [("cin", C.c_int32), ("cout", C.c_int32), ("layers", C.c_int32), ("features", C.c_int32),
+                ("frequencies", C.c_int32), ("skip", C.c_int32)]
+
+
+class NerfFitJob(C.Structure):      # brief_nerf_fit_job: brief_fit_job's fields after the desc
+    _fields_ = [("desc", NerfDesc)] + FitJob._fields_[1:]
+
+
 LOSS_KIND = {"datal2": 0, "datasmoothl1": 1, "external": 2}
 OPT_KIND = {"Adamax": 0, "Adam": 1, "SGD": 2}
 OUT_F32, OUT_U8, OUT_U16 = 0, 1, 2
@@ -72,7 +81,9 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_optim_step", "brief_sample_indices", "brief_sse_u16", "brief_profile_enable", "brief_profile_fused", "brief_deblock_edge", "brief_ssim_u16", "brief_ssim_partial_count",
            "brief_sincos_probe", "brief_cu_count",
            "brief_ffn_param_count", "brief_ffn_packed_count", "brief_ffn_train_workspace_bytes", "brief_ffn_repack", "brief_ffn_forward",
-           "brief_ffn_forward_box", "brief_ffn_train_step", "brief_ffn_fit"]
+           "brief_ffn_forward_box", "brief_ffn_train_step", "brief_ffn_fit",
+           "brief_nerf_param_count", "brief_nerf_packed_count", "brief_nerf_train_workspace_bytes", "brief_nerf_repack", "brief_nerf_forward",
+           "brief_nerf_forward_box", "brief_nerf_train_step", "brief_nerf_fit"]
 
 
 def needs_build():
@@ -166,6 +177,17 @@ def lib():
     L.brief_ffn_forward_box.argtypes = [fp, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
     L.brief_ffn_train_step.argtypes = [fp, vp, gp, bp, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, C.c_int64, vp]
     L.brief_ffn_fit.argtypes = [C.POINTER(FfnFitJob), C.c_int64, vp]
+    np_ = C.POINTER(NerfDesc)
+    for name in ("brief_nerf_param_count", "brief_nerf_packed_count"):
+        getattr(L, name).restype = C.c_int64
+        getattr(L, name).argtypes = [np_]
+    L.brief_nerf_train_workspace_bytes.restype = C.c_int64
+    L.brief_nerf_train_workspace_bytes.argtypes = [np_, C.c_int64]
+    L.brief_nerf_repack.argtypes = [np_, vp, vp, vp]
+    L.brief_nerf_forward.argtypes = [np_, vp, gp, bp, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
+    L.brief_nerf_forward_box.argtypes = [np_, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
+    L.brief_nerf_train_step.argtypes = [np_, vp, gp, bp, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, C.c_int64, vp]
+    L.brief_nerf_fit.argtypes = [C.POINTER(NerfFitJob), C.c_int64, vp]
     _LIB = L
     return L
 

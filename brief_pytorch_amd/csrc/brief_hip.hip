@@ -54,6 +54,7 @@
 #include "brief_bf16.inc"       // bf16: k16, k_wgrad16, k_reduce16
 #include "brief_aux.inc"        // k_repack, index stream, metrics, deblocking filter
 #include "brief_ffn.inc"        // FFN: k_ffn_fwd, k_ffn_wgrad, k_ffn_reduce, k_ffn_repack
+#include "brief_nerf.inc"       // NeRF: k_nerf_fwd, k_nerf_wgrad, k_nerf_repack
 
 // =============================================================================================
 // C-ABI
@@ -1815,6 +1816,311 @@ int brief_ffn_fit(const brief_ffn_fit_job *j, int64_t steps, void *stream)
         up.params = j->params; up.s1 = j->state1; up.s2 = j->state2; up.pk = j->packed;
         if (int rc = ffn_train_impl(&j->desc, j->packed, &j->grid, &b, j->loss_kind, j->thr, j->beta, j->grads,
                                     j->loss_log ? j->loss_log + k : j->loss_out, nullptr, j->workspace, j->workspace_bytes, (void *)st, &up))
+            return rc;
+    }
+    if (j->loss_log && steps > 0)
+        HIP_TRY(hipMemcpyAsync(j->loss_out, j->loss_log + steps - 1, sizeof(float), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+}   // extern "C"
+
+// =============================================================================================
+// NeRF (positional-encoding network, brief_nerf.inc): train step = k_nerf_fwd<TRAIN> + k_nerf_wgrad + k_ffn_reduce (bv = 0)
+// (+ k_nerf_repack after an update)
+static int check_nerf_desc(const brief_nerf_desc *d)
+{
+    if (!d) return fail(BRIEF_ERR_INVALID, "null desc");
+    if (d->cin != 2 && d->cin != 3) return fail(BRIEF_ERR_INVALID, "NeRF: coords_channel must be 2 or 3");
+    if (d->cout < 1 || d->cout > 4) return fail(BRIEF_ERR_INVALID, "NeRF: data_channel must be 1..4");
+    if (d->skip != 0 && d->skip != 1) return fail(BRIEF_ERR_INVALID, "NeRF: skip must be 0 or 1");
+    if (d->layers < 2) return fail(BRIEF_ERR_INVALID, "NeRF: layers must be >= 2");
+    if (d->skip && d->layers < 3) return fail(BRIEF_ERR_INVALID, "NeRF: layers must be >= 3 with skip");
+    if (d->features < 1 || d->features > 1024) return fail(BRIEF_ERR_INVALID, "NeRF: features must be 1..1024 on the fused path");
+    if (d->frequencies < 0 || d->frequencies > 16) return fail(BRIEF_ERR_INVALID, "NeRF: frequencies must be 0..16 on the fused path");
+    return 0;
+}
+
+static int nerf_lds_bytes(const brief_nerf_desc &d)
+{
+    const NerfLayout l = nerf_layout(d);
+    return (int)sizeof(float) * (32 * (l.DP + l.FP) + 128);
+}
+// persistent grid: up to two workgroups per CU (one wave per SIMD each), fewer when the LDS image does not fit twice
+static int nerf_grid(const brief_nerf_desc &d, int64_t n)
+{
+    const int64_t tiles = (n + 31) / 32;
+    const int by_lds = (160 * 1024) / nerf_lds_bytes(d);
+    const int64_t cap = (int64_t)kCUs * (by_lds < 2 ? (by_lds > 0 ? by_lds : 1) : 2);
+    return (int)(tiles < cap ? tiles : cap);
+}
+struct NerfWs { int64_t npad, H, D, ENC, G, lpart, slabs, total, chunk; int nsplit, waves; };
+// weight-gradient block i (0 .. nerf_wgrad_count - 1) of the net, in canonical order: W0 | per hidden layer (the skip layer's encoding
+// columns first) | head; planes at the workspace offsets of w (ws == nullptr: shapes only), wave_begin left to the caller
+static int nerf_wgrad_count(const brief_nerf_desc &d) { return d.layers + (d.skip ? 1 : 0); }
+static NerfWgradBlock nerf_wgrad_block(const brief_nerf_desc &d, const NerfWs &w, float *ws, int i)
+{
+    const NerfLayout lay = nerf_layout(d);
+    const int F = d.features, L = d.layers;
+    const int64_t plane = (int64_t)lay.FP * w.npad;
+    int64_t A, B, w_off, b_off;
+    int arows = F, brows = F, ldw = F;
+    if (i == 0) {
+        A = w.D; B = w.ENC; brows = lay.d; ldw = lay.d; w_off = 0; b_off = (int64_t)F * lay.d;
+    } else if (i == nerf_wgrad_count(d) - 1) {
+        A = w.G; B = w.H + (int64_t)(L - 2) * plane; arows = d.cout;
+        w_off = nerf_canon_head(d); b_off = w_off + (int64_t)d.cout * F;
+    } else {
+        const bool past = lay.sl && i > lay.sl;                        // block index i: layer i, or i - 1 past the skip layer's extra block
+        const int l = past ? i - 1 : i;
+        const bool enc = lay.sl && i == lay.sl;                        // the skip layer's encoding columns
+        const int coff = l == lay.sl ? lay.d : 0;
+        const int64_t c = nerf_canon_hidden(d, l);
+        A = w.D + (int64_t)l * plane; ldw = F + coff;
+        if (enc) { B = w.ENC; brows = lay.d; w_off = c; b_off = -1; }
+        else { B = w.H + (int64_t)(l - 1) * plane; w_off = c + coff; b_off = c + (int64_t)F * ldw; }
+    }
+    NerfWgradBlock b;
+    memset(&b, 0, sizeof(b));
+    b.A = ws ? ws + A : nullptr; b.B = ws ? ws + B : nullptr;
+    b.arows = arows; b.brows = brows;
+    b.mb = (arows + 63) / 64; b.nb = (brows + 63) / 64;
+    b.w_off = w_off; b.b_off = b_off; b.ldw = ldw;
+    return b;
+}
+static NerfWs nerf_ws_layout(const brief_nerf_desc &d, int64_t n)
+{
+    const NerfLayout lay = nerf_layout(d);
+    NerfWs w;
+    w.npad = (n + 31) / 32 * 32;
+    const int64_t plane = (int64_t)lay.FP * w.npad;
+    w.H = 0;
+    w.D = w.H + (int64_t)(d.layers - 1) * plane;
+    w.ENC = w.D + (int64_t)(d.layers - 1) * plane;
+    w.G = w.ENC + (int64_t)lay.DP * w.npad;
+    w.lpart = w.G + 4 * w.npad;
+    w.slabs = w.lpart + kFfnLossParts;
+    w.waves = 0;
+    for (int i = 0; i < nerf_wgrad_count(d); ++i) {
+        const NerfWgradBlock b = nerf_wgrad_block(d, w, nullptr, i);
+        w.waves += b.mb * b.nb;
+    }
+    const int64_t wgs = (w.waves + 3) / 4;
+    int64_t ns = (8 * (int64_t)kCUs + wgs - 1) / wgs;      // K-splits: about eight workgroups per CU (as k_ffn_wgrad)
+    if (ns > 64) ns = 64;
+    if (ns > w.npad / 256) ns = w.npad / 256;
+    if (ns < 1) ns = 1;
+    w.chunk = (w.npad / ns + 31) / 32 * 32;
+    w.nsplit = (int)((w.npad + w.chunk - 1) / w.chunk);
+    w.total = w.slabs + (int64_t)w.nsplit * nerf_canon_count(d);
+    return w;
+}
+
+template <bool TRAIN, bool BOX>
+static int launch_nerf_fwd(const NerfArgs &na, int grid, hipStream_t st)
+{
+    const int mtw = (na.nt + 3) / 4;
+    const int lds = nerf_lds_bytes(na.d);
+    const void *fn = nullptr;
+    switch (mtw) {
+#define NERF_CASE(M) case M: fn = (const void *)k_nerf_fwd<M, TRAIN, BOX>; break;
+        NERF_CASE(1) NERF_CASE(2) NERF_CASE(3) NERF_CASE(4) NERF_CASE(5) NERF_CASE(6) NERF_CASE(7) NERF_CASE(8)
+#undef NERF_CASE
+        default: return fail(BRIEF_ERR_INVALID, "NeRF: features must be 1..1024 on the fused path");
+    }
+    if (int rc = dev_attr_once(fn, lds)) return rc;
+    switch (mtw) {
+#define NERF_CASE(M) case M: hipLaunchKernelGGL((k_nerf_fwd<M, TRAIN, BOX>), dim3(grid), dim3(256), lds, st, na); break;
+        NERF_CASE(1) NERF_CASE(2) NERF_CASE(3) NERF_CASE(4) NERF_CASE(5) NERF_CASE(6) NERF_CASE(7) NERF_CASE(8)
+#undef NERF_CASE
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static void nerf_forward_args(NerfArgs &na, const brief_nerf_desc *d, const float *packed, int64_t n, void *out, int out_kind,
+                              float scale_min, float scale_max, double vmin, double vmax)
+{
+    memset(&na, 0, sizeof(na));
+    const NerfLayout lay = nerf_layout(*d);
+    na.d = *d; na.nt = lay.nt; na.DP = lay.DP; na.pk = packed;
+    na.n = n; na.npad = (n + 31) / 32 * 32;
+    na.out = out; na.out_kind = out_kind;
+    na.scale_min = scale_min;
+    na.den = (float)((double)scale_max - (double)scale_min);
+    na.span = (float)(vmax - vmin);
+    na.vmin = (float)vmin;
+}
+
+static int nerf_train_impl(const brief_nerf_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                           int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
+                           void *workspace, int64_t workspace_bytes, void *stream, const FfnUpdate *upd)
+{
+    if (int rc = check_nerf_desc(d)) return rc;
+    brief_siren_desc sd;      // check_batch reads cin only
+    memset(&sd, 0, sizeof(sd));
+    sd.cin = d->cin;
+    if (int rc = check_batch(&sd, grid, batch, true)) return rc;
+    if (!packed || !grads || !loss_out || !workspace) return fail(BRIEF_ERR_INVALID, "null buffer");
+    if (loss_kind < BRIEF_LOSS_L2 || loss_kind > BRIEF_LOSS_EXTERNAL) return fail(BRIEF_ERR_INVALID, "bad loss_kind");
+    const NerfWs w = nerf_ws_layout(*d, batch->n);
+    if (workspace_bytes < w.total * (int64_t)sizeof(float)) return fail(BRIEF_ERR_WORKSPACE, "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    float *ws = (float *)workspace;
+    const NerfLayout lay = nerf_layout(*d);
+    NerfArgs na;
+    nerf_forward_args(na, d, packed, batch->n, nullptr, 0, 0.f, 1.f, 0.0, 1.0);
+    na.coords = batch->coords; na.targets = batch->targets; na.weights = batch->weights;
+    na.idx = batch->idx; na.offset = batch->offset;
+    if (!batch->idx && batch->rng_pop > 0) { na.rng_pop = (uint64_t)batch->rng_pop; na.rng_seed = batch->rng_seed; na.rng_step = batch->rng_step; }
+    fill_grid(na.grid, grid);
+    na.loss_kind = loss_kind; na.thr = thr; na.beta = beta;
+    na.inv_count = (float)(1.0 / ((double)batch->n * d->cout));
+    na.H = ws + w.H; na.D = ws + w.D; na.ENC = ws + w.ENC; na.G = ws + w.G; na.lpart = ws + w.lpart;
+    na.npad = w.npad; na.yhat_out = yhat_out;
+    const int grid1 = nerf_grid(*d, batch->n);
+    const bool prof = prof_live();
+    hipEvent_t *pev = prof ? dev_state()->prof_ev : nullptr;
+    if (prof) HIP_TRY(hipEventRecord(pev[2 * g_prof_n], st));
+    if (int rc = launch_nerf_fwd<true, false>(na, grid1, st)) return rc;
+    if (prof) { HIP_TRY(hipEventRecord(pev[2 * g_prof_n + 1], st)); ++g_prof_n; }
+    // weight gradients, at most NERF_WGRAD_BLOCKS blocks per launch
+    const int64_t mlp = nerf_canon_count(*d);
+    const int nblocks = nerf_wgrad_count(*d);
+    for (int b0 = 0; b0 < nblocks; b0 += NERF_WGRAD_BLOCKS) {
+        NerfWgradArgs wa;
+        memset(&wa, 0, sizeof(wa));
+        wa.npad = w.npad; wa.chunk = w.chunk; wa.mlp = mlp; wa.slabs = ws + w.slabs;
+        wa.nblocks = (nblocks - b0) < NERF_WGRAD_BLOCKS ? (nblocks - b0) : NERF_WGRAD_BLOCKS;
+        int waves = 0;
+        for (int i = 0; i < wa.nblocks; ++i) {
+            wa.blk[i] = nerf_wgrad_block(*d, w, ws, b0 + i);
+            wa.blk[i].wave_begin = waves;
+            waves += wa.blk[i].mb * wa.blk[i].nb;
+        }
+        wa.waves = waves;
+        hipLaunchKernelGGL(k_nerf_wgrad, dim3((unsigned)((waves + 3) / 4), (unsigned)w.nsplit), dim3(256), 0, st, wa);
+        HIP_TRY(hipGetLastError());
+    }
+    OptimScalars o;
+    memset(&o, 0, sizeof(o));
+    if (upd) o = upd->opt;
+    hipLaunchKernelGGL(k_ffn_reduce, dim3((unsigned)((mlp + 255) / 256)), dim3(256), 0, st, (const float *)(ws + w.slabs), w.nsplit, mlp, (int64_t)0,
+                       grads, (const float *)(ws + w.lpart), grid1, loss_kind == BRIEF_LOSS_EXTERNAL ? 0.f : na.inv_count, loss_out,
+                       upd ? 1 : 0, o, upd ? upd->params : nullptr, upd ? upd->s1 : nullptr, upd ? upd->s2 : nullptr);
+    HIP_TRY(hipGetLastError());
+    if (upd) {
+        hipLaunchKernelGGL(k_nerf_repack, dim3((unsigned)((lay.total + 255) / 256)), dim3(256), 0, st, *d, (const float *)upd->params, upd->pk);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" {
+
+int64_t brief_nerf_param_count(const brief_nerf_desc *d) { return check_nerf_desc(d) ? -1 : nerf_canon_count(*d); }
+int64_t brief_nerf_packed_count(const brief_nerf_desc *d) { return check_nerf_desc(d) ? -1 : nerf_layout(*d).total; }
+int64_t brief_nerf_train_workspace_bytes(const brief_nerf_desc *d, int64_t n)
+{
+    if (check_nerf_desc(d)) return -1;
+    if (n < 1) { fail(BRIEF_ERR_INVALID, "empty batch"); return -1; }
+    return nerf_ws_layout(*d, n).total * (int64_t)sizeof(float);
+}
+
+int brief_nerf_repack(const brief_nerf_desc *d, const float *params, float *packed, void *stream)
+{
+    if (int rc = check_nerf_desc(d)) return rc;
+    if (!params || !packed) return fail(BRIEF_ERR_INVALID, "null buffer");
+    const int64_t total = nerf_layout(*d).total;
+    hipLaunchKernelGGL(k_nerf_repack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *d, params, packed);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_nerf_forward(const brief_nerf_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                       void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream)
+{
+    if (int rc = check_nerf_desc(d)) return rc;
+    brief_siren_desc sd;
+    memset(&sd, 0, sizeof(sd));
+    sd.cin = d->cin;
+    if (int rc = check_batch(&sd, grid, batch, false)) return rc;
+    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
+    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
+    NerfArgs na;
+    nerf_forward_args(na, d, packed, batch->n, out, out_kind, scale_min, scale_max, vmin, vmax);
+    na.coords = batch->coords; na.idx = batch->idx; na.offset = batch->offset;
+    fill_grid(na.grid, grid);
+    return launch_nerf_fwd<false, false>(na, nerf_grid(*d, batch->n), (hipStream_t)stream);
+}
+
+int brief_nerf_forward_box(const brief_nerf_desc *d, const float *packed, const brief_grid_box *box, int64_t offset, int64_t n,
+                           void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream)
+{
+    if (int rc = check_nerf_desc(d)) return rc;
+    brief_siren_desc sd;
+    memset(&sd, 0, sizeof(sd));
+    sd.cin = d->cin;
+    int64_t voxels = 0;
+    if (int rc = check_box(&sd, box, &voxels)) return rc;
+    if (n < 1) return fail(BRIEF_ERR_INVALID, "empty batch");
+    if (offset < 0 || offset > voxels - n) return fail(BRIEF_ERR_INVALID, "offset + n exceeds the box's voxel count");
+    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
+    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
+    NerfArgs na;
+    nerf_forward_args(na, d, packed, n, out, out_kind, scale_min, scale_max, vmin, vmax);
+    na.offset = offset;
+    fill_grid(na.grid, &box->grid);
+    double total = 1.0;
+    for (int a = 0; a < 3; ++a) {
+        const bool on = a < box->grid.ndim;
+        na.box.start[a] = on ? box->start[a] : 0;
+        na.box.step[a] = on ? box->step[a] : 1;
+        na.box.extent[a] = on ? box->extent[a] : 1;
+        na.box.magic[a] = ~(uint64_t)0 / (uint64_t)na.box.extent[a] + 1;
+        total *= (double)na.box.extent[a];
+    }
+    na.box.fast = total < 4294967296.0;
+    return launch_nerf_fwd<false, true>(na, nerf_grid(*d, n), (hipStream_t)stream);
+}
+
+int brief_nerf_train_step(const brief_nerf_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                          int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
+                          void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return nerf_train_impl(d, packed, grid, batch, loss_kind, thr, beta, grads, loss_out, yhat_out, workspace, workspace_bytes, stream, nullptr);
+}
+
+int brief_nerf_fit(const brief_nerf_fit_job *j, int64_t steps, void *stream)
+{
+    if (!j) return fail(BRIEF_ERR_INVALID, "null job");
+    if (int rc = check_nerf_desc(&j->desc)) return rc;
+    if (steps < 0) return fail(BRIEF_ERR_INVALID, "bad step count");
+    if (j->batch.idx && j->idx_stride <= 0) return fail(BRIEF_ERR_INVALID, "brief_nerf_fit needs idx_stride > 0 with batch.idx (one index set per step)");
+    if (j->batch.idx && j->idx_stride < j->batch.n) return fail(BRIEF_ERR_INVALID, "idx_stride is smaller than the batch");
+    if (!j->params || !j->packed || !j->grads || !j->loss_out || !j->workspace) return fail(BRIEF_ERR_INVALID, "null buffer");
+    if (j->t0 < 0) return fail(BRIEF_ERR_INVALID, "bad step count");
+    if (j->n_milestones < 0 || (j->n_milestones > 0 && !j->milestones)) return fail(BRIEF_ERR_INVALID, "bad lr milestones");
+    if (j->optim_kind < BRIEF_OPT_ADAMAX || j->optim_kind > BRIEF_OPT_SGD) return fail(BRIEF_ERR_INVALID, "bad optimizer kind");
+    if (j->optim_kind != BRIEF_OPT_SGD && (!j->state1 || !j->state2)) return fail(BRIEF_ERR_INVALID, "optimizer state required");
+    hipStream_t st = (hipStream_t)stream;
+    // the schedule fields mean what they mean in brief_fit_job: brief_siren_fit's rule (fit_job_lr) evaluates them
+    brief_fit_job sched;
+    memset(&sched, 0, sizeof(sched));
+    sched.milestones = j->milestones; sched.n_milestones = j->n_milestones; sched.gamma = j->gamma; sched.t0 = j->t0;
+    sched.lr_table = j->lr_table;
+    double lr = j->lr;
+    for (int64_t k = 0; k < steps; ++k) {
+        const int64_t t = j->t0 + 1 + k;
+        fit_job_lr(&sched, t, k, &lr);
+        brief_batch_desc b = j->batch;
+        if (b.idx) b.idx = b.idx + k * j->idx_stride;
+        else if (b.rng_pop > 0) b.rng_step = (uint64_t)t;
+        FfnUpdate up;
+        up.opt = optim_scalars(j->optim_kind, lr, j->beta1_table ? j->beta1_table[k] : j->beta1, j->beta2, j->eps, t);
+        up.params = j->params; up.s1 = j->state1; up.s2 = j->state2; up.pk = j->packed;
+        if (int rc = nerf_train_impl(&j->desc, j->packed, &j->grid, &b, j->loss_kind, j->thr, j->beta, j->grads,
+                                     j->loss_log ? j->loss_log + k : j->loss_out, nullptr, j->workspace, j->workspace_bytes, (void *)st, &up))
             return rc;
     }
     if (j->loss_log && steps > 0)

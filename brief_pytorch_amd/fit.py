@@ -73,8 +73,9 @@ def cyclic_lr(base_lr, max_lr, step_size_up=2000, step_size_down=None, mode="tri
     return lr_at, beta1_at
 
 
-def _is_ffn(module):
-    return getattr(module, "kind", "SIREN") == "FFN"
+def _is_siren(module):
+    """SIREN runs through brief_siren_fit / brief_multi_fit; every other net kind (FFN, NeRF) names its own fit job type and entry"""
+    return getattr(module, "kind", "SIREN") == "SIREN"
 
 
 class Fitter:
@@ -163,7 +164,7 @@ class Fitter:
         b = _lib.BatchDesc(None, self.targets.data_ptr(), self.weights.data_ptr() if self.weights is not None else None,
                            idx.data_ptr() if idx is not None else None,
                            0, int(self.n), int(self.pop) if rnd else 0, int(self.seed) if rnd else 0, 0)
-        j = _lib.FfnFitJob() if _is_ffn(m) else _lib.FitJob()
+        j = _lib.FitJob() if _is_siren(m) else m._fit_job()
         j.desc, j.grid, j.batch = m.desc, g, b
         j.params, j.packed = m.params.data_ptr(), m.packed.data_ptr()
         j.state1, j.state2 = self.s1.data_ptr(), self.s2.data_ptr()
@@ -194,7 +195,7 @@ class Fitter:
         while True:
             k = min(steps, self.max_steps_per_call())
             j, loss_log = self.job(k, log)
-            fit = _lib.lib().brief_ffn_fit if _is_ffn(self.m) else _lib.lib().brief_siren_fit
+            fit = _lib.lib().brief_siren_fit if _is_siren(self.m) else getattr(_lib.lib(), self.m._fit_entry)
             _lib.check(fit(C.byref(j), k, _lib.stream_ptr()))
             self.t += k
             steps -= k
@@ -228,14 +229,14 @@ class MultiFitter:
         self.fitters = list(fitters)
 
     def run(self, steps, log=False):
-        """(brief_multi_fit co-trains SIREN fits only: FFN fits run one after another through their own Fitter.run)"""
-        if any(_is_ffn(f.m) for f in self.fitters):
-            res, sir = [None] * len(self.fitters), [i for i, f in enumerate(self.fitters) if not _is_ffn(f.m)]
+        """(brief_multi_fit co-trains SIREN fits only: FFN and NeRF fits run one after another through their own Fitter.run)"""
+        if not all(_is_siren(f.m) for f in self.fitters):
+            res, sir = [None] * len(self.fitters), [i for i, f in enumerate(self.fitters) if _is_siren(f.m)]
             if sir:
                 for i, r in zip(sir, MultiFitter([self.fitters[i] for i in sir]).run(steps, log)):
                     res[i] = r
             for i, f in enumerate(self.fitters):
-                if _is_ffn(f.m):
+                if not _is_siren(f.m):
                     res[i] = f.run(steps, log)
             return res
         if not self.fitters:

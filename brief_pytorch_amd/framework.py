@@ -105,9 +105,10 @@ class NFGR:
         precision = self.precision
         feats = int(self.opt.Module.phi.get("features", 0) or 0)
         limit = self.PRECISION_MAX_FEATURES.get(precision)
-        if self.opt.Module.phi.name == "FFN" and precision != "fp32":
-            # no low-precision FFN kernels: the budget keeps the reference's 2 bytes per parameter, the net runs (and is recorded) in fp32
-            logging.warning("Compress.precision=%s: FFN has fp32 kernels only; this net runs in fp32" % precision)
+        if self.opt.Module.phi.name in ("FFN", "NeRF") and precision != "fp32":
+            # no low-precision FFN / NeRF kernels: the budget keeps the reference's 2 bytes per parameter, the net runs (and is recorded)
+            # in fp32
+            logging.warning("Compress.precision=%s: %s has fp32 kernels only; this net runs in fp32" % (precision, self.opt.Module.phi.name))
             precision = "fp32"
         elif limit is not None and feats > limit:
             # decided BEFORE any work starts (in a DivideTask one large block would otherwise abort the job after partitioning):

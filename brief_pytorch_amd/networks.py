@@ -17,7 +17,7 @@ import torch
 
 from . import _lib, region
 
-__all__ = ["SIREN", "FFN", "init_phi", "ALLPHI", "ALL_CALC_PHI_FEATURES", "ALL_CALC_PHI_PARAM_COUNT",
+__all__ = ["SIREN", "FFN", "NeRF", "init_phi", "ALLPHI", "ALL_CALC_PHI_FEATURES", "ALL_CALC_PHI_PARAM_COUNT",
            "ALL_CHECK_PARAM_COUNT", "get_nnmodule_param_count"]
 
 
@@ -492,6 +492,7 @@ class FFN(SIREN):
     (brief_ffn_fit) updates the MLP span only."""
 
     kind = "FFN"
+    _fit_job, _fit_entry = _lib.FfnFitJob, "brief_ffn_fit"      # brief_*_fit_job type and brief_*_fit entry (Fitter, fit_step)
 
     def __init__(self, coords_channel=3, data_channel=1, embsize=256, scale=10, features=256, layers=5, skip=False,
                  device=None, precision="fp32", **kwargs):
@@ -611,7 +612,7 @@ class FFN(SIREN):
 
     def fit_step(self, n, targets, opt_kind, s1, s2, lr, t, idx=None, weights=None, grid=None, offset=0,
                  loss="datal2", thr=0.0, beta=0.01, betas=(0.9, 0.999), eps=1e-8, rng=None):
-        """train_step + optimizer update of the MLP span + refresh of the packed copy: one step of brief_ffn_fit"""
+        """train_step + optimizer update of the MLP span + refresh of the packed copy: one step of brief_ffn_fit (brief_nerf_fit)"""
         self._require_gpu()
         self.sync_packed()
         self.ensure_train_buffers(n)
@@ -621,7 +622,7 @@ class FFN(SIREN):
         dev = self.params.device
         b = _lib.BatchDesc(None, _dev_ptr(targets, torch.float32, "targets", dev), _dev_ptr(weights, torch.float32, "weights", dev),
                            _dev_ptr(idx, torch.int64, "idx", dev), int(offset), int(n), int(pop), int(seed), 0)
-        j = _lib.FfnFitJob()
+        j = self._fit_job()
         j.desc, j.grid, j.batch = self.desc, g, b
         j.params, j.packed, j.state1, j.state2 = self.params.data_ptr(), self.packed.data_ptr(), _lib.ptr(s1), _lib.ptr(s2)
         j.grads, j.loss_out, j.loss_log = self.grads.data_ptr(), self._loss.data_ptr(), None
@@ -630,7 +631,7 @@ class FFN(SIREN):
         j.lr, j.beta1, j.beta2, j.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
         j.n_milestones, j.gamma, j.t0 = 0, 1.0, int(t) - 1
         j.idx_stride = int(n) if idx is not None else 0      # (in-kernel draws of step t are keyed by rng_step = t0 + 1 = t)
-        _lib.check(_lib.lib().brief_ffn_fit(C.byref(j), 1, _lib.stream_ptr()))
+        _lib.check(getattr(_lib.lib(), self._fit_entry)(C.byref(j), 1, _lib.stream_ptr()))
         return self._loss
 
     # ---- budget -> width (utils/Networks.py:188-207)
@@ -660,6 +661,152 @@ class FFN(SIREN):
             raise NotImplementedError("FFN(skip=True) is unsupported on the fused path")
 
 
+class NeRF(FFN):
+    """reference: utils/Networks.py:64-136 (PosEncodingNeRF + NeRF).  Parameters live in one canonical buffer in state_dict() order
+    [W0 b0 | hidden | head] (include/brief_hip.h, brief_nerf_desc); with skip the hidden layer sl = (layers - 1) // 2 is
+    Linear(d + F, F) on cat[encoding, h].  The encoding has no parameters; the whole buffer is trained.  Like FFN it has fp32 kernels
+    only (half() / low-precision modes run in fp32 with a warning)."""
+
+    kind = "NeRF"
+    _fit_job, _fit_entry = _lib.NerfFitJob, "brief_nerf_fit"
+
+    def __init__(self, coords_channel=3, data_channel=1, frequencies=10, features=256, layers=5, skip=True,
+                 device=None, precision="fp32", **kwargs):
+        """w0 / res / output_act / embsize of another net's YAML are ignored, as NeRF(**phi) ignores them.  precision: the fused path
+        is fp32 only; 'bf16' / 'bf16x3' run in fp32 with a warning."""
+        if str(precision) not in ("fp32", "f32"):
+            logging.warning("NeRF: no %s kernels; the net runs in fp32" % precision)
+        self.coords_channel, self.data_channel = int(coords_channel), int(data_channel)
+        self.features, self.layers = int(features), int(layers)
+        self.frequencies, self.skip = int(frequencies), bool(skip)
+        NeRF._check(self.coords_channel, self.data_channel, self.features, self.frequencies, self.layers, self.skip)
+        self.precision = "fp32"
+        self.w0, self.output_act = 0.0, False
+        self.desc = _lib.NerfDesc(self.coords_channel, self.data_channel, self.layers, self.features, self.frequencies, int(self.skip))
+        F, d = self.features, NeRF.encoding_width(self.coords_channel, self.frequencies)
+        self.skip_layer = (self.layers - 1) // 2 if self.skip else -1
+        self._shapes = [(F, d)] + [(F, d + F if l == self.skip_layer else F) for l in range(1, self.layers - 1)] + [(self.data_channel, F)]
+        self.bv_count = 0
+        self.param_count = sum(o * i + o for o, i in self._shapes)
+        self.params = self._reference_init()
+        self.grads = None
+        self.packed = None
+        self._stale = True
+        self._seen_version = -1
+        self._autograd = False
+        self._anchor = None
+        self._ws = None
+        self._fws = None
+        self._loss = None
+        self.positional_encoding = _PosEncoding(self.coords_channel, self.frequencies)
+        net, off = [], 0
+        for (o, i) in self._shapes:
+            net.append(_Seq(_Linear(self, off, (o, i), off + o * i)))
+            off += o * i + o
+        self.net = net
+        if device is not None:
+            self.to(device)
+
+    @staticmethod
+    def encoding_width(coords_channel, frequencies):
+        """PosEncodingNeRF.out_channel: cin (1 + 2 frequencies)"""
+        return coords_channel + 2 * coords_channel * frequencies
+
+    @staticmethod
+    def _check(cin, cout, features, frequencies, layers, skip):
+        """the limits of include/brief_hip.h (brief_nerf_desc); the reference itself fails on layers = 2 with skip (its forward
+        concatenates the encoding with itself)"""
+        if cin not in (2, 3) or not 1 <= cout <= 4:
+            raise NotImplementedError("NeRF: coords_channel must be 2 or 3 and data_channel 1..4")
+        if layers < 2 or (skip and layers < 3):
+            raise NotImplementedError("NeRF: layers must be >= 2, and >= 3 with skip=True (got layers=%d, skip=%s)" % (layers, skip))
+        if not 1 <= features <= 1024:
+            raise NotImplementedError("NeRF: features must be 1..1024 on the fused path (got %d)" % features)
+        if not 0 <= frequencies <= 16:
+            raise NotImplementedError("NeRF: frequencies must be 0..16 on the fused path (got %d)" % frequencies)
+
+    def _reference_init(self):
+        """the nn.Linear default inits (kaiming_uniform(a=sqrt 5) weight, then bias; fan-in d + F for the skip layer) in layer order on
+        the caller's global generator (NeRF does not reseed): the values AND the generator state afterwards equal the reference's"""
+        parts = []
+        for (o, i) in self._shapes:
+            w = torch.empty(o, i)
+            gain = math.sqrt(2.0 / (1 + math.sqrt(5) ** 2))
+            w.uniform_(-math.sqrt(3.0) * gain / math.sqrt(i), math.sqrt(3.0) * gain / math.sqrt(i))
+            b = torch.empty(o)
+            b.uniform_(-1 / math.sqrt(i), 1 / math.sqrt(i))
+            parts += [w.reshape(-1), b]
+        return torch.cat(parts).contiguous()
+
+    def state_dict(self):
+        return SIREN.state_dict(self)
+
+    def load_state_dict(self, sd):
+        SIREN.load_state_dict(self, sd)
+
+    def half(self):
+        """no low-precision NeRF kernels: the net stays in fp32 (NFGR keeps the reference's 2-bytes-per-parameter budget and records
+        phi_precision: fp32)"""
+        if not getattr(NeRF, "_warned_half", False):
+            NeRF._warned_half = True
+            logging.warning("NeRF.half(): there are no low-precision NeRF kernels; the net stays in fp32")
+        return self
+
+    # ---- C-ABI entries
+    def _abi_packed_count(self):
+        return _lib.lib().brief_nerf_packed_count(C.byref(self.desc))
+
+    def _abi_repack(self):
+        return _lib.lib().brief_nerf_repack(C.byref(self.desc), _lib.ptr(self.params), _lib.ptr(self.packed), _lib.stream_ptr())
+
+    def _abi_forward(self, grid, batch, out, kind, scale, vrange, n):
+        return _lib.lib().brief_nerf_forward(C.byref(self.desc), _lib.ptr(self.packed), C.byref(grid) if grid is not None else None,
+                                             C.byref(batch), _lib.ptr(out), kind, float(scale[0]), float(scale[1]),
+                                             float(vrange[0]), float(vrange[1]), _lib.stream_ptr())
+
+    def _abi_forward_box(self, box, off, cnt, out, kind, scale, vrange):
+        return _lib.lib().brief_nerf_forward_box(C.byref(self.desc), _lib.ptr(self.packed), C.byref(box), off, cnt, _lib.ptr(out),
+                                                 kind, float(scale[0]), float(scale[1]), float(vrange[0]), float(vrange[1]),
+                                                 _lib.stream_ptr())
+
+    def _abi_train_ws_bytes(self, n):
+        return _lib.lib().brief_nerf_train_workspace_bytes(C.byref(self.desc), int(n))
+
+    def _abi_train_step(self, g, b, loss_kind, thr, beta, yhat):
+        return _lib.lib().brief_nerf_train_step(
+            C.byref(self.desc), _lib.ptr(self.packed), C.byref(g) if g is not None else None, C.byref(b),
+            loss_kind, float(thr), float(beta), _lib.ptr(self.grads), _lib.ptr(self._loss), _lib.ptr(yhat),
+            _lib.ptr(self._ws), self._ws.numel() * 4, _lib.stream_ptr())
+
+    # ---- budget -> width (utils/Networks.py:118-136)
+    @staticmethod
+    def calc_param_count(coords_channel, data_channel, features, frequencies, layers, skip, **kwargs):
+        """the reference's signature (frequencies, layers and skip have no default) and formula: d F + F + (layers-2)(F^2 + F) [+ d F with skip] + F cout + cout, d = cin (1 + 2 frequencies)"""
+        d = NeRF.encoding_width(coords_channel, frequencies)
+        return int(d * features + features + (layers - 2) * (features ** 2 + features) + (d * features if skip else 0)
+                   + features * data_channel + data_channel)
+
+    @staticmethod
+    def calc_features(param_count, coords_channel, data_channel, frequencies, layers, skip, **kwargs):
+        """the reference's signature (frequencies, layers and skip have no default); the positive root of (layers-2) F^2 + ([2] d + 1 + layers-2 + cout) F + cout = P, rounded (the reference's formula; the
+        linear case layers = 2 solved directly instead of dividing by zero)"""
+        d = NeRF.encoding_width(coords_channel, frequencies)
+        a = layers - 2
+        b = (2 * d if skip else d) + 1 + layers - 2 + data_channel
+        c = -param_count + data_channel
+        if a == 0:
+            return round(-c / b)
+        return round((-b + math.sqrt(b ** 2 - 4 * a * c)) / (2 * a))
+
+
+class _PosEncoding:
+    """stands for PosEncodingNeRF (no parameters): the encoding runs inside the fused kernels"""
+
+    def __init__(self, in_channel, frequencies):
+        self.in_channel, self.frequencies = in_channel, frequencies
+        self.out_channel = NeRF.encoding_width(in_channel, frequencies)
+
+
 class _Embedding:
     """stands for FourierFeatureEmbedding: `.bvals` is a window into the canonical buffer (requires_grad False)"""
 
@@ -687,17 +834,25 @@ def get_nnmodule_param_count(module):
     return sum(int(np.prod(p.shape)) for p in module.state_dict().values())
 
 
-# registry with the reference's names (utils/Networks.py:795-802).  SIREN and FFN exist on the fused
+# registry with the reference's names (utils/Networks.py:795-802).  SIREN, FFN and NeRF exist on the fused
 # path; every other phi.name of the reference raises instead of silently running something else.
-ALLPHI = {"SIREN": SIREN, "FFN": FFN}
-ALL_CALC_PHI_FEATURES = {"SIREN": SIREN.calc_features, "FFN": FFN.calc_features}
-ALL_CALC_PHI_PARAM_COUNT = {"SIREN": SIREN.calc_param_count, "FFN": FFN.calc_param_count}
+ALLPHI = {"SIREN": SIREN, "FFN": FFN, "NeRF": NeRF}
+ALL_CALC_PHI_FEATURES = {"SIREN": SIREN.calc_features, "FFN": FFN.calc_features, "NeRF": NeRF.calc_features}
+ALL_CALC_PHI_PARAM_COUNT = {"SIREN": SIREN.calc_param_count, "FFN": FFN.calc_param_count, "NeRF": NeRF.calc_param_count}
 ALL_CHECK_PARAM_COUNT = {}
+# keys a Module.phi spec of this net must name: the reference's NeRF budget rule (calc_features / calc_param_count,
+# utils/Networks.py:118-136) takes frequencies and skip without defaults, so its NFGR cannot build a NeRF from a spec that leaves them
+# out; init_phi refuses such a spec by name instead of filling in the constructor's defaults
+REQUIRED_PHI_KEYS = {"NeRF": ("frequencies", "skip")}
 
 
 def init_phi(kwargs):
     kwargs = copy.deepcopy(dict(kwargs))
     name = kwargs.pop("name")
     if name not in ALLPHI:
-        raise NotImplementedError("Module.phi.name=%r is not available on the fused MI355X path (only SIREN and FFN)" % name)
+        raise NotImplementedError("Module.phi.name=%r is not available on the fused MI355X path (only SIREN, FFN and NeRF)" % name)
+    missing = [k for k in REQUIRED_PHI_KEYS.get(name, ()) if k not in kwargs]
+    if missing:
+        raise NotImplementedError("Module.phi.name=%r without %s is not supported: the reference's budget rule for this net needs %s "
+                                  "in the spec" % (name, " / ".join(missing), " and ".join(REQUIRED_PHI_KEYS[name])))
     return ALLPHI[name](**kwargs)

@@ -301,6 +301,67 @@ typedef struct brief_ffn_fit_job {
 /* `steps` optimizer steps (train step + reduction + update + repack: four launches each, no host synchronisation) */
 int brief_ffn_fit(const brief_ffn_fit_job *job, int64_t steps, void *stream);
 
+/* ---- NeRF: positional-encoding network (Mildenhall et al.)  utils/Networks.py:64-136 ----------------------------------------
+ *   enc = [x_0 .. x_{cin-1}, sin(2^0 pi x_0), cos(2^0 pi x_0), sin(2^0 pi x_1), cos(2^0 pi x_1), ..., cos(2^{Lf-1} pi x_{cin-1})]
+ *   (d = cin (1 + 2 frequencies) columns; the phase is the fp32 number 2^i fl32(fl32(pi) x), as the reference's fp32 torch.sin sees it)
+ *   Linear(d, F) + ReLU, (layers - 2) x (Linear(F, F) + ReLU), Linear(F, cout)  (no output activation)
+ *   skip != 0: the hidden layer sl = (layers - 1) / 2 is Linear(d + F, F) + ReLU on cat[enc, h] (encoding columns first)
+ * Limits (anything else: BRIEF_ERR_INVALID with a message naming the limit): fp32 only, cin 2 | 3, cout 1 .. 4, layers >= 2 (>= 3 with
+ * skip), features 1 .. 1024 (padded internally to whole 32-wide tiles), frequencies 0 .. 16, skip 0 | 1.
+ * Canonical parameter buffer (== torch parameters() / state_dict() order):
+ *   W0 [F][d] b0 [F] | (W_l [F][F] b_l [F]) x (layers - 2), W_sl [F][d + F] with skip | Wh [cout][F] bh [cout]
+ * The whole buffer is trained (the encoding has no parameters). */
+typedef struct {
+    int32_t cin;          /* 2 | 3 */
+    int32_t cout;         /* 1 .. 4 */
+    int32_t layers;       /* >= 2; >= 3 with skip */
+    int32_t features;     /* 1 .. 1024 */
+    int32_t frequencies;  /* 0 .. 16 */
+    int32_t skip;         /* 0 | 1 */
+} brief_nerf_desc;
+
+/* floats of the canonical buffer (== NeRF.calc_param_count) / of the fragment-ordered copy / train-step scratch bytes */
+int64_t brief_nerf_param_count(const brief_nerf_desc *d);
+int64_t brief_nerf_packed_count(const brief_nerf_desc *d);
+int64_t brief_nerf_train_workspace_bytes(const brief_nerf_desc *d, int64_t n);
+/* canonical params -> fragment-ordered copy (call after every change of params made outside brief_nerf_fit) */
+int brief_nerf_repack(const brief_nerf_desc *d, const float *params, float *packed, void *stream);
+/* NeRF.forward under no_grad, with the out_kind epilogue of brief_siren_forward (no scratch) */
+int brief_nerf_forward(const brief_nerf_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                       void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream);
+/* the box decode of brief_siren_forward_box (same box rules and refusals) */
+int brief_nerf_forward_box(const brief_nerf_desc *d, const float *packed, const brief_grid_box *box, int64_t offset, int64_t n,
+                           void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream);
+/* forward + loss + backward of one batch, as brief_siren_train_step (grads: canonical layout) */
+int brief_nerf_train_step(const brief_nerf_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                          int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
+                          void *workspace, int64_t workspace_bytes, void *stream);
+/* brief_fit_job with a NeRF desc: every field after `desc` means exactly what it means in brief_fit_job
+ * (workspace: brief_nerf_train_workspace_bytes(desc, batch.n)) */
+typedef struct brief_nerf_fit_job {
+    brief_nerf_desc desc;
+    brief_grid_desc grid;
+    brief_batch_desc batch;
+    float *params, *packed;
+    float *state1, *state2;
+    float *grads;
+    float *loss_out;
+    float *loss_log;
+    void *workspace;
+    int64_t workspace_bytes;
+    int32_t loss_kind, optim_kind;
+    float thr, beta;
+    double lr, beta1, beta2, eps;
+    const int64_t *milestones;
+    int32_t n_milestones, reserved;
+    double gamma;
+    int64_t t0;
+    const double *lr_table, *beta1_table;
+    int64_t idx_stride;
+} brief_nerf_fit_job;
+/* `steps` optimizer steps (train step + reduction + update + repack: four launches each, no host synchronisation) */
+int brief_nerf_fit(const brief_nerf_fit_job *job, int64_t steps, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
