@@ -70,6 +70,15 @@ class NerfFitJob(C.Structure):      # brief_nerf_fit_job: brief_fit_job's fields
     _fields_ = [("desc", NerfDesc)] + FitJob._fields_[1:]
 
 
+class MfnDesc(C.Structure):         # brief_mfn_desc
+    _fields_ = [("cin", C.c_int32), ("cout", C.c_int32), ("layers", C.c_int32), ("features", C.c_int32),
+                ("filter", C.c_int32), ("output_act", C.c_int32)]
+
+
+class MfnFitJob(C.Structure):       # brief_mfn_fit_job: brief_fit_job's fields after the desc
+    _fields_ = [("desc", MfnDesc)] + FitJob._fields_[1:]
+
+
 LOSS_KIND = {"datal2": 0, "datasmoothl1": 1, "external": 2}
 OPT_KIND = {"Adamax": 0, "Adam": 1, "SGD": 2}
 OUT_F32, OUT_U8, OUT_U16 = 0, 1, 2
@@ -83,7 +92,9 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_ffn_param_count", "brief_ffn_packed_count", "brief_ffn_train_workspace_bytes", "brief_ffn_repack", "brief_ffn_forward",
            "brief_ffn_forward_box", "brief_ffn_train_step", "brief_ffn_fit",
            "brief_nerf_param_count", "brief_nerf_packed_count", "brief_nerf_train_workspace_bytes", "brief_nerf_repack", "brief_nerf_forward",
-           "brief_nerf_forward_box", "brief_nerf_train_step", "brief_nerf_fit"]
+           "brief_nerf_forward_box", "brief_nerf_train_step", "brief_nerf_fit",
+           "brief_mfn_param_count", "brief_mfn_packed_count", "brief_mfn_train_workspace_bytes", "brief_mfn_repack", "brief_mfn_forward",
+           "brief_mfn_forward_box", "brief_mfn_train_step", "brief_mfn_fit"]
 
 
 def needs_build():
@@ -188,6 +199,17 @@ def lib():
     L.brief_nerf_forward_box.argtypes = [np_, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
     L.brief_nerf_train_step.argtypes = [np_, vp, gp, bp, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, C.c_int64, vp]
     L.brief_nerf_fit.argtypes = [C.POINTER(NerfFitJob), C.c_int64, vp]
+    mp_ = C.POINTER(MfnDesc)
+    for name in ("brief_mfn_param_count", "brief_mfn_packed_count"):
+        getattr(L, name).restype = C.c_int64
+        getattr(L, name).argtypes = [mp_]
+    L.brief_mfn_train_workspace_bytes.restype = C.c_int64
+    L.brief_mfn_train_workspace_bytes.argtypes = [mp_, C.c_int64]
+    L.brief_mfn_repack.argtypes = [mp_, vp, vp, vp]
+    L.brief_mfn_forward.argtypes = [mp_, vp, gp, bp, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
+    L.brief_mfn_forward_box.argtypes = [mp_, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
+    L.brief_mfn_train_step.argtypes = [mp_, vp, gp, bp, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, C.c_int64, vp]
+    L.brief_mfn_fit.argtypes = [C.POINTER(MfnFitJob), C.c_int64, vp]
     _LIB = L
     return L
 

@@ -55,6 +55,7 @@
 #include "brief_aux.inc"        // k_repack, index stream, metrics, deblocking filter
 #include "brief_ffn.inc"        // FFN: k_ffn_fwd, k_ffn_wgrad, k_ffn_reduce, k_ffn_repack
 #include "brief_nerf.inc"       // NeRF: k_nerf_fwd, k_nerf_wgrad, k_nerf_repack
+#include "brief_mfn.inc"        // MFN: k_mfn_fwd, k_mfn_wgrad, k_mfn_repack
 
 // =============================================================================================
 // C-ABI
@@ -2121,6 +2122,327 @@ int brief_nerf_fit(const brief_nerf_fit_job *j, int64_t steps, void *stream)
         up.params = j->params; up.s1 = j->state1; up.s2 = j->state2; up.pk = j->packed;
         if (int rc = nerf_train_impl(&j->desc, j->packed, &j->grid, &b, j->loss_kind, j->thr, j->beta, j->grads,
                                      j->loss_log ? j->loss_log + k : j->loss_out, nullptr, j->workspace, j->workspace_bytes, (void *)st, &up))
+            return rc;
+    }
+    if (j->loss_log && steps > 0)
+        HIP_TRY(hipMemcpyAsync(j->loss_out, j->loss_log + steps - 1, sizeof(float), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+}   // extern "C"
+
+// =============================================================================================
+// MFN (multiplicative filter networks, brief_mfn.inc): train step = k_mfn_fwd<TRAIN> + k_mfn_wgrad + k_ffn_reduce (bv = 0)
+// (+ k_mfn_repack after an update)
+static int check_mfn_desc(const brief_mfn_desc *d)
+{
+    if (!d) return fail(BRIEF_ERR_INVALID, "null desc");
+    if (d->cin != 2 && d->cin != 3) return fail(BRIEF_ERR_INVALID, "MFN: coords_channel must be 2 or 3");
+    if (d->cout < 1 || d->cout > 4) return fail(BRIEF_ERR_INVALID, "MFN: data_channel must be 1..4");
+    if (d->layers < 2) return fail(BRIEF_ERR_INVALID, "MFN: layers must be >= 2");
+    if (d->features < 1 || d->features > 1024) return fail(BRIEF_ERR_INVALID, "MFN: features must be 1..1024 on the fused path");
+    if (d->filter != 0 && d->filter != 1) return fail(BRIEF_ERR_INVALID, "MFN: filter must be 0 (Fourier) or 1 (Gabor)");
+    if (d->output_act != 0 && d->output_act != 1) return fail(BRIEF_ERR_INVALID, "MFN: output_act must be 0 or 1");
+    return 0;
+}
+
+static int mfn_lds_bytes(const brief_mfn_desc &d)
+{
+    const MfnLayout l = mfn_layout(d);
+    return (int)sizeof(float) * (32 * l.FP + 128);
+}
+// persistent grid: up to two workgroups per CU (one wave per SIMD each), fewer when the LDS image does not fit twice
+static int mfn_grid(const brief_mfn_desc &d, int64_t n)
+{
+    const int64_t tiles = (n + 31) / 32;
+    const int by_lds = (160 * 1024) / mfn_lds_bytes(d);
+    const int64_t cap = (int64_t)kCUs * (by_lds < 2 ? (by_lds > 0 ? by_lds : 1) : 2);
+    return (int)(tiles < cap ? tiles : cap);
+}
+struct MfnWs { int64_t npad, Z, U, DU, DA, Q, XP, G, lpart, slabs, total, chunk; int nsplit, waves; };
+// weight-gradient block i (0 .. mfn_wgrad_count - 1) of the net: hidden layers | head | per filter (W / b, then Gabor's mu / gamma);
+// planes at the workspace offsets of w (ws == nullptr: shapes only), wave_begin left to the caller
+static int mfn_wgrad_count(const brief_mfn_desc &d) { return d.layers - 1 + (d.layers - 1) * (d.filter ? 2 : 1); }
+static MfnWgradBlock mfn_wgrad_block(const brief_mfn_desc &d, const MfnWs &w, float *ws, const float *packed, int i)
+{
+    const MfnLayout lay = mfn_layout(d);
+    const int F = d.features, L = d.layers, cin = d.cin;
+    const int64_t plane = (int64_t)lay.FP * w.npad;
+    int64_t A, B, w_off, b_off;
+    int arows = F, brows = F, ldw = F, gabor = 0;
+    const float *fg = nullptr;
+    if (i < L - 2) {                                                   // hidden layer l = i + 1
+        const int l = i + 1;
+        A = w.DU + (int64_t)(l - 1) * plane; B = w.Z + (int64_t)(l - 1) * plane;
+        w_off = mfn_canon_hidden(d, l); b_off = w_off + (int64_t)F * F;
+    } else if (i == L - 2) {                                           // head
+        A = w.G; B = w.Z + (int64_t)(L - 2) * plane; arows = d.cout;
+        w_off = mfn_canon_head(d); b_off = w_off + (int64_t)d.cout * F;
+    } else {
+        const int per = d.filter ? 2 : 1, j = i - (L - 1), fi = j / per;
+        B = w.XP; ldw = cin;
+        if (j % per == 0) {                                            // filter fi: Wf / bf
+            A = w.DA + (int64_t)fi * plane; brows = cin;
+            w_off = mfn_canon_filter_w(d, fi); b_off = w_off + (int64_t)F * cin;
+        } else {                                                       // Gabor filter fi: mu / gamma
+            A = w.Q + (int64_t)fi * plane; brows = cin + 2;
+            w_off = mfn_canon_filter(d, fi); b_off = -1; gabor = 1;
+            fg = packed ? packed + lay.filt + (int64_t)fi * lay.filt_stride + 4 * (int64_t)lay.FP : nullptr;
+        }
+    }
+    MfnWgradBlock b;
+    memset(&b, 0, sizeof(b));
+    b.A = ws ? ws + A : nullptr; b.B = ws ? ws + B : nullptr;
+    b.arows = arows; b.brows = brows;
+    b.mb = (arows + 63) / 64; b.nb = (brows + 63) / 64;
+    b.w_off = w_off; b.b_off = b_off; b.ldw = ldw;
+    b.gabor = gabor; b.fg = fg;
+    return b;
+}
+static MfnWs mfn_ws_layout(const brief_mfn_desc &d, int64_t n)
+{
+    const MfnLayout lay = mfn_layout(d);
+    MfnWs w;
+    w.npad = (n + 31) / 32 * 32;
+    const int64_t plane = (int64_t)lay.FP * w.npad;
+    const int nf = d.layers - 1, nh = d.layers - 2;
+    w.Z = 0;
+    w.U = w.Z + nf * plane;
+    w.DU = w.U + nh * plane;
+    w.DA = w.DU + nh * plane;
+    w.Q = w.DA + nf * plane;
+    w.XP = w.Q + (d.filter ? nf : 0) * plane;
+    w.G = w.XP + 5 * w.npad;
+    w.lpart = w.G + 4 * w.npad;
+    w.slabs = w.lpart + kFfnLossParts;
+    w.waves = 0;
+    for (int i = 0; i < mfn_wgrad_count(d); ++i) {
+        const MfnWgradBlock b = mfn_wgrad_block(d, w, nullptr, nullptr, i);
+        w.waves += b.mb * b.nb;
+    }
+    const int64_t wgs = (w.waves + 3) / 4;
+    int64_t ns = (8 * (int64_t)kCUs + wgs - 1) / wgs;      // K-splits: about eight workgroups per CU (as k_ffn_wgrad)
+    if (ns > 64) ns = 64;
+    if (ns > w.npad / 256) ns = w.npad / 256;
+    if (ns < 1) ns = 1;
+    w.chunk = (w.npad / ns + 31) / 32 * 32;
+    w.nsplit = (int)((w.npad + w.chunk - 1) / w.chunk);
+    w.total = w.slabs + (int64_t)w.nsplit * mfn_canon_count(d);
+    return w;
+}
+
+template <bool TRAIN, bool BOX, bool GABOR>
+static int launch_mfn_fwd_kind(const MfnArgs &ma, int grid, hipStream_t st)
+{
+    const int mtw = (ma.nt + 3) / 4;
+    const int lds = mfn_lds_bytes(ma.d);
+    const void *fn = nullptr;
+    switch (mtw) {
+#define MFN_CASE(M) case M: fn = (const void *)k_mfn_fwd<M, TRAIN, BOX, GABOR>; break;
+        MFN_CASE(1) MFN_CASE(2) MFN_CASE(3) MFN_CASE(4) MFN_CASE(5) MFN_CASE(6) MFN_CASE(7) MFN_CASE(8)
+#undef MFN_CASE
+        default: return fail(BRIEF_ERR_INVALID, "MFN: features must be 1..1024 on the fused path");
+    }
+    if (int rc = dev_attr_once(fn, lds)) return rc;
+    switch (mtw) {
+#define MFN_CASE(M) case M: hipLaunchKernelGGL((k_mfn_fwd<M, TRAIN, BOX, GABOR>), dim3(grid), dim3(256), lds, st, ma); break;
+        MFN_CASE(1) MFN_CASE(2) MFN_CASE(3) MFN_CASE(4) MFN_CASE(5) MFN_CASE(6) MFN_CASE(7) MFN_CASE(8)
+#undef MFN_CASE
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+template <bool TRAIN, bool BOX>
+static int launch_mfn_fwd(const MfnArgs &ma, int grid, hipStream_t st)
+{
+    return ma.d.filter ? launch_mfn_fwd_kind<TRAIN, BOX, true>(ma, grid, st) : launch_mfn_fwd_kind<TRAIN, BOX, false>(ma, grid, st);
+}
+
+static void mfn_forward_args(MfnArgs &ma, const brief_mfn_desc *d, const float *packed, int64_t n, void *out, int out_kind,
+                             float scale_min, float scale_max, double vmin, double vmax)
+{
+    memset(&ma, 0, sizeof(ma));
+    const MfnLayout lay = mfn_layout(*d);
+    ma.d = *d; ma.nt = lay.nt; ma.pk = packed;
+    ma.n = n; ma.npad = (n + 31) / 32 * 32;
+    ma.out = out; ma.out_kind = out_kind;
+    ma.scale_min = scale_min;
+    ma.den = (float)((double)scale_max - (double)scale_min);
+    ma.span = (float)(vmax - vmin);
+    ma.vmin = (float)vmin;
+}
+
+static int mfn_train_impl(const brief_mfn_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                          int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
+                          void *workspace, int64_t workspace_bytes, void *stream, const FfnUpdate *upd)
+{
+    if (int rc = check_mfn_desc(d)) return rc;
+    brief_siren_desc sd;      // check_batch reads cin only
+    memset(&sd, 0, sizeof(sd));
+    sd.cin = d->cin;
+    if (int rc = check_batch(&sd, grid, batch, true)) return rc;
+    if (!packed || !grads || !loss_out || !workspace) return fail(BRIEF_ERR_INVALID, "null buffer");
+    if (loss_kind < BRIEF_LOSS_L2 || loss_kind > BRIEF_LOSS_EXTERNAL) return fail(BRIEF_ERR_INVALID, "bad loss_kind");
+    const MfnWs w = mfn_ws_layout(*d, batch->n);
+    if (workspace_bytes < w.total * (int64_t)sizeof(float)) return fail(BRIEF_ERR_WORKSPACE, "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    float *ws = (float *)workspace;
+    const MfnLayout lay = mfn_layout(*d);
+    MfnArgs ma;
+    mfn_forward_args(ma, d, packed, batch->n, nullptr, 0, 0.f, 1.f, 0.0, 1.0);
+    ma.coords = batch->coords; ma.targets = batch->targets; ma.weights = batch->weights;
+    ma.idx = batch->idx; ma.offset = batch->offset;
+    if (!batch->idx && batch->rng_pop > 0) { ma.rng_pop = (uint64_t)batch->rng_pop; ma.rng_seed = batch->rng_seed; ma.rng_step = batch->rng_step; }
+    fill_grid(ma.grid, grid);
+    ma.loss_kind = loss_kind; ma.thr = thr; ma.beta = beta;
+    ma.inv_count = (float)(1.0 / ((double)batch->n * d->cout));
+    ma.Z = ws + w.Z; ma.U = ws + w.U; ma.DU = ws + w.DU; ma.DA = ws + w.DA; ma.Q = ws + w.Q; ma.XP = ws + w.XP; ma.G = ws + w.G;
+    ma.lpart = ws + w.lpart;
+    ma.npad = w.npad; ma.yhat_out = yhat_out;
+    const int grid1 = mfn_grid(*d, batch->n);
+    const bool prof = prof_live();
+    hipEvent_t *pev = prof ? dev_state()->prof_ev : nullptr;
+    if (prof) HIP_TRY(hipEventRecord(pev[2 * g_prof_n], st));
+    if (int rc = launch_mfn_fwd<true, false>(ma, grid1, st)) return rc;
+    if (prof) { HIP_TRY(hipEventRecord(pev[2 * g_prof_n + 1], st)); ++g_prof_n; }
+    // weight gradients, at most MFN_WGRAD_BLOCKS blocks per launch
+    const int64_t mlp = mfn_canon_count(*d);
+    const int nblocks = mfn_wgrad_count(*d);
+    for (int b0 = 0; b0 < nblocks; b0 += MFN_WGRAD_BLOCKS) {
+        MfnWgradArgs wa;
+        memset(&wa, 0, sizeof(wa));
+        wa.npad = w.npad; wa.chunk = w.chunk; wa.mlp = mlp; wa.slabs = ws + w.slabs;
+        wa.cin = d->cin; wa.FP = lay.FP;
+        wa.nblocks = (nblocks - b0) < MFN_WGRAD_BLOCKS ? (nblocks - b0) : MFN_WGRAD_BLOCKS;
+        int waves = 0;
+        for (int i = 0; i < wa.nblocks; ++i) {
+            wa.blk[i] = mfn_wgrad_block(*d, w, ws, packed, b0 + i);
+            wa.blk[i].wave_begin = waves;
+            waves += wa.blk[i].mb * wa.blk[i].nb;
+        }
+        wa.waves = waves;
+        hipLaunchKernelGGL(k_mfn_wgrad, dim3((unsigned)((waves + 3) / 4), (unsigned)w.nsplit), dim3(256), 0, st, wa);
+        HIP_TRY(hipGetLastError());
+    }
+    OptimScalars o;
+    memset(&o, 0, sizeof(o));
+    if (upd) o = upd->opt;
+    hipLaunchKernelGGL(k_ffn_reduce, dim3((unsigned)((mlp + 255) / 256)), dim3(256), 0, st, (const float *)(ws + w.slabs), w.nsplit, mlp, (int64_t)0,
+                       grads, (const float *)(ws + w.lpart), grid1, loss_kind == BRIEF_LOSS_EXTERNAL ? 0.f : ma.inv_count, loss_out,
+                       upd ? 1 : 0, o, upd ? upd->params : nullptr, upd ? upd->s1 : nullptr, upd ? upd->s2 : nullptr);
+    HIP_TRY(hipGetLastError());
+    if (upd) {
+        hipLaunchKernelGGL(k_mfn_repack, dim3((unsigned)((lay.total + 255) / 256)), dim3(256), 0, st, *d, (const float *)upd->params, upd->pk);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" {
+
+int64_t brief_mfn_param_count(const brief_mfn_desc *d) { return check_mfn_desc(d) ? -1 : mfn_canon_count(*d); }
+int64_t brief_mfn_packed_count(const brief_mfn_desc *d) { return check_mfn_desc(d) ? -1 : mfn_layout(*d).total; }
+int64_t brief_mfn_train_workspace_bytes(const brief_mfn_desc *d, int64_t n)
+{
+    if (check_mfn_desc(d)) return -1;
+    if (n < 1) { fail(BRIEF_ERR_INVALID, "empty batch"); return -1; }
+    return mfn_ws_layout(*d, n).total * (int64_t)sizeof(float);
+}
+
+int brief_mfn_repack(const brief_mfn_desc *d, const float *params, float *packed, void *stream)
+{
+    if (int rc = check_mfn_desc(d)) return rc;
+    if (!params || !packed) return fail(BRIEF_ERR_INVALID, "null buffer");
+    const int64_t total = mfn_layout(*d).total;
+    hipLaunchKernelGGL(k_mfn_repack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *d, params, packed);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_mfn_forward(const brief_mfn_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                      void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream)
+{
+    if (int rc = check_mfn_desc(d)) return rc;
+    brief_siren_desc sd;
+    memset(&sd, 0, sizeof(sd));
+    sd.cin = d->cin;
+    if (int rc = check_batch(&sd, grid, batch, false)) return rc;
+    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
+    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
+    MfnArgs ma;
+    mfn_forward_args(ma, d, packed, batch->n, out, out_kind, scale_min, scale_max, vmin, vmax);
+    ma.coords = batch->coords; ma.idx = batch->idx; ma.offset = batch->offset;
+    fill_grid(ma.grid, grid);
+    return launch_mfn_fwd<false, false>(ma, mfn_grid(*d, batch->n), (hipStream_t)stream);
+}
+
+int brief_mfn_forward_box(const brief_mfn_desc *d, const float *packed, const brief_grid_box *box, int64_t offset, int64_t n,
+                          void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream)
+{
+    if (int rc = check_mfn_desc(d)) return rc;
+    brief_siren_desc sd;
+    memset(&sd, 0, sizeof(sd));
+    sd.cin = d->cin;
+    int64_t voxels = 0;
+    if (int rc = check_box(&sd, box, &voxels)) return rc;
+    if (n < 1) return fail(BRIEF_ERR_INVALID, "empty batch");
+    if (offset < 0 || offset > voxels - n) return fail(BRIEF_ERR_INVALID, "offset + n exceeds the box's voxel count");
+    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
+    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
+    MfnArgs ma;
+    mfn_forward_args(ma, d, packed, n, out, out_kind, scale_min, scale_max, vmin, vmax);
+    ma.offset = offset;
+    fill_grid(ma.grid, &box->grid);
+    double total = 1.0;
+    for (int a = 0; a < 3; ++a) {
+        const bool on = a < box->grid.ndim;
+        ma.box.start[a] = on ? box->start[a] : 0;
+        ma.box.step[a] = on ? box->step[a] : 1;
+        ma.box.extent[a] = on ? box->extent[a] : 1;
+        ma.box.magic[a] = ~(uint64_t)0 / (uint64_t)ma.box.extent[a] + 1;
+        total *= (double)ma.box.extent[a];
+    }
+    ma.box.fast = total < 4294967296.0;
+    return launch_mfn_fwd<false, true>(ma, mfn_grid(*d, n), (hipStream_t)stream);
+}
+
+int brief_mfn_train_step(const brief_mfn_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                         int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
+                         void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return mfn_train_impl(d, packed, grid, batch, loss_kind, thr, beta, grads, loss_out, yhat_out, workspace, workspace_bytes, stream, nullptr);
+}
+
+int brief_mfn_fit(const brief_mfn_fit_job *j, int64_t steps, void *stream)
+{
+    if (!j) return fail(BRIEF_ERR_INVALID, "null job");
+    if (int rc = check_mfn_desc(&j->desc)) return rc;
+    if (steps < 0) return fail(BRIEF_ERR_INVALID, "bad step count");
+    if (j->batch.idx && j->idx_stride <= 0) return fail(BRIEF_ERR_INVALID, "brief_mfn_fit needs idx_stride > 0 with batch.idx (one index set per step)");
+    if (j->batch.idx && j->idx_stride < j->batch.n) return fail(BRIEF_ERR_INVALID, "idx_stride is smaller than the batch");
+    if (!j->params || !j->packed || !j->grads || !j->loss_out || !j->workspace) return fail(BRIEF_ERR_INVALID, "null buffer");
+    if (j->t0 < 0) return fail(BRIEF_ERR_INVALID, "bad step count");
+    if (j->n_milestones < 0 || (j->n_milestones > 0 && !j->milestones)) return fail(BRIEF_ERR_INVALID, "bad lr milestones");
+    if (j->optim_kind < BRIEF_OPT_ADAMAX || j->optim_kind > BRIEF_OPT_SGD) return fail(BRIEF_ERR_INVALID, "bad optimizer kind");
+    if (j->optim_kind != BRIEF_OPT_SGD && (!j->state1 || !j->state2)) return fail(BRIEF_ERR_INVALID, "optimizer state required");
+    hipStream_t st = (hipStream_t)stream;
+    // the schedule fields mean what they mean in brief_fit_job: brief_siren_fit's rule (fit_job_lr) evaluates them
+    brief_fit_job sched;
+    memset(&sched, 0, sizeof(sched));
+    sched.milestones = j->milestones; sched.n_milestones = j->n_milestones; sched.gamma = j->gamma; sched.t0 = j->t0;
+    sched.lr_table = j->lr_table;
+    double lr = j->lr;
+    for (int64_t k = 0; k < steps; ++k) {
+        const int64_t t = j->t0 + 1 + k;
+        fit_job_lr(&sched, t, k, &lr);
+        brief_batch_desc b = j->batch;
+        if (b.idx) b.idx = b.idx + k * j->idx_stride;
+        else if (b.rng_pop > 0) b.rng_step = (uint64_t)t;
+        FfnUpdate up;
+        up.opt = optim_scalars(j->optim_kind, lr, j->beta1_table ? j->beta1_table[k] : j->beta1, j->beta2, j->eps, t);
+        up.params = j->params; up.s1 = j->state1; up.s2 = j->state2; up.pk = j->packed;
+        if (int rc = mfn_train_impl(&j->desc, j->packed, &j->grid, &b, j->loss_kind, j->thr, j->beta, j->grads,
+                                    j->loss_log ? j->loss_log + k : j->loss_out, nullptr, j->workspace, j->workspace_bytes, (void *)st, &up))
             return rc;
     }
     if (j->loss_log && steps > 0)

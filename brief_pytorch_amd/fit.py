@@ -74,7 +74,7 @@ def cyclic_lr(base_lr, max_lr, step_size_up=2000, step_size_down=None, mode="tri
 
 
 def _is_siren(module):
-    """SIREN runs through brief_siren_fit / brief_multi_fit; every other net kind (FFN, NeRF) names its own fit job type and entry"""
+    """SIREN runs through brief_siren_fit / brief_multi_fit; every other net kind (FFN, NeRF, MFN) names its own fit job type and entry"""
     return getattr(module, "kind", "SIREN") == "SIREN"
 
 
@@ -229,7 +229,7 @@ class MultiFitter:
         self.fitters = list(fitters)
 
     def run(self, steps, log=False):
-        """(brief_multi_fit co-trains SIREN fits only: FFN and NeRF fits run one after another through their own Fitter.run)"""
+        """(brief_multi_fit co-trains SIREN fits only: FFN, NeRF and MFN fits run one after another through their own Fitter.run)"""
         if not all(_is_siren(f.m) for f in self.fitters):
             res, sir = [None] * len(self.fitters), [i for i, f in enumerate(self.fitters) if _is_siren(f.m)]
             if sir:

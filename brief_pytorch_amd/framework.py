@@ -105,9 +105,9 @@ class NFGR:
         precision = self.precision
         feats = int(self.opt.Module.phi.get("features", 0) or 0)
         limit = self.PRECISION_MAX_FEATURES.get(precision)
-        if self.opt.Module.phi.name in ("FFN", "NeRF") and precision != "fp32":
-            # no low-precision FFN / NeRF kernels: the budget keeps the reference's 2 bytes per parameter, the net runs (and is recorded)
-            # in fp32
+        if self.opt.Module.phi.name in ("FFN", "NeRF", "MFNFourier", "MFNGabor") and precision != "fp32":
+            # no low-precision FFN / NeRF / MFN kernels: the budget keeps the reference's 2 bytes per parameter, the net runs (and is
+            # recorded) in fp32
             logging.warning("Compress.precision=%s: %s has fp32 kernels only; this net runs in fp32" % (precision, self.opt.Module.phi.name))
             precision = "fp32"
         elif limit is not None and feats > limit:
@@ -532,7 +532,10 @@ class NFGR:
                 sdst = opj(logdir, "steps{}".format(k), "compressed", "sideinfos", c["name"])
                 os.makedirs(mdst, exist_ok=True)
                 os.makedirs(sdst, exist_ok=True)
-                CopyDir(opj(srcd, "module"), opj(mdst, "module"))
+                if os.path.isfile(opj(srcd, "module")):      # a state_dict artefact (MFN): one torch.save file
+                    shutil.copy(opj(srcd, "module"), opj(mdst, "module"))
+                else:
+                    CopyDir(opj(srcd, "module"), opj(mdst, "module"))
                 shutil.copy(opj(srcd, "sideinfos.yaml"), opj(sdst, "sideinfos.yaml"))
             ctx["fit"] = None
             ctx["phi"] = None

@@ -133,7 +133,10 @@ def minmaxany_range(name):
 
 
 def get_folder_size(folder_path):
-    """utils/io.py get_folder_size: bytes of every file below the folder"""
+    """utils/io.py get_folder_size: bytes of every file below the folder; a path that is a file counts its own size (the reference's
+    second definition returns 0 there, so its compress_ratio/actual of a single-file MFN artefact ignores the net)"""
+    if os.path.isfile(folder_path):
+        return os.path.getsize(folder_path)
     total = 0
     for root, _, files in os.walk(folder_path):
         for f in files:

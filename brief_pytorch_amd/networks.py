@@ -17,7 +17,7 @@ import torch
 
 from . import _lib, region
 
-__all__ = ["SIREN", "FFN", "NeRF", "init_phi", "ALLPHI", "ALL_CALC_PHI_FEATURES", "ALL_CALC_PHI_PARAM_COUNT",
+__all__ = ["SIREN", "FFN", "NeRF", "MFNFourier", "MFNGabor", "init_phi", "ALLPHI", "ALL_CALC_PHI_FEATURES", "ALL_CALC_PHI_PARAM_COUNT",
            "ALL_CHECK_PARAM_COUNT", "get_nnmodule_param_count"]
 
 
@@ -799,6 +799,233 @@ class NeRF(FFN):
         return round((-b + math.sqrt(b ** 2 - 4 * a * c)) / (2 * a))
 
 
+class _MFNBase(FFN):
+    """reference: utils/Networks.py:648-799 (MFNBase + FourierLayer / GaborLayer).  Parameters live in one canonical buffer in
+    state_dict() order [linear.i (W b) | output_linear | per filter: (mu gamma) linear] (include/brief_hip.h, brief_mfn_desc); the whole
+    buffer is trained.  `linear[i]`, `output_linear`, `filters[i].linear` and `filters[i].mu` / `.gamma` are windows into it.  There is
+    no `.net`: ModelSave takes its state_dict branch (one torch.save file), as it does for the reference's MFN.  fp32 kernels only."""
+
+    _fit_job, _fit_entry = _lib.MfnFitJob, "brief_mfn_fit"
+    GABOR = False
+
+    def __init__(self, coords_channel=3, features=256, data_channel=1, layers=5, input_scale=256.0, weight_scale=1.0, bias=True,
+                 output_act=False, device=None, precision="fp32", alpha=6.0, beta=1.0, **kwargs):
+        """the reference's signature and defaults; w0 / res / embsize / frequencies / skip of another net's YAML are ignored, as its
+        **kwargs ignores them.  input_scale, weight_scale, alpha and beta shape the init only."""
+        name = type(self).kind
+        if not bias:
+            raise NotImplementedError("%s(bias=False) is unsupported on the fused path (it changes the state_dict keys and the "
+                                      "reference's budget rule ignores it)" % name)
+        if str(precision) not in ("fp32", "f32"):
+            logging.warning("%s: no %s kernels; the net runs in fp32" % (name, precision))
+        self.coords_channel, self.data_channel = int(coords_channel), int(data_channel)
+        self.features, self.layers = int(features), int(layers)
+        _MFNBase._check(name, self.coords_channel, self.data_channel, self.features, self.layers)
+        self.input_scale, self.weight_scale = float(input_scale), float(weight_scale)
+        self.alpha, self.beta = float(alpha), float(beta)
+        self.precision = "fp32"
+        self.w0, self.output_act = 0.0, bool(output_act)
+        self.desc = _lib.MfnDesc(self.coords_channel, self.data_channel, self.layers, self.features, int(self.GABOR), int(self.output_act))
+        F, cin, cout, L = self.features, self.coords_channel, self.data_channel, self.layers
+        ent = []
+        for i in range(L - 2):
+            ent += [("linear.%d.weight" % i, (F, F)), ("linear.%d.bias" % i, (F,))]
+        ent += [("output_linear.weight", (cout, F)), ("output_linear.bias", (cout,))]
+        for i in range(L - 1):
+            if self.GABOR:
+                ent += [("filters.%d.mu" % i, (F, cin)), ("filters.%d.gamma" % i, (F,))]
+            ent += [("filters.%d.linear.weight" % i, (F, cin)), ("filters.%d.linear.bias" % i, (F,))]
+        self._entries, off = [], 0
+        for k, shp in ent:
+            self._entries.append((k, off, shp))
+            off += int(np.prod(shp))
+        self.bv_count = 0
+        self.param_count = off
+        self.params = self._reference_init()
+        self.grads = None
+        self.packed = None
+        self._stale = True
+        self._seen_version = -1
+        self._autograd = False
+        self._anchor = None
+        self._ws = None
+        self._fws = None
+        self._loss = None
+        views = {k: _ParamView(self, o, shp) for k, o, shp in self._entries}
+        lin = (lambda p: _Window(views[p + ".weight"], views[p + ".bias"]))
+        self.linear = [lin("linear.%d" % i) for i in range(L - 2)]
+        self.output_linear = lin("output_linear")
+        self.filters = [_Filter(lin("filters.%d.linear" % i), views.get("filters.%d.mu" % i), views.get("filters.%d.gamma" % i))
+                        for i in range(L - 1)]
+        if device is not None:
+            self.to(device)
+
+    @staticmethod
+    def _check(name, cin, cout, features, layers):
+        """the limits of include/brief_hip.h (brief_mfn_desc)"""
+        if cin not in (2, 3) or not 1 <= cout <= 4:
+            raise NotImplementedError("%s: coords_channel must be 2 or 3 and data_channel 1..4" % name)
+        if layers < 2:
+            raise NotImplementedError("%s: layers must be >= 2 (got %d)" % (name, layers))
+        if not 1 <= features <= 1024:
+            raise NotImplementedError("%s: features must be 1..1024 on the fused path (got %d)" % (name, features))
+
+    def _reference_init(self):
+        """MFNBase.__init__ then the filters, replayed with torch on the caller's global CPU generator (no reseed): the hidden
+        nn.Linear(F, F) and output_linear default draws, the hidden weights re-drawn as uniform(+-sqrt(weight_scale / F)), then per
+        filter its nn.Linear(cin, F) draws [Gabor: mu = 2 rand(F, cin) - 1, gamma = Gamma(alpha / (L-1), beta).sample((F,))], the
+        weight scaled by input_scale / sqrt(L-1) [* sqrt(gamma)] and the bias re-drawn as uniform(-pi, pi).  The values AND the
+        generator state afterwards equal the reference's."""
+        F, cin, cout, L = self.features, self.coords_channel, self.data_channel, self.layers
+        with torch.no_grad():
+            hidden = [torch.nn.Linear(F, F) for _ in range(L - 2)]
+            head = torch.nn.Linear(F, cout)
+            for lin in hidden:
+                lin.weight.data.uniform_(-np.sqrt(self.weight_scale / F), np.sqrt(self.weight_scale / F))
+            parts = []
+            for lin in hidden:
+                parts += [lin.weight.data.reshape(-1), lin.bias.data]
+            parts += [head.weight.data.reshape(-1), head.bias.data]
+            scale = self.input_scale / np.sqrt(L - 1)
+            for _ in range(L - 1):
+                lin = torch.nn.Linear(cin, F)
+                if self.GABOR:
+                    mu = 2 * torch.rand(F, cin) - 1
+                    gamma = torch.distributions.gamma.Gamma(self.alpha / (L - 1), self.beta).sample((F,))
+                    # torch.sqrt as the reference calls it: its CPU kernel is not correctly rounded everywhere, so these bits follow
+                    # the reference on the same machine (tests/test_gpu_mfn_framework.py)
+                    lin.weight.data *= scale * torch.sqrt(gamma[:, None])
+                    parts += [mu.reshape(-1), gamma]
+                else:
+                    lin.weight.data *= scale
+                lin.bias.data.uniform_(-np.pi, np.pi)
+                parts += [lin.weight.data.reshape(-1), lin.bias.data]
+            return torch.cat([p.to(torch.float32) for p in parts]).contiguous()
+
+    def state_dict(self):
+        """the reference's keys in its order; every value a contiguous CPU float32 tensor with its own storage of exactly its size
+        (torch.save writes the whole storage of a view)"""
+        sd = OrderedDict()
+        for k, o, shp in self._entries:
+            n = int(np.prod(shp))
+            sd[k] = self.params[o:o + n].detach().to("cpu", torch.float32).clone().view(shp)
+        return sd
+
+    def load_state_dict(self, sd):
+        want = [k for k, _, _ in self._entries]
+        if set(sd.keys()) != set(want):
+            missing, extra = [k for k in want if k not in sd], [k for k in sd if k not in want]
+            raise KeyError("%s.load_state_dict: missing keys %s, unexpected keys %s" % (type(self).kind, missing, extra))
+        for k, o, shp in self._entries:
+            v = torch.as_tensor(sd[k], dtype=torch.float32)
+            if tuple(v.shape) != tuple(shp):
+                raise ValueError("%s.load_state_dict: %s has shape %s, expected %s" % (type(self).kind, k, tuple(v.shape), tuple(shp)))
+            self.params[o:o + v.numel()].copy_(v.reshape(-1).to(self.params.device))
+        self._stale = True
+
+    def half(self):
+        """no low-precision MFN kernels: the net stays in fp32 (NFGR keeps the reference's 2-bytes-per-parameter budget and records
+        phi_precision: fp32)"""
+        if not getattr(_MFNBase, "_warned_half", False):
+            _MFNBase._warned_half = True
+            logging.warning("%s.half(): there are no low-precision MFN kernels; the net stays in fp32" % type(self).kind)
+        return self
+
+    # ---- C-ABI entries
+    def _abi_packed_count(self):
+        return _lib.lib().brief_mfn_packed_count(C.byref(self.desc))
+
+    def _abi_repack(self):
+        return _lib.lib().brief_mfn_repack(C.byref(self.desc), _lib.ptr(self.params), _lib.ptr(self.packed), _lib.stream_ptr())
+
+    def _abi_forward(self, grid, batch, out, kind, scale, vrange, n):
+        return _lib.lib().brief_mfn_forward(C.byref(self.desc), _lib.ptr(self.packed), C.byref(grid) if grid is not None else None,
+                                            C.byref(batch), _lib.ptr(out), kind, float(scale[0]), float(scale[1]),
+                                            float(vrange[0]), float(vrange[1]), _lib.stream_ptr())
+
+    def _abi_forward_box(self, box, off, cnt, out, kind, scale, vrange):
+        return _lib.lib().brief_mfn_forward_box(C.byref(self.desc), _lib.ptr(self.packed), C.byref(box), off, cnt, _lib.ptr(out),
+                                                kind, float(scale[0]), float(scale[1]), float(vrange[0]), float(vrange[1]),
+                                                _lib.stream_ptr())
+
+    def _abi_train_ws_bytes(self, n):
+        return _lib.lib().brief_mfn_train_workspace_bytes(C.byref(self.desc), int(n))
+
+    def _abi_train_step(self, g, b, loss_kind, thr, beta, yhat):
+        return _lib.lib().brief_mfn_train_step(
+            C.byref(self.desc), _lib.ptr(self.packed), C.byref(g) if g is not None else None, C.byref(b),
+            loss_kind, float(thr), float(beta), _lib.ptr(self.grads), _lib.ptr(self._loss), _lib.ptr(yhat),
+            _lib.ptr(self._ws), self._ws.numel() * 4, _lib.stream_ptr())
+
+    # ---- budget -> width (utils/Networks.py:721-731, 787-797)
+    FILTER_PARAMS = 1       # per feature and filter: (cin + 1) x FILTER_PARAMS
+
+    @classmethod
+    def _count(cls, coords_channel, data_channel, features, layers):
+        F = features
+        return int((layers - 2) * (F ** 2 + F) + F * data_channel + data_channel + (layers - 1) * cls.FILTER_PARAMS * (coords_channel * F + F))
+
+    @classmethod
+    def _features(cls, param_count, coords_channel, data_channel, layers):
+        """the positive root of (L-2) F^2 + (L-2 + cout + (L-1) k (1 + cin)) F + cout = P, rounded (the reference's formula; the
+        linear case L = 2, where the reference divides by zero, solved directly)"""
+        a = layers - 2
+        b = layers - 2 + data_channel + (layers - 1) * cls.FILTER_PARAMS * (1 + coords_channel)
+        c = -param_count + data_channel
+        if a == 0:
+            return round(-c / b)
+        return round((-b + math.sqrt(b ** 2 - 4 * a * c)) / (2 * a))
+
+
+class MFNFourier(_MFNBase):
+    """reference: utils/Networks.py:667-731 (MFNBase + FourierLayer): g_i = sin(Wf_i x + bf_i)"""
+
+    kind = "MFNFourier"
+    GABOR = False
+    FILTER_PARAMS = 1
+
+    @staticmethod
+    def calc_param_count(coords_channel, data_channel, features, layers, **kwargs):
+        return MFNFourier._count(coords_channel, data_channel, features, layers)
+
+    @staticmethod
+    def calc_features(param_count, coords_channel, data_channel, layers, **kwargs):
+        return MFNFourier._features(param_count, coords_channel, data_channel, layers)
+
+
+class MFNGabor(_MFNBase):
+    """reference: utils/Networks.py:732-797 (MFNBase + GaborLayer): g_i = sin(Wf_i x + bf_i) exp(-gamma_i (|x|^2 + |mu_i|^2 - 2 x.mu_i) / 2)"""
+
+    kind = "MFNGabor"
+    GABOR = True
+    FILTER_PARAMS = 2
+
+    @staticmethod
+    def calc_param_count(coords_channel, data_channel, features, layers, **kwargs):
+        return MFNGabor._count(coords_channel, data_channel, features, layers)
+
+    @staticmethod
+    def calc_features(param_count, coords_channel, data_channel, layers, **kwargs):
+        return MFNGabor._features(param_count, coords_channel, data_channel, layers)
+
+
+class _Window:
+    """stands for an nn.Linear of an MFN: `.weight` / `.bias` are windows into the canonical buffer"""
+
+    def __init__(self, weight, bias):
+        self.weight, self.bias = weight, bias
+        self.out_features, self.in_features = weight.shape[0], weight.shape[1]
+
+
+class _Filter:
+    """stands for FourierLayer / GaborLayer: `.linear`, and for Gabor `.mu` / `.gamma` (windows into the canonical buffer)"""
+
+    def __init__(self, linear, mu=None, gamma=None):
+        self.linear = linear
+        if mu is not None:
+            self.mu, self.gamma = mu, gamma
+
+
 class _PosEncoding:
     """stands for PosEncodingNeRF (no parameters): the encoding runs inside the fused kernels"""
 
@@ -834,23 +1061,28 @@ def get_nnmodule_param_count(module):
     return sum(int(np.prod(p.shape)) for p in module.state_dict().values())
 
 
-# registry with the reference's names (utils/Networks.py:795-802).  SIREN, FFN and NeRF exist on the fused
+# registry with the reference's names (utils/Networks.py:795-802).  SIREN, FFN, NeRF, MFNFourier and MFNGabor exist on the fused
 # path; every other phi.name of the reference raises instead of silently running something else.
-ALLPHI = {"SIREN": SIREN, "FFN": FFN, "NeRF": NeRF}
-ALL_CALC_PHI_FEATURES = {"SIREN": SIREN.calc_features, "FFN": FFN.calc_features, "NeRF": NeRF.calc_features}
-ALL_CALC_PHI_PARAM_COUNT = {"SIREN": SIREN.calc_param_count, "FFN": FFN.calc_param_count, "NeRF": NeRF.calc_param_count}
+ALLPHI = {"SIREN": SIREN, "FFN": FFN, "NeRF": NeRF, "MFNFourier": MFNFourier, "MFNGabor": MFNGabor}
+ALL_CALC_PHI_FEATURES = {"SIREN": SIREN.calc_features, "FFN": FFN.calc_features, "NeRF": NeRF.calc_features,
+                         "MFNFourier": MFNFourier.calc_features, "MFNGabor": MFNGabor.calc_features}
+ALL_CALC_PHI_PARAM_COUNT = {"SIREN": SIREN.calc_param_count, "FFN": FFN.calc_param_count, "NeRF": NeRF.calc_param_count,
+                            "MFNFourier": MFNFourier.calc_param_count, "MFNGabor": MFNGabor.calc_param_count}
 ALL_CHECK_PARAM_COUNT = {}
 # keys a Module.phi spec of this net must name: the reference's NeRF budget rule (calc_features / calc_param_count,
 # utils/Networks.py:118-136) takes frequencies and skip without defaults, so its NFGR cannot build a NeRF from a spec that leaves them
 # out; init_phi refuses such a spec by name instead of filling in the constructor's defaults
-REQUIRED_PHI_KEYS = {"NeRF": ("frequencies", "skip")}
+# (the MFN budget rules, utils/Networks.py:727-731 / 793-797, take coords_channel, data_channel and layers without defaults)
+REQUIRED_PHI_KEYS = {"NeRF": ("frequencies", "skip"), "MFNFourier": ("coords_channel", "data_channel", "layers"),
+                     "MFNGabor": ("coords_channel", "data_channel", "layers")}
 
 
 def init_phi(kwargs):
     kwargs = copy.deepcopy(dict(kwargs))
     name = kwargs.pop("name")
     if name not in ALLPHI:
-        raise NotImplementedError("Module.phi.name=%r is not available on the fused MI355X path (only SIREN, FFN and NeRF)" % name)
+        raise NotImplementedError("Module.phi.name=%r is not available on the fused MI355X path (only SIREN, FFN, NeRF, MFNFourier and "
+                                  "MFNGabor)" % name)
     missing = [k for k in REQUIRED_PHI_KEYS.get(name, ()) if k not in kwargs]
     if missing:
         raise NotImplementedError("Module.phi.name=%r without %s is not supported: the reference's budget rule for this net needs %s "

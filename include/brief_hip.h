@@ -362,6 +362,66 @@ typedef struct brief_nerf_fit_job {
 /* `steps` optimizer steps (train step + reduction + update + repack: four launches each, no host synchronisation) */
 int brief_nerf_fit(const brief_nerf_fit_job *job, int64_t steps, void *stream);
 
+/* ---- MFN: multiplicative filter networks MFNFourier / MFNGabor (Fathony et al.)  utils/Networks.py:648-799 -------------------
+ *   filter i = 0 .. layers-2:  a_i = Wf_i x + bf_i;  g_i = sin(a_i)  (filter 0, Fourier)  or
+ *                              g_i = sin(a_i) exp(-0.5 gamma_i (|x|^2 + |mu_i|^2 - 2 x.mu_i))  (filter 1, Gabor)
+ *   z_0 = g_0,  z_i = g_i . (W_i z_{i-1} + b_i)  (i = 1 .. layers-2),  out = Wo z_{layers-2} + bo,  sin(out) with output_act (no w0)
+ * Limits (anything else: BRIEF_ERR_INVALID with a message naming the limit): fp32 only, cin 2 | 3, cout 1 .. 4, layers >= 2,
+ * features 1 .. 1024 (padded internally to whole 32-wide tiles), filter 0 | 1, output_act 0 | 1; every Linear carries a bias.
+ * Canonical parameter buffer (== torch state_dict() order):
+ *   (W_i [F][F] b_i [F]) x (layers - 2) | Wo [cout][F] bo [cout] | per filter: [mu [F][cin] gamma [F]] (Gabor) Wf [F][cin] bf [F]
+ * The whole buffer is trained (input_scale / weight_scale / alpha / beta of the reference shape the init only). */
+typedef struct {
+    int32_t cin;          /* 2 | 3 */
+    int32_t cout;         /* 1 .. 4 */
+    int32_t layers;       /* >= 2 */
+    int32_t features;     /* 1 .. 1024 */
+    int32_t filter;       /* 0 Fourier | 1 Gabor */
+    int32_t output_act;   /* 0 | 1 */
+} brief_mfn_desc;
+
+/* floats of the canonical buffer (== MFNFourier / MFNGabor.calc_param_count) / of the fragment-ordered copy / train-step scratch bytes */
+int64_t brief_mfn_param_count(const brief_mfn_desc *d);
+int64_t brief_mfn_packed_count(const brief_mfn_desc *d);
+int64_t brief_mfn_train_workspace_bytes(const brief_mfn_desc *d, int64_t n);
+/* canonical params -> fragment-ordered copy (call after every change of params made outside brief_mfn_fit) */
+int brief_mfn_repack(const brief_mfn_desc *d, const float *params, float *packed, void *stream);
+/* MFN forward under no_grad, with the out_kind epilogue of brief_siren_forward (no scratch) */
+int brief_mfn_forward(const brief_mfn_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                      void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream);
+/* the box decode of brief_siren_forward_box (same box rules and refusals) */
+int brief_mfn_forward_box(const brief_mfn_desc *d, const float *packed, const brief_grid_box *box, int64_t offset, int64_t n,
+                          void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream);
+/* forward + loss + backward of one batch, as brief_siren_train_step (grads: canonical layout) */
+int brief_mfn_train_step(const brief_mfn_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                         int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
+                         void *workspace, int64_t workspace_bytes, void *stream);
+/* brief_fit_job with an MFN desc: every field after `desc` means exactly what it means in brief_fit_job
+ * (workspace: brief_mfn_train_workspace_bytes(desc, batch.n)) */
+typedef struct brief_mfn_fit_job {
+    brief_mfn_desc desc;
+    brief_grid_desc grid;
+    brief_batch_desc batch;
+    float *params, *packed;
+    float *state1, *state2;
+    float *grads;
+    float *loss_out;
+    float *loss_log;
+    void *workspace;
+    int64_t workspace_bytes;
+    int32_t loss_kind, optim_kind;
+    float thr, beta;
+    double lr, beta1, beta2, eps;
+    const int64_t *milestones;
+    int32_t n_milestones, reserved;
+    double gamma;
+    int64_t t0;
+    const double *lr_table, *beta1_table;
+    int64_t idx_stride;
+} brief_mfn_fit_job;
+/* `steps` optimizer steps (train step + reduction + update + repack: four launches each, no host synchronisation) */
+int brief_mfn_fit(const brief_mfn_fit_job *job, int64_t steps, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
