@@ -79,6 +79,18 @@ class MfnFitJob(C.Structure):       # brief_mfn_fit_job: brief_fit_job's fields 
     _fields_ = [("desc", MfnDesc)] + FitJob._fields_[1:]
 
 
+TAPER_MAX_LAYERS = 16              # BRIEF_TAPER_MAX_LAYERS
+
+
+class TaperDesc(C.Structure):       # brief_taper_desc
+    _fields_ = [("cin", C.c_int32), ("cout", C.c_int32), ("layers", C.c_int32), ("output_act", C.c_int32),
+                ("widths", C.c_int32 * TAPER_MAX_LAYERS), ("w0", C.c_float * TAPER_MAX_LAYERS)]
+
+
+class TaperFitJob(C.Structure):     # brief_taper_fit_job: brief_fit_job's fields after the desc
+    _fields_ = [("desc", TaperDesc)] + FitJob._fields_[1:]
+
+
 LOSS_KIND = {"datal2": 0, "datasmoothl1": 1, "external": 2}
 OPT_KIND = {"Adamax": 0, "Adam": 1, "SGD": 2}
 OUT_F32, OUT_U8, OUT_U16 = 0, 1, 2
@@ -94,7 +106,9 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_nerf_param_count", "brief_nerf_packed_count", "brief_nerf_train_workspace_bytes", "brief_nerf_repack", "brief_nerf_forward",
            "brief_nerf_forward_box", "brief_nerf_train_step", "brief_nerf_fit",
            "brief_mfn_param_count", "brief_mfn_packed_count", "brief_mfn_train_workspace_bytes", "brief_mfn_repack", "brief_mfn_forward",
-           "brief_mfn_forward_box", "brief_mfn_train_step", "brief_mfn_fit"]
+           "brief_mfn_forward_box", "brief_mfn_train_step", "brief_mfn_fit",
+           "brief_taper_param_count", "brief_taper_packed_count", "brief_taper_train_workspace_bytes", "brief_taper_repack",
+           "brief_taper_forward", "brief_taper_forward_box", "brief_taper_train_step", "brief_taper_fit"]
 
 
 def needs_build():
@@ -210,6 +224,17 @@ def lib():
     L.brief_mfn_forward_box.argtypes = [mp_, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
     L.brief_mfn_train_step.argtypes = [mp_, vp, gp, bp, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, C.c_int64, vp]
     L.brief_mfn_fit.argtypes = [C.POINTER(MfnFitJob), C.c_int64, vp]
+    tp_ = C.POINTER(TaperDesc)
+    for name in ("brief_taper_param_count", "brief_taper_packed_count"):
+        getattr(L, name).restype = C.c_int64
+        getattr(L, name).argtypes = [tp_]
+    L.brief_taper_train_workspace_bytes.restype = C.c_int64
+    L.brief_taper_train_workspace_bytes.argtypes = [tp_, C.c_int64]
+    L.brief_taper_repack.argtypes = [tp_, vp, vp, vp]
+    L.brief_taper_forward.argtypes = [tp_, vp, gp, bp, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
+    L.brief_taper_forward_box.argtypes = [tp_, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
+    L.brief_taper_train_step.argtypes = [tp_, vp, gp, bp, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, C.c_int64, vp]
+    L.brief_taper_fit.argtypes = [C.POINTER(TaperFitJob), C.c_int64, vp]
     _LIB = L
     return L
 

@@ -56,6 +56,7 @@
 #include "brief_ffn.inc"        // FFN: k_ffn_fwd, k_ffn_wgrad, k_ffn_reduce, k_ffn_repack
 #include "brief_nerf.inc"       // NeRF: k_nerf_fwd, k_nerf_wgrad, k_nerf_repack
 #include "brief_mfn.inc"        // MFN: k_mfn_fwd, k_mfn_wgrad, k_mfn_repack
+#include "brief_taper.inc"      // tapered SIRENs: k_taper_fwd, k_taper_wgrad, k_taper_repack
 
 // =============================================================================================
 // C-ABI
@@ -2443,6 +2444,283 @@ int brief_mfn_fit(const brief_mfn_fit_job *j, int64_t steps, void *stream)
         up.params = j->params; up.s1 = j->state1; up.s2 = j->state2; up.pk = j->packed;
         if (int rc = mfn_train_impl(&j->desc, j->packed, &j->grid, &b, j->loss_kind, j->thr, j->beta, j->grads,
                                     j->loss_log ? j->loss_log + k : j->loss_out, nullptr, j->workspace, j->workspace_bytes, (void *)st, &up))
+            return rc;
+    }
+    if (j->loss_log && steps > 0)
+        HIP_TRY(hipMemcpyAsync(j->loss_out, j->loss_log + steps - 1, sizeof(float), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+}   // extern "C"
+
+// =============================================================================================
+// Tapered SIRENs (SIREN_Pyramid, SIRENFT, SIRENPS; brief_taper.inc): train step = k_taper_fwd<TRAIN> + k_taper_wgrad + k_ffn_reduce
+// (bv = 0) (+ k_taper_repack after an update)
+static int check_taper_desc(const brief_taper_desc *d)
+{
+    if (!d) return fail(BRIEF_ERR_INVALID, "null desc");
+    if (d->cin != 2 && d->cin != 3) return fail(BRIEF_ERR_INVALID, "tapered SIREN: coords_channel must be 2 or 3");
+    if (d->cout < 1 || d->cout > 4) return fail(BRIEF_ERR_INVALID, "tapered SIREN: data_channel must be 1..4");
+    if (d->layers < 3 || d->layers > BRIEF_TAPER_MAX_LAYERS) return fail(BRIEF_ERR_INVALID, "tapered SIREN: layers must be 3..16");
+    if (d->output_act != 0 && d->output_act != 1) return fail(BRIEF_ERR_INVALID, "tapered SIREN: output_act must be 0 or 1");
+    for (int l = 0; l < d->layers - 1; ++l)
+        if (d->widths[l] < 1 || d->widths[l] > 1024) return fail(BRIEF_ERR_INVALID, "tapered SIREN: every hidden width must be 1..1024 on the fused path");
+    return 0;
+}
+
+static int taper_lds_bytes(const TaperLayout &l) { return (int)sizeof(float) * (1024 * l.ntmax + 128); }
+// persistent grid: up to two workgroups per CU (one wave per SIMD each), fewer when the LDS image does not fit twice
+static int taper_grid(const TaperLayout &l, int64_t n)
+{
+    const int64_t tiles = (n + 31) / 32;
+    const int by_lds = (160 * 1024) / taper_lds_bytes(l);
+    const int64_t cap = (int64_t)kCUs * (by_lds < 2 ? (by_lds > 0 ? by_lds : 1) : 2);
+    return (int)(tiles < cap ? tiles : cap);
+}
+struct TaperWs { int64_t npad, Z, D, X, G, lpart, slabs, total, chunk; int nsplit, waves; };
+// weight-gradient block of Linear i (0 .. layers - 1) in canonical order; planes at the workspace offsets of w (ws == nullptr: shapes
+// only), wave_begin left to the caller
+static TaperWgradBlock taper_wgrad_block(const TaperLayout &lay, const TaperWs &w, float *ws, int i)
+{
+    const int L = lay.L;
+    const int64_t A = i == L - 1 ? w.G : w.D + (int64_t)lay.row0[i] * w.npad;
+    const int64_t B = i == 0 ? w.X : w.Z + (int64_t)lay.row0[i - 1] * w.npad;
+    TaperWgradBlock b;
+    memset(&b, 0, sizeof(b));
+    b.A = ws ? ws + A : nullptr; b.B = ws ? ws + B : nullptr;
+    b.arows = lay.out[i]; b.brows = lay.in[i];
+    b.mb = (b.arows + 63) / 64; b.nb = (b.brows + 63) / 64;
+    b.bsin = i > 0;
+    b.w_off = lay.canon[i]; b.b_off = lay.canon[i] + (int64_t)lay.out[i] * lay.in[i]; b.ldw = lay.in[i];
+    return b;
+}
+static TaperWs taper_ws_layout(const TaperLayout &lay, int64_t n)
+{
+    TaperWs w;
+    w.npad = (n + 31) / 32 * 32;
+    w.Z = 0;
+    w.D = w.Z + (int64_t)lay.rows * w.npad;
+    w.X = w.D + (int64_t)lay.rows * w.npad;
+    w.G = w.X + 4 * w.npad;
+    w.lpart = w.G + 4 * w.npad;
+    w.slabs = w.lpart + kFfnLossParts;
+    w.waves = 0;
+    for (int i = 0; i < lay.L; ++i) {
+        const TaperWgradBlock b = taper_wgrad_block(lay, w, nullptr, i);
+        w.waves += b.mb * b.nb;
+    }
+    const int64_t wgs = (w.waves + 3) / 4;
+    int64_t ns = (8 * (int64_t)kCUs + wgs - 1) / wgs;      // K-splits: about eight workgroups per CU (as k_ffn_wgrad)
+    if (ns > 64) ns = 64;
+    if (ns > w.npad / 256) ns = w.npad / 256;
+    if (ns < 1) ns = 1;
+    w.chunk = (w.npad / ns + 31) / 32 * 32;
+    w.nsplit = (int)((w.npad + w.chunk - 1) / w.chunk);
+    w.total = w.slabs + (int64_t)w.nsplit * lay.count;
+    return w;
+}
+
+template <bool TRAIN, bool BOX>
+static int launch_taper_fwd(const TaperArgs &ta, int grid, hipStream_t st)
+{
+    const int mtw = (ta.lay.ntmax + 3) / 4;
+    const int lds = taper_lds_bytes(ta.lay);
+    const void *fn = nullptr;
+    switch (mtw) {
+#define TAPER_CASE(M) case M: fn = (const void *)k_taper_fwd<M, TRAIN, BOX>; break;
+        TAPER_CASE(1) TAPER_CASE(2) TAPER_CASE(3) TAPER_CASE(4) TAPER_CASE(5) TAPER_CASE(6) TAPER_CASE(7) TAPER_CASE(8)
+#undef TAPER_CASE
+        default: return fail(BRIEF_ERR_INVALID, "tapered SIREN: every hidden width must be 1..1024 on the fused path");
+    }
+    if (int rc = dev_attr_once(fn, lds)) return rc;
+    switch (mtw) {
+#define TAPER_CASE(M) case M: hipLaunchKernelGGL((k_taper_fwd<M, TRAIN, BOX>), dim3(grid), dim3(256), lds, st, ta); break;
+        TAPER_CASE(1) TAPER_CASE(2) TAPER_CASE(3) TAPER_CASE(4) TAPER_CASE(5) TAPER_CASE(6) TAPER_CASE(7) TAPER_CASE(8)
+#undef TAPER_CASE
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static void taper_forward_args(TaperArgs &ta, const brief_taper_desc *d, const float *packed, int64_t n, void *out, int out_kind,
+                               float scale_min, float scale_max, double vmin, double vmax)
+{
+    memset(&ta, 0, sizeof(ta));
+    ta.d = *d; ta.lay = taper_layout(*d); ta.pk = packed;
+    ta.n = n; ta.npad = (n + 31) / 32 * 32;
+    ta.out = out; ta.out_kind = out_kind;
+    ta.scale_min = scale_min;
+    ta.den = (float)((double)scale_max - (double)scale_min);
+    ta.span = (float)(vmax - vmin);
+    ta.vmin = (float)vmin;
+}
+
+static int taper_train_impl(const brief_taper_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                            int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
+                            void *workspace, int64_t workspace_bytes, void *stream, const FfnUpdate *upd)
+{
+    if (int rc = check_taper_desc(d)) return rc;
+    brief_siren_desc sd;      // check_batch reads cin only
+    memset(&sd, 0, sizeof(sd));
+    sd.cin = d->cin;
+    if (int rc = check_batch(&sd, grid, batch, true)) return rc;
+    if (!packed || !grads || !loss_out || !workspace) return fail(BRIEF_ERR_INVALID, "null buffer");
+    if (loss_kind < BRIEF_LOSS_L2 || loss_kind > BRIEF_LOSS_EXTERNAL) return fail(BRIEF_ERR_INVALID, "bad loss_kind");
+    TaperArgs ta;
+    taper_forward_args(ta, d, packed, batch->n, nullptr, 0, 0.f, 1.f, 0.0, 1.0);
+    const TaperLayout &lay = ta.lay;
+    const TaperWs w = taper_ws_layout(lay, batch->n);
+    if (workspace_bytes < w.total * (int64_t)sizeof(float)) return fail(BRIEF_ERR_WORKSPACE, "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    float *ws = (float *)workspace;
+    ta.coords = batch->coords; ta.targets = batch->targets; ta.weights = batch->weights;
+    ta.idx = batch->idx; ta.offset = batch->offset;
+    if (!batch->idx && batch->rng_pop > 0) { ta.rng_pop = (uint64_t)batch->rng_pop; ta.rng_seed = batch->rng_seed; ta.rng_step = batch->rng_step; }
+    fill_grid(ta.grid, grid);
+    ta.loss_kind = loss_kind; ta.thr = thr; ta.beta = beta;
+    ta.inv_count = (float)(1.0 / ((double)batch->n * d->cout));
+    ta.Z = ws + w.Z; ta.D = ws + w.D; ta.X = ws + w.X; ta.G = ws + w.G; ta.lpart = ws + w.lpart;
+    ta.npad = w.npad; ta.yhat_out = yhat_out;
+    const int grid1 = taper_grid(lay, batch->n);
+    const bool prof = prof_live();
+    hipEvent_t *pev = prof ? dev_state()->prof_ev : nullptr;
+    if (prof) HIP_TRY(hipEventRecord(pev[2 * g_prof_n], st));
+    if (int rc = launch_taper_fwd<true, false>(ta, grid1, st)) return rc;
+    if (prof) { HIP_TRY(hipEventRecord(pev[2 * g_prof_n + 1], st)); ++g_prof_n; }
+    // weight gradients: one rectangular block per Linear, all in one launch (layers <= BRIEF_TAPER_MAX_LAYERS)
+    const int64_t mlp = lay.count;
+    TaperWgradArgs wa;
+    memset(&wa, 0, sizeof(wa));
+    wa.npad = w.npad; wa.chunk = w.chunk; wa.mlp = mlp; wa.slabs = ws + w.slabs;
+    wa.nblocks = lay.L;
+    int waves = 0;
+    for (int i = 0; i < wa.nblocks; ++i) {
+        wa.blk[i] = taper_wgrad_block(lay, w, ws, i);
+        wa.blk[i].wave_begin = waves;
+        waves += wa.blk[i].mb * wa.blk[i].nb;
+    }
+    wa.waves = waves;
+    hipLaunchKernelGGL(k_taper_wgrad, dim3((unsigned)((waves + 3) / 4), (unsigned)w.nsplit), dim3(256), 0, st, wa);
+    HIP_TRY(hipGetLastError());
+    OptimScalars o;
+    memset(&o, 0, sizeof(o));
+    if (upd) o = upd->opt;
+    hipLaunchKernelGGL(k_ffn_reduce, dim3((unsigned)((mlp + 255) / 256)), dim3(256), 0, st, (const float *)(ws + w.slabs), w.nsplit, mlp, (int64_t)0,
+                       grads, (const float *)(ws + w.lpart), grid1, loss_kind == BRIEF_LOSS_EXTERNAL ? 0.f : ta.inv_count, loss_out,
+                       upd ? 1 : 0, o, upd ? upd->params : nullptr, upd ? upd->s1 : nullptr, upd ? upd->s2 : nullptr);
+    HIP_TRY(hipGetLastError());
+    if (upd) {
+        hipLaunchKernelGGL(k_taper_repack, dim3((unsigned)((lay.total + 255) / 256)), dim3(256), 0, st, *d, lay, (const float *)upd->params, upd->pk);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" {
+
+int64_t brief_taper_param_count(const brief_taper_desc *d) { return check_taper_desc(d) ? -1 : taper_layout(*d).count; }
+int64_t brief_taper_packed_count(const brief_taper_desc *d) { return check_taper_desc(d) ? -1 : taper_layout(*d).total; }
+int64_t brief_taper_train_workspace_bytes(const brief_taper_desc *d, int64_t n)
+{
+    if (check_taper_desc(d)) return -1;
+    if (n < 1) { fail(BRIEF_ERR_INVALID, "empty batch"); return -1; }
+    return taper_ws_layout(taper_layout(*d), n).total * (int64_t)sizeof(float);
+}
+
+int brief_taper_repack(const brief_taper_desc *d, const float *params, float *packed, void *stream)
+{
+    if (int rc = check_taper_desc(d)) return rc;
+    if (!params || !packed) return fail(BRIEF_ERR_INVALID, "null buffer");
+    const TaperLayout lay = taper_layout(*d);
+    hipLaunchKernelGGL(k_taper_repack, dim3((unsigned)((lay.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *d, lay, params, packed);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_taper_forward(const brief_taper_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                        void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream)
+{
+    if (int rc = check_taper_desc(d)) return rc;
+    brief_siren_desc sd;
+    memset(&sd, 0, sizeof(sd));
+    sd.cin = d->cin;
+    if (int rc = check_batch(&sd, grid, batch, false)) return rc;
+    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
+    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
+    TaperArgs ta;
+    taper_forward_args(ta, d, packed, batch->n, out, out_kind, scale_min, scale_max, vmin, vmax);
+    ta.coords = batch->coords; ta.idx = batch->idx; ta.offset = batch->offset;
+    fill_grid(ta.grid, grid);
+    return launch_taper_fwd<false, false>(ta, taper_grid(ta.lay, batch->n), (hipStream_t)stream);
+}
+
+int brief_taper_forward_box(const brief_taper_desc *d, const float *packed, const brief_grid_box *box, int64_t offset, int64_t n,
+                            void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream)
+{
+    if (int rc = check_taper_desc(d)) return rc;
+    brief_siren_desc sd;
+    memset(&sd, 0, sizeof(sd));
+    sd.cin = d->cin;
+    int64_t voxels = 0;
+    if (int rc = check_box(&sd, box, &voxels)) return rc;
+    if (n < 1) return fail(BRIEF_ERR_INVALID, "empty batch");
+    if (offset < 0 || offset > voxels - n) return fail(BRIEF_ERR_INVALID, "offset + n exceeds the box's voxel count");
+    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
+    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
+    TaperArgs ta;
+    taper_forward_args(ta, d, packed, n, out, out_kind, scale_min, scale_max, vmin, vmax);
+    ta.offset = offset;
+    fill_grid(ta.grid, &box->grid);
+    double total = 1.0;
+    for (int a = 0; a < 3; ++a) {
+        const bool on = a < box->grid.ndim;
+        ta.box.start[a] = on ? box->start[a] : 0;
+        ta.box.step[a] = on ? box->step[a] : 1;
+        ta.box.extent[a] = on ? box->extent[a] : 1;
+        ta.box.magic[a] = ~(uint64_t)0 / (uint64_t)ta.box.extent[a] + 1;
+        total *= (double)ta.box.extent[a];
+    }
+    ta.box.fast = total < 4294967296.0;
+    return launch_taper_fwd<false, true>(ta, taper_grid(ta.lay, n), (hipStream_t)stream);
+}
+
+int brief_taper_train_step(const brief_taper_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                           int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
+                           void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return taper_train_impl(d, packed, grid, batch, loss_kind, thr, beta, grads, loss_out, yhat_out, workspace, workspace_bytes, stream, nullptr);
+}
+
+int brief_taper_fit(const brief_taper_fit_job *j, int64_t steps, void *stream)
+{
+    if (!j) return fail(BRIEF_ERR_INVALID, "null job");
+    if (int rc = check_taper_desc(&j->desc)) return rc;
+    if (steps < 0) return fail(BRIEF_ERR_INVALID, "bad step count");
+    if (j->batch.idx && j->idx_stride <= 0) return fail(BRIEF_ERR_INVALID, "brief_taper_fit needs idx_stride > 0 with batch.idx (one index set per step)");
+    if (j->batch.idx && j->idx_stride < j->batch.n) return fail(BRIEF_ERR_INVALID, "idx_stride is smaller than the batch");
+    if (!j->params || !j->packed || !j->grads || !j->loss_out || !j->workspace) return fail(BRIEF_ERR_INVALID, "null buffer");
+    if (j->t0 < 0) return fail(BRIEF_ERR_INVALID, "bad step count");
+    if (j->n_milestones < 0 || (j->n_milestones > 0 && !j->milestones)) return fail(BRIEF_ERR_INVALID, "bad lr milestones");
+    if (j->optim_kind < BRIEF_OPT_ADAMAX || j->optim_kind > BRIEF_OPT_SGD) return fail(BRIEF_ERR_INVALID, "bad optimizer kind");
+    if (j->optim_kind != BRIEF_OPT_SGD && (!j->state1 || !j->state2)) return fail(BRIEF_ERR_INVALID, "optimizer state required");
+    hipStream_t st = (hipStream_t)stream;
+    // the schedule fields mean what they mean in brief_fit_job: brief_siren_fit's rule (fit_job_lr) evaluates them
+    brief_fit_job sched;
+    memset(&sched, 0, sizeof(sched));
+    sched.milestones = j->milestones; sched.n_milestones = j->n_milestones; sched.gamma = j->gamma; sched.t0 = j->t0;
+    sched.lr_table = j->lr_table;
+    double lr = j->lr;
+    for (int64_t k = 0; k < steps; ++k) {
+        const int64_t t = j->t0 + 1 + k;
+        fit_job_lr(&sched, t, k, &lr);
+        brief_batch_desc b = j->batch;
+        if (b.idx) b.idx = b.idx + k * j->idx_stride;
+        else if (b.rng_pop > 0) b.rng_step = (uint64_t)t;
+        FfnUpdate up;
+        up.opt = optim_scalars(j->optim_kind, lr, j->beta1_table ? j->beta1_table[k] : j->beta1, j->beta2, j->eps, t);
+        up.params = j->params; up.s1 = j->state1; up.s2 = j->state2; up.pk = j->packed;
+        if (int rc = taper_train_impl(&j->desc, j->packed, &j->grid, &b, j->loss_kind, j->thr, j->beta, j->grads,
+                                      j->loss_log ? j->loss_log + k : j->loss_out, nullptr, j->workspace, j->workspace_bytes, (void *)st, &up))
             return rc;
     }
     if (j->loss_log && steps > 0)

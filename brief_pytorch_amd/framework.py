@@ -27,7 +27,7 @@ from .metrics import cal_ssim, eval_performance, gpu_eval_u16, gpu_ssim_u16, psn
 from .misc import (alloc_param, cal_divide_num, divide_data, merge_divided_data, mip_ops, save_mips, parse_checkpoints,
                    parse_chunk_name, parse_weight, preprocess, preprocess_is_identity, weight_is_unit)
 from .modelsave import CopyDir, load_model, save_model
-from .networks import (ALL_CALC_PHI_FEATURES, ALL_CALC_PHI_PARAM_COUNT, get_nnmodule_param_count, init_phi)
+from .networks import (ALL_CALC_PHI_FEATURES, ALL_CALC_PHI_PARAM_COUNT, ALL_CHECK_PARAM_COUNT, get_nnmodule_param_count, init_phi)
 from .tool import create_stack, read_img, save_img, write_slab
 
 
@@ -105,8 +105,8 @@ class NFGR:
         precision = self.precision
         feats = int(self.opt.Module.phi.get("features", 0) or 0)
         limit = self.PRECISION_MAX_FEATURES.get(precision)
-        if self.opt.Module.phi.name in ("FFN", "NeRF", "MFNFourier", "MFNGabor") and precision != "fp32":
-            # no low-precision FFN / NeRF / MFN kernels: the budget keeps the reference's 2 bytes per parameter, the net runs (and is
+        if self.opt.Module.phi.name in ("FFN", "NeRF", "MFNFourier", "MFNGabor", "SIREN_Pyramid", "SIRENFT", "SIRENPS") and precision != "fp32":
+            # no low-precision FFN / NeRF / MFN / tapered-SIREN kernels: the budget keeps the reference's 2 bytes per parameter, the net runs (and is
             # recorded) in fp32
             logging.warning("Compress.precision=%s: %s has fp32 kernels only; this net runs in fp32" % (precision, self.opt.Module.phi.name))
             precision = "fp32"
@@ -121,11 +121,35 @@ class NFGR:
         self.module["phi"] = init_phi({**dict(self.opt.Module.phi), "precision": precision})
 
     @staticmethod
+    def _under_floor(opt, name, ideal):
+        """main.py:222-234: is the budget below the floor of net `name` (its check_param_count with the spec's own keys)?"""
+        kw = {k: v for k, v in opt.Module.phi.items() if k != "name"}
+        try:
+            return not ALL_CHECK_PARAM_COUNT[name](param_count=ideal, **kw)
+        except TypeError:
+            # the reference dies here with "check_param_count() missing ... 'ratio'": a SIREN_Pyramid spec needs `ratio` for its fallback
+            need = "features_dis" if name == "SIREN_Pyramid" else "ratio"
+            missing = [k for k in ("coords_channel", "data_channel", "layers", "res", need) if k not in kw]
+            raise TypeError("Module.phi: the budget floor of %s needs %s in the spec (missing: %s)%s" % (
+                name, need, ", ".join(missing) or "?",
+                "; a SIREN_Pyramid whose budget is under its floor falls back to SIRENFT, which takes `ratio`" if need == "ratio" else "")) from None
+
+    @staticmethod
     def estimate_module_size(ideal_module_size, opt):
-        name = opt.Module.phi.name
-        if name not in ALL_CALC_PHI_FEATURES:
-            raise NotImplementedError("Module.phi.name=%r" % name)
+        """main.py:214-246.  The tapered SIRENs have a budget floor: under it SIREN_Pyramid becomes SIRENFT (features_plus = features_dis),
+        SIRENFT and SIRENPS become SIREN.  The name is changed IN THE OPTIONS, as the reference does, so that everything downstream
+        (init_module, the DivideTask cost model, sideinfos phi_name) sees the net that is really built."""
+        if opt.Module.phi.name not in ALL_CALC_PHI_FEATURES:
+            raise NotImplementedError("Module.phi.name=%r" % opt.Module.phi.name)
         ideal = ideal_module_size / (2.0 if opt.Compress.half else 4.0)
+        if opt.Module.phi.name == "SIREN_Pyramid" and NFGR._under_floor(opt, "SIREN_Pyramid", ideal):
+            opt.Module.phi.name = "SIRENFT"
+            opt.Module.phi.features_plus = opt.Module.phi.features_dis
+        if opt.Module.phi.name == "SIRENFT" and NFGR._under_floor(opt, "SIRENFT", ideal):
+            opt.Module.phi.name = "SIREN"
+        if opt.Module.phi.name == "SIRENPS" and NFGR._under_floor(opt, "SIRENPS", ideal):
+            opt.Module.phi.name = "SIREN"
+        name = opt.Module.phi.name
         feats = ALL_CALC_PHI_FEATURES[name](param_count=ideal, **{k: v for k, v in opt.Module.phi.items() if k != "name"})
         kw = {k: v for k, v in opt.Module.phi.items() if k not in ("name", "features")}
         actual = ALL_CALC_PHI_PARAM_COUNT[name](features=feats, **kw)

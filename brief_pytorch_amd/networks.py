@@ -17,7 +17,7 @@ import torch
 
 from . import _lib, region
 
-__all__ = ["SIREN", "FFN", "NeRF", "MFNFourier", "MFNGabor", "init_phi", "ALLPHI", "ALL_CALC_PHI_FEATURES", "ALL_CALC_PHI_PARAM_COUNT",
+__all__ = ["SIREN", "FFN", "NeRF", "MFNFourier", "MFNGabor", "SIREN_Pyramid", "SIRENFT", "SIRENPS", "init_phi", "ALLPHI", "ALL_CALC_PHI_FEATURES", "ALL_CALC_PHI_PARAM_COUNT",
            "ALL_CHECK_PARAM_COUNT", "get_nnmodule_param_count"]
 
 
@@ -1009,6 +1009,279 @@ class MFNGabor(_MFNBase):
         return MFNGabor._features(param_count, coords_channel, data_channel, layers)
 
 
+class _TaperBase(FFN):
+    """the tapered SIRENs of the reference (utils/Networks.py:316-552): a SIREN whose every Linear has its own width and every sine its
+    own w0.  Parameters live in one canonical buffer in state_dict() order (W_l b_l per Linear); `.net[l][0].weight / .bias`, the
+    state_dict keys, the init replay and the raw weight-l-out-in / bias-l-n artefact are SIREN's.  The subclasses give the widths and the
+    budget rules.  fp32 kernels only (include/brief_hip.h, brief_taper_desc)."""
+
+    _fit_job, _fit_entry = _lib.TaperFitJob, "brief_taper_fit"
+    MAX_LAYERS, MAX_WIDTH = _lib.TAPER_MAX_LAYERS, 1024
+
+    def _setup(self, coords_channel, data_channel, features, layers, w0, res, output_act, device, precision, widths, w0s):
+        name = type(self).kind
+        _TaperBase._no_res(name, res)
+        if str(precision) not in ("fp32", "f32"):
+            logging.warning("%s: no %s kernels; the net runs in fp32" % (name, precision))
+        self.coords_channel, self.data_channel = int(coords_channel), int(data_channel)
+        self.features, self.layers = features, int(layers)       # features: as given (a float for SIRENFT / SIRENPS, truncated per layer)
+        self.widths = [int(v) for v in widths]
+        _TaperBase._check(name, self.coords_channel, self.data_channel, self.layers, self.widths)
+        self.precision = "fp32"
+        self.w0, self.output_act = float(w0), bool(output_act)
+        self.w0s = [float(v) for v in w0s] + [30.0]               # the sine behind every Linear (the last: the output activation, Sine())
+        wd = (C.c_int32 * self.MAX_LAYERS)(*self.widths)
+        ww = (C.c_float * self.MAX_LAYERS)(*self.w0s)
+        self.desc = _lib.TaperDesc(self.coords_channel, self.data_channel, self.layers, int(self.output_act), wd, ww)
+        ins = [self.coords_channel] + self.widths
+        outs = self.widths + [self.data_channel]
+        self._shapes = list(zip(outs, ins))
+        self.bv_count = 0
+        self.param_count = sum(o * i + o for o, i in self._shapes)
+        self.params = SIREN._reference_init(self)
+        self.grads = None
+        self.packed = None
+        self._stale = True
+        self._seen_version = -1
+        self._autograd = False
+        self._anchor = None
+        self._ws = None
+        self._fws = None
+        self._loss = None
+        net, off = [], 0
+        for (o, i) in self._shapes:
+            net.append(_Seq(_Linear(self, off, (o, i), off + o * i)))
+            off += o * i + o
+        self.net = net
+        if device is not None:
+            self.to(device)
+
+    @staticmethod
+    def _no_res(name, res):
+        if res:
+            # HalfResidual blocks cannot be saved by the reference's own ModelSave (as for SIREN)
+            raise NotImplementedError("%s(res=True) is unsupported on the fused path" % name)
+
+    @staticmethod
+    def _check_layers(name, layers):
+        if not 3 <= layers <= _TaperBase.MAX_LAYERS:
+            raise NotImplementedError("%s: layers must be 3..%d (got %d); the reference's own rules divide by zero or miscount at layers = 2"
+                                      % (name, _TaperBase.MAX_LAYERS, layers))
+
+    @staticmethod
+    def _check(name, cin, cout, layers, widths):
+        """the limits of include/brief_hip.h (brief_taper_desc)"""
+        if cin not in (2, 3) or not 1 <= cout <= 4:
+            raise NotImplementedError("%s: coords_channel must be 2 or 3 and data_channel 1..4" % name)
+        _TaperBase._check_layers(name, layers)
+        if min(widths) < 1:
+            raise ValueError("%s: a layer of width %d (layer widths %s): every hidden width must be >= 1" % (name, min(widths), widths))
+        if max(widths) > _TaperBase.MAX_WIDTH:
+            raise NotImplementedError("%s: every hidden width must be 1..1024 on the fused path (layer widths %s)" % (name, widths))
+
+    def _reference_init(self):
+        return SIREN._reference_init(self)
+
+    def state_dict(self):
+        return SIREN.state_dict(self)
+
+    def load_state_dict(self, sd):
+        SIREN.load_state_dict(self, sd)
+
+    def half(self):
+        """no low-precision kernels for the tapered nets: the net stays in fp32 (NFGR keeps the reference's 2-bytes-per-parameter budget
+        and records phi_precision: fp32)"""
+        if not getattr(_TaperBase, "_warned_half", False):
+            _TaperBase._warned_half = True
+            logging.warning("%s.half(): there are no low-precision kernels for the tapered SIRENs; the net stays in fp32" % type(self).kind)
+        return self
+
+    # ---- C-ABI entries
+    def _abi_packed_count(self):
+        return _lib.lib().brief_taper_packed_count(C.byref(self.desc))
+
+    def _abi_repack(self):
+        return _lib.lib().brief_taper_repack(C.byref(self.desc), _lib.ptr(self.params), _lib.ptr(self.packed), _lib.stream_ptr())
+
+    def _abi_forward(self, grid, batch, out, kind, scale, vrange, n):
+        return _lib.lib().brief_taper_forward(C.byref(self.desc), _lib.ptr(self.packed), C.byref(grid) if grid is not None else None,
+                                              C.byref(batch), _lib.ptr(out), kind, float(scale[0]), float(scale[1]),
+                                              float(vrange[0]), float(vrange[1]), _lib.stream_ptr())
+
+    def _abi_forward_box(self, box, off, cnt, out, kind, scale, vrange):
+        return _lib.lib().brief_taper_forward_box(C.byref(self.desc), _lib.ptr(self.packed), C.byref(box), off, cnt, _lib.ptr(out),
+                                                  kind, float(scale[0]), float(scale[1]), float(vrange[0]), float(vrange[1]),
+                                                  _lib.stream_ptr())
+
+    def _abi_train_ws_bytes(self, n):
+        return _lib.lib().brief_taper_train_workspace_bytes(C.byref(self.desc), int(n))
+
+    def _abi_train_step(self, g, b, loss_kind, thr, beta, yhat):
+        return _lib.lib().brief_taper_train_step(
+            C.byref(self.desc), _lib.ptr(self.packed), C.byref(g) if g is not None else None, C.byref(b),
+            loss_kind, float(thr), float(beta), _lib.ptr(self.grads), _lib.ptr(self._loss), _lib.ptr(yhat),
+            _lib.ptr(self._ws), self._ws.numel() * 4, _lib.stream_ptr())
+
+    @staticmethod
+    def _count(cin, cout, widths):
+        ins, outs = [cin] + list(widths), list(widths) + [cout]
+        return sum(o * i + o for o, i in zip(outs, ins))
+
+
+class SIREN_Pyramid(_TaperBase):
+    """reference: utils/Networks.py:370-457.  Hidden widths F, F - d, ..., F - (layers - 2) d (d = features_dis; negative d grows)."""
+
+    kind = "SIREN_Pyramid"
+
+    def __init__(self, coords_channel=3, data_channel=1, features=256, layers=5, w0=30, res=False, output_act=False, features_dis=10,
+                 device=None, precision="fp32", **kwargs):
+        _TaperBase._no_res(self.kind, res)
+        _TaperBase._check_layers(self.kind, int(layers))
+        if int(features) != features or int(features_dis) != features_dis:
+            raise ValueError("SIREN_Pyramid: features and features_dis must be integers (got %r, %r)" % (features, features_dis))
+        self.features_dis = int(features_dis)
+        widths = SIREN_Pyramid.layer_widths(int(features), int(layers), self.features_dis)
+        self._setup(coords_channel, data_channel, int(features), layers, w0, res, output_act, device, precision,
+                    widths, [w0] + [30.0] * (int(layers) - 2))
+
+    @staticmethod
+    def layer_widths(features, layers, features_dis):
+        return [features - i * features_dis for i in range(layers - 1)]
+
+    @staticmethod
+    def calc_param_count(coords_channel, data_channel, features, layers, res, features_dis, **kwargs):
+        _TaperBase._no_res("SIREN_Pyramid", res)
+        return int(_TaperBase._count(coords_channel, data_channel, SIREN_Pyramid.layer_widths(features, layers, features_dis)))
+
+    @staticmethod
+    def check_param_count(param_count, coords_channel, data_channel, layers, res, features_dis, **kwargs):
+        """the budget floor: the pyramid whose last hidden layer has width 1"""
+        _TaperBase._no_res("SIREN_Pyramid", res)
+        floor = _TaperBase._count(coords_channel, data_channel, SIREN_Pyramid.layer_widths(1 + (layers - 2) * features_dis, layers, features_dis))
+        return bool(param_count >= floor)
+
+    @staticmethod
+    def calc_features(param_count, coords_channel, data_channel, layers, res, features_dis, **kwargs):
+        """the positive root of the reference's quadratic in F (the widths' products summed in closed form), rounded; ValueError when
+        the last hidden layer would have width <= 0 (as the reference)"""
+        _TaperBase._no_res("SIREN_Pyramid", res)
+        _TaperBase._check_layers("SIREN_Pyramid", layers)
+        l, c, d, o = layers, coords_channel, features_dis, data_channel
+        a = l - 2
+        b = c + 1 + (1 - d) * (l - 2) - (l - 2) * (l - 3) * d + o
+        cc = ((l - 2) * (1 - d) ** 2 / 4 - (l - 2) * (l - 3) * d + (l - 2) * (l - 3) * (2 * l - 5) * d ** 2 / 6 - (l - 2) * (1 + d) ** 2 / 4
+              - (l - 2) * d * o + o - param_count)
+        features = round((-b + math.sqrt(b ** 2 - 4 * a * cc)) / (2 * a))
+        if features - (l - 2) * d <= 0 or features <= 0:
+            raise ValueError("SIREN_Pyramid: the budget of %s parameters gives features=%d, a last hidden width of %d" % (param_count, features, features - (l - 2) * d))
+        return features
+
+
+class SIRENFT(_TaperBase):
+    """reference: utils/Networks.py:316-369.  Hidden widths int(F ratio), int(F), ..., int(F); the sines behind Linear 0 AND Linear 1
+    carry w0 (the reference's :324), the others 30."""
+
+    kind = "SIRENFT"
+
+    def __init__(self, coords_channel=3, data_channel=1, features=256, layers=5, w0=30, res=False, output_act=False, ratio=1,
+                 device=None, precision="fp32", **kwargs):
+        _TaperBase._no_res(self.kind, res)
+        _TaperBase._check_layers(self.kind, int(layers))
+        self.ratio = ratio
+        widths = SIRENFT.layer_widths(features, int(layers), ratio)
+        self._setup(coords_channel, data_channel, features, layers, w0, res, output_act, device, precision,
+                    widths, [w0, w0] + [30.0] * (int(layers) - 3))
+
+    @staticmethod
+    def layer_widths(features, layers, ratio):
+        return [int(features * ratio)] + [int(features)] * (layers - 2)
+
+    @staticmethod
+    def calc_param_count(coords_channel, data_channel, features, layers, res, ratio, **kwargs):
+        _TaperBase._no_res("SIRENFT", res)
+        return int(_TaperBase._count(coords_channel, data_channel, SIRENFT.layer_widths(features, layers, ratio)))
+
+    @staticmethod
+    def check_param_count(param_count, coords_channel, data_channel, layers, res, ratio, **kwargs):
+        """the budget floor: features = 1"""
+        _TaperBase._no_res("SIRENFT", res)
+        return bool(param_count >= _TaperBase._count(coords_channel, data_channel, SIRENFT.layer_widths(1, layers, ratio)))
+
+    @staticmethod
+    def calc_features(param_count, coords_channel, data_channel, layers, res, ratio, **kwargs):
+        """the positive root of (r + L - 3) F^2 + (cin r + r + 1 + L - 3 + cout) F + cout = P as a FLOAT (the reference does not round:
+        the constructor truncates F and F r)"""
+        _TaperBase._no_res("SIRENFT", res)
+        _TaperBase._check_layers("SIRENFT", layers)
+        a = ratio + layers - 3
+        b = coords_channel * ratio + ratio + 1 + layers - 3 + data_channel
+        c = data_channel - param_count
+        features = (-b + math.sqrt(b ** 2 - 4 * a * c)) / (2 * a)
+        if min(SIRENFT.layer_widths(features, layers, ratio)) < 1:
+            raise ValueError("SIRENFT: the budget of %s parameters gives features=%s, a layer of width 0" % (param_count, features))
+        return features
+
+
+class SIRENPS(_TaperBase):
+    """reference: utils/Networks.py:458-552.  Hidden widths int(F r^(L-2)), int(F r^(L-3)), ..., int(F r), int(F) (a geometric taper)."""
+
+    kind = "SIRENPS"
+
+    def __init__(self, coords_channel=3, data_channel=1, features=256, layers=5, w0=30, res=False, output_act=False, ratio=1,
+                 device=None, precision="fp32", **kwargs):
+        _TaperBase._no_res(self.kind, res)
+        _TaperBase._check_layers(self.kind, int(layers))
+        SIRENPS._no_unit_ratio(ratio)
+        self.ratio = ratio
+        widths = SIRENPS.layer_widths(features, int(layers), ratio)
+        self._setup(coords_channel, data_channel, features, layers, w0, res, output_act, device, precision,
+                    widths, [w0] + [30.0] * (int(layers) - 2))
+
+    @staticmethod
+    def _no_unit_ratio(ratio):
+        if ratio == 1:
+            raise ValueError("SIRENPS(ratio=1) is refused: the reference's budget rule divides by zero at ratio == 1 (use SIREN)")
+
+    @staticmethod
+    def layer_widths(features, layers, ratio):
+        return [int(features * ratio ** (layers - 2 - i)) for i in range(layers - 1)]
+
+    @staticmethod
+    def calc_param_count(coords_channel, data_channel, features, layers, res, ratio, **kwargs):
+        """the reference's count: the head is counted with the FLOAT width (features * data_channel), so with data_channel > 1 it can
+        exceed the module's own count by 1-2"""
+        _TaperBase._no_res("SIRENPS", res)
+        w = SIRENPS.layer_widths(features, layers, ratio)
+        count = _TaperBase._count(coords_channel, data_channel, w) - w[-1] * data_channel + features * data_channel
+        return int(count)
+
+    @staticmethod
+    def check_param_count(param_count, coords_channel, data_channel, layers, res, ratio, **kwargs):
+        """the budget floor: features = 1"""
+        _TaperBase._no_res("SIRENPS", res)
+        return bool(param_count >= SIRENPS.calc_param_count(coords_channel, data_channel, 1, layers, res, ratio))
+
+    @staticmethod
+    def calc_features(param_count, coords_channel, data_channel, layers, res, ratio, **kwargs):
+        """the positive root of the geometric sums in F as a FLOAT (not rounded), with the reference's own identity check (< 1 parameter)"""
+        _TaperBase._no_res("SIRENPS", res)
+        _TaperBase._check_layers("SIRENPS", layers)
+        SIRENPS._no_unit_ratio(ratio)
+        l, c, o, r = layers, coords_channel, data_channel, ratio
+        a = r * (1 - (r ** 2) ** (l - 2)) / (1 - r ** 2)
+        b = (1 - r ** (l - 2)) / (1 - r) + (c + 1) * r ** (l - 2) + o
+        cc = o - param_count
+        features = (-b + math.sqrt(b ** 2 - 4 * a * cc)) / (2 * a)
+        if features <= 0:
+            raise ValueError("SIRENPS: the budget of %s parameters gives features=%s" % (param_count, features))
+        w = [features * r ** (l - 2 - i) for i in range(l - 1)]
+        ident = _TaperBase._count(c, o, w)
+        assert abs(param_count - ident) < 1, "ERROR!"
+        if min(SIRENPS.layer_widths(features, layers, ratio)) < 1:
+            raise ValueError("SIRENPS: the budget of %s parameters gives features=%s, a layer of width 0" % (param_count, features))
+        return features
+
+
 class _Window:
     """stands for an nn.Linear of an MFN: `.weight` / `.bias` are windows into the canonical buffer"""
 
@@ -1061,28 +1334,33 @@ def get_nnmodule_param_count(module):
     return sum(int(np.prod(p.shape)) for p in module.state_dict().values())
 
 
-# registry with the reference's names (utils/Networks.py:795-802).  SIREN, FFN, NeRF, MFNFourier and MFNGabor exist on the fused
-# path; every other phi.name of the reference raises instead of silently running something else.
-ALLPHI = {"SIREN": SIREN, "FFN": FFN, "NeRF": NeRF, "MFNFourier": MFNFourier, "MFNGabor": MFNGabor}
-ALL_CALC_PHI_FEATURES = {"SIREN": SIREN.calc_features, "FFN": FFN.calc_features, "NeRF": NeRF.calc_features,
-                         "MFNFourier": MFNFourier.calc_features, "MFNGabor": MFNGabor.calc_features}
-ALL_CALC_PHI_PARAM_COUNT = {"SIREN": SIREN.calc_param_count, "FFN": FFN.calc_param_count, "NeRF": NeRF.calc_param_count,
-                            "MFNFourier": MFNFourier.calc_param_count, "MFNGabor": MFNGabor.calc_param_count}
-ALL_CHECK_PARAM_COUNT = {}
+# registry with the reference's names (utils/Networks.py:795-802).  SIREN, FFN, NeRF, MFNFourier, MFNGabor, SIREN_Pyramid, SIRENFT and
+# SIRENPS exist on the fused path; every other phi.name of the reference raises instead of silently running something else.
+ALLPHI = {"SIREN": SIREN, "FFN": FFN, "NeRF": NeRF, "MFNFourier": MFNFourier, "MFNGabor": MFNGabor,
+          "SIREN_Pyramid": SIREN_Pyramid, "SIRENFT": SIRENFT, "SIRENPS": SIRENPS}
+ALL_CALC_PHI_FEATURES = {k: v.calc_features for k, v in ALLPHI.items()}
+ALL_CALC_PHI_PARAM_COUNT = {k: v.calc_param_count for k, v in ALLPHI.items()}
+# budget floors (main.py:222-234): the only nets NFGR.estimate_module_size knows by name; under its floor SIREN_Pyramid becomes SIRENFT,
+# SIRENFT and SIRENPS become SIREN
+ALL_CHECK_PARAM_COUNT = {"SIREN_Pyramid": SIREN_Pyramid.check_param_count, "SIRENFT": SIRENFT.check_param_count,
+                         "SIRENPS": SIRENPS.check_param_count}
 # keys a Module.phi spec of this net must name: the reference's NeRF budget rule (calc_features / calc_param_count,
 # utils/Networks.py:118-136) takes frequencies and skip without defaults, so its NFGR cannot build a NeRF from a spec that leaves them
 # out; init_phi refuses such a spec by name instead of filling in the constructor's defaults
-# (the MFN budget rules, utils/Networks.py:727-731 / 793-797, take coords_channel, data_channel and layers without defaults)
+# (the MFN budget rules, utils/Networks.py:727-731 / 793-797, take coords_channel, data_channel and layers without defaults; the
+# tapered SIRENs' rules, :347-369 / :417-457 / :488-552, also res and features_dis or ratio)
+_TAPER_KEYS = ("coords_channel", "data_channel", "layers", "res")
 REQUIRED_PHI_KEYS = {"NeRF": ("frequencies", "skip"), "MFNFourier": ("coords_channel", "data_channel", "layers"),
-                     "MFNGabor": ("coords_channel", "data_channel", "layers")}
+                     "MFNGabor": ("coords_channel", "data_channel", "layers"), "SIREN_Pyramid": _TAPER_KEYS + ("features_dis",),
+                     "SIRENFT": _TAPER_KEYS + ("ratio",), "SIRENPS": _TAPER_KEYS + ("ratio",)}
 
 
 def init_phi(kwargs):
     kwargs = copy.deepcopy(dict(kwargs))
     name = kwargs.pop("name")
     if name not in ALLPHI:
-        raise NotImplementedError("Module.phi.name=%r is not available on the fused MI355X path (only SIREN, FFN, NeRF, MFNFourier and "
-                                  "MFNGabor)" % name)
+        raise NotImplementedError("Module.phi.name=%r is not available on the fused MI355X path (only SIREN, FFN, NeRF, MFNFourier, "
+                                  "MFNGabor, SIREN_Pyramid, SIRENFT and SIRENPS)" % name)
     missing = [k for k in REQUIRED_PHI_KEYS.get(name, ()) if k not in kwargs]
     if missing:
         raise NotImplementedError("Module.phi.name=%r without %s is not supported: the reference's budget rule for this net needs %s "

@@ -422,6 +422,65 @@ typedef struct brief_mfn_fit_job {
 /* `steps` optimizer steps (train step + reduction + update + repack: four launches each, no host synchronisation) */
 int brief_mfn_fit(const brief_mfn_fit_job *job, int64_t steps, void *stream);
 
+/* ---- tapered SIRENs: SIREN_Pyramid, SIRENFT, SIRENPS  utils/Networks.py:316-552 ---------------------------------------------
+ *   a SIREN whose every Linear has its own width and every sine its own w0:
+ *   h_0 = sin(w0[0] (W_0 x + b_0)),  h_l = sin(w0[l] (W_l h_{l-1} + b_l))  (l = 1 .. layers-2),  y = Wh h_{layers-2} + bh,
+ *   sin(w0[layers-1] y) with output_act.  W_l is [widths[l]][widths[l-1]] (W_0: [widths[0]][cin], Wh: [cout][widths[layers-2]]).
+ * Limits (anything else: BRIEF_ERR_INVALID with a message naming the limit): fp32 only, cin 2 | 3, cout 1 .. 4, layers 3 ..
+ * BRIEF_TAPER_MAX_LAYERS, every hidden width 1 .. 1024 (each layer padded on its own to whole 32-wide tiles), output_act 0 | 1.
+ * Canonical parameter buffer (== torch state_dict() order): (W_l b_l) per Linear in layer order.  The whole buffer is trained. */
+#define BRIEF_TAPER_MAX_LAYERS 16
+typedef struct {
+    int32_t cin;          /* 2 | 3 */
+    int32_t cout;         /* 1 .. 4 */
+    int32_t layers;       /* 3 .. BRIEF_TAPER_MAX_LAYERS Linear layers, the head included */
+    int32_t output_act;   /* 0 | 1 */
+    int32_t widths[BRIEF_TAPER_MAX_LAYERS];   /* outputs of Linear 0 .. layers-2 (1 .. 1024 each); the rest is ignored */
+    float w0[BRIEF_TAPER_MAX_LAYERS];         /* w0 of the sine behind Linear l (l = layers-1: the output activation) */
+} brief_taper_desc;
+
+/* floats of the canonical buffer / of the fragment-ordered copy / train-step scratch bytes */
+int64_t brief_taper_param_count(const brief_taper_desc *d);
+int64_t brief_taper_packed_count(const brief_taper_desc *d);
+int64_t brief_taper_train_workspace_bytes(const brief_taper_desc *d, int64_t n);
+/* canonical params -> fragment-ordered copy (call after every change of params made outside brief_taper_fit) */
+int brief_taper_repack(const brief_taper_desc *d, const float *params, float *packed, void *stream);
+/* forward under no_grad, with the out_kind epilogue of brief_siren_forward (no scratch) */
+int brief_taper_forward(const brief_taper_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                        void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream);
+/* the box decode of brief_siren_forward_box (same box rules and refusals) */
+int brief_taper_forward_box(const brief_taper_desc *d, const float *packed, const brief_grid_box *box, int64_t offset, int64_t n,
+                            void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream);
+/* forward + loss + backward of one batch, as brief_siren_train_step (grads: canonical layout) */
+int brief_taper_train_step(const brief_taper_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                           int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
+                           void *workspace, int64_t workspace_bytes, void *stream);
+/* brief_fit_job with a tapered desc: every field after `desc` means exactly what it means in brief_fit_job
+ * (workspace: brief_taper_train_workspace_bytes(desc, batch.n)) */
+typedef struct brief_taper_fit_job {
+    brief_taper_desc desc;
+    brief_grid_desc grid;
+    brief_batch_desc batch;
+    float *params, *packed;
+    float *state1, *state2;
+    float *grads;
+    float *loss_out;
+    float *loss_log;
+    void *workspace;
+    int64_t workspace_bytes;
+    int32_t loss_kind, optim_kind;
+    float thr, beta;
+    double lr, beta1, beta2, eps;
+    const int64_t *milestones;
+    int32_t n_milestones, reserved;
+    double gamma;
+    int64_t t0;
+    const double *lr_table, *beta1_table;
+    int64_t idx_stride;
+} brief_taper_fit_job;
+/* `steps` optimizer steps (train step + reduction + update + repack: four launches each, no host synchronisation) */
+int brief_taper_fit(const brief_taper_fit_job *job, int64_t steps, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
