@@ -108,7 +108,8 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_mfn_param_count", "brief_mfn_packed_count", "brief_mfn_train_workspace_bytes", "brief_mfn_repack", "brief_mfn_forward",
            "brief_mfn_forward_box", "brief_mfn_train_step", "brief_mfn_fit",
            "brief_taper_param_count", "brief_taper_packed_count", "brief_taper_train_workspace_bytes", "brief_taper_repack",
-           "brief_taper_forward", "brief_taper_forward_box", "brief_taper_train_step", "brief_taper_fit"]
+           "brief_taper_forward", "brief_taper_forward_box", "brief_taper_train_step", "brief_taper_fit",
+           "brief_correct_chunk_elems", "brief_correct_count", "brief_correct_emit", "brief_correct_apply"]
 
 
 def needs_build():
@@ -235,6 +236,11 @@ def lib():
     L.brief_taper_forward_box.argtypes = [tp_, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
     L.brief_taper_train_step.argtypes = [tp_, vp, gp, bp, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, C.c_int64, vp]
     L.brief_taper_fit.argtypes = [C.POINTER(TaperFitJob), C.c_int64, vp]
+    L.brief_correct_chunk_elems.restype = C.c_int64
+    L.brief_correct_chunk_elems.argtypes = [C.c_int]
+    L.brief_correct_count.argtypes = [vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp, vp]
+    L.brief_correct_emit.argtypes = [vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int64, vp, vp, vp]
+    L.brief_correct_apply.argtypes = [vp, C.c_int, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp]
     _LIB = L
     return L
 

@@ -33,6 +33,7 @@
 //   k_repack           canonical params -> fragment-ordered copies (fp32, and bf16 when precision = BF16).
 //   brief_bf16.inc     k16 / k_wgrad16 / k_reduce16: the same path on v_mfma_f32_32x32x16_bf16 (BRIEF_PREC_BF16).
 //   k_sample, k_sse_u16, k_ssim_u16, k_deblock_edge: index stream, metrics and the deblocking filter.
+//   brief_correct.inc  k_correct_count / k_correct_emit / k_correct_apply: the stored corrections of the error-bounded mode.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
@@ -57,6 +58,7 @@
 #include "brief_nerf.inc"       // NeRF: k_nerf_fwd, k_nerf_wgrad, k_nerf_repack
 #include "brief_mfn.inc"        // MFN: k_mfn_fwd, k_mfn_wgrad, k_mfn_repack
 #include "brief_taper.inc"      // tapered SIRENs: k_taper_fwd, k_taper_wgrad, k_taper_repack
+#include "brief_correct.inc"    // error-bounded mode: k_correct_count, k_correct_emit, k_correct_apply
 
 // =============================================================================================
 // C-ABI
@@ -1522,6 +1524,80 @@ int brief_sse_u16(const uint16_t *a, const uint16_t *b, int64_t n, double *sse_o
     HIP_TRY(hipMemsetAsync(acc, 0, sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_sse_u16, dim3(1024), dim3(256), 0, st, a, b, n, acc);
     hipLaunchKernelGGL(k_u64_to_double, dim3(1), dim3(1), 0, st, acc, sse_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- error-bounded mode (brief_correct.inc)
+static const int64_t kCorrMaxElems = (int64_t)1 << 40;
+static int check_correct(const void *a, const void *b, int elem_bytes, int64_t n, int64_t bound, int64_t base)
+{
+    if (elem_bytes != 1 && elem_bytes != 2) return fail(BRIEF_ERR_INVALID, "corrections: elem_bytes must be 1 (uint8) or 2 (uint16)");
+    if (!a || !b) return fail(BRIEF_ERR_INVALID, "corrections: null buffer");
+    if (((uintptr_t)a | (uintptr_t)b) & 15) return fail(BRIEF_ERR_INVALID, "corrections: both arrays must be 16-byte aligned");
+    if (n < 1 || base < 0 || n > kCorrMaxElems || base > kCorrMaxElems - n) return fail(BRIEF_ERR_INVALID, "corrections: need n >= 1, base >= 0 and base + n <= 2^40");
+    if (bound < 0 || bound > 65535) return fail(BRIEF_ERR_INVALID, "corrections: the error bound must be 0 .. 65535");
+    return 0;
+}
+static int corr_grid(int64_t nchunks)
+{
+    const int64_t cap = (int64_t)kCUs * 8;
+    return (int)(nchunks < cap ? nchunks : cap);
+}
+
+int64_t brief_correct_chunk_elems(int elem_bytes) { return elem_bytes == 1 || elem_bytes == 2 ? kCorrChunkBytes / elem_bytes : -1; }
+
+int brief_correct_count(const void *dec, const void *src, int elem_bytes, int64_t n, int64_t bound, int64_t base, int32_t *counts, void *stream)
+{
+    if (int rc = check_correct(dec, src, elem_bytes, n, bound, base)) return rc;
+    if (!counts) return fail(BRIEF_ERR_INVALID, "corrections: null buffer");
+    const int64_t E = kCorrChunkBytes / elem_bytes, nchunks = (n + E - 1) / E;
+    if (elem_bytes == 1)
+        hipLaunchKernelGGL(k_correct_count<uint8_t>, dim3(corr_grid(nchunks)), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)dec, (const uint8_t *)src,
+                           n, (int)bound, nchunks, counts);
+    else
+        hipLaunchKernelGGL(k_correct_count<uint16_t>, dim3(corr_grid(nchunks)), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)dec, (const uint16_t *)src,
+                           n, (int)bound, nchunks, counts);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_correct_emit(const void *dec, const void *src, int elem_bytes, int64_t n, int64_t bound, int64_t base, const int64_t *offsets, int64_t total,
+                       int64_t *idx_out, int32_t *q_out, void *stream)
+{
+    if (int rc = check_correct(dec, src, elem_bytes, n, bound, base)) return rc;
+    if (total < 0 || total > n) return fail(BRIEF_ERR_INVALID, "corrections: total must be 0 .. n");
+    if (total == 0) return 0;
+    if (!offsets || !idx_out || !q_out) return fail(BRIEF_ERR_INVALID, "corrections: null buffer");
+    const int64_t E = kCorrChunkBytes / elem_bytes, nchunks = (n + E - 1) / E;
+    if (elem_bytes == 1)
+        hipLaunchKernelGGL(k_correct_emit<uint8_t>, dim3(corr_grid(nchunks)), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)dec, (const uint8_t *)src,
+                           n, (int)bound, base, nchunks, offsets, total, idx_out, q_out);
+    else
+        hipLaunchKernelGGL(k_correct_emit<uint16_t>, dim3(corr_grid(nchunks)), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)dec, (const uint16_t *)src,
+                           n, (int)bound, base, nchunks, offsets, total, idx_out, q_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_correct_apply(void *out, int elem_bytes, int64_t n, const int64_t *idx, const int32_t *q, int64_t count, int64_t bound, int64_t base, void *stream)
+{
+    if (elem_bytes != 1 && elem_bytes != 2) return fail(BRIEF_ERR_INVALID, "corrections: elem_bytes must be 1 (uint8) or 2 (uint16)");
+    if (n < 1 || base < 0 || n > kCorrMaxElems || base > kCorrMaxElems - n) return fail(BRIEF_ERR_INVALID, "corrections: need n >= 1, base >= 0 and base + n <= 2^40");
+    if (bound < 0 || bound > 65535) return fail(BRIEF_ERR_INVALID, "corrections: the error bound must be 0 .. 65535");
+    if (count < 0) return fail(BRIEF_ERR_INVALID, "corrections: negative count");
+    if (count == 0) return 0;
+    if (!out || !idx || !q) return fail(BRIEF_ERR_INVALID, "corrections: null buffer");
+    const int m = 2 * (int)bound + 1;
+    const int64_t per = (int64_t)1 << 30;                          // corrections per launch (the grid's x extent is 32-bit)
+    for (int64_t k0 = 0; k0 < count; k0 += per) {
+        const int64_t cnt = count - k0 < per ? count - k0 : per;
+        const unsigned blocks = (unsigned)((cnt + 255) / 256);
+        if (elem_bytes == 1)
+            hipLaunchKernelGGL(k_correct_apply<uint8_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (uint8_t *)out, n, idx + k0, q + k0, cnt, m, base);
+        else
+            hipLaunchKernelGGL(k_correct_apply<uint16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (uint16_t *)out, n, idx + k0, q + k0, cnt, m, base);
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -18,7 +18,7 @@ from os.path import splitext as ops
 import numpy as np
 import torch
 
-from . import _lib, config
+from . import _lib, config, corrections
 from . import region as region_mod
 from .fit import Fitter
 from .io import (get_folder_size, get_type_max, invnormalize_data, minmaxany_range, normalize_data, normalize_data_device, range_limit, save_yaml,
@@ -177,25 +177,43 @@ class NFGR:
         if isinstance(sideinfos, str):
             sideinfos = load_yaml(sideinfos)
         cf = copy.deepcopy(opt.CompressFramework)
+        corr = _load_corrections(cf, module_path, sideinfos)      # error-bounded artefacts: raises before any decode if they cannot be honoured
+        cf.Module.phi.features = sideinfos["phi_features"]
+        cf.Module.phi.name = sideinfos["phi_name"]
+        shape = list(sideinfos["data_shape"])
+        dims = shape[:-1]
+        lo, hi = _coords_range(cf.Compress.coords_mode)
+        rng = minmaxany_range(cf.Normalize.name)
+        if rng is not None and sideinfos["dtype"] in ("uint8", "uint16"):
+            out = NFGR._decode_integer(cf, module_path, sideinfos, device)
+            if corr is not None:
+                corrections.apply(out, corr[0], corr[1], corr[2]["bound"])
+            data = out.cpu().numpy().reshape(shape)
+        else:
+            # decode in the arithmetic the net was fitted in (side info records it when it is not fp32)
+            phi = init_phi({**dict(cf.Module.phi), "precision": str(sideinfos.get("phi_precision", cf.Compress.get("precision", "fp32")))})
+            load_model(phi, module_path, "cpu")
+            phi.to(device)
+            yhat = phi.decode_grid(dims, lo, hi).cpu().reshape(shape)
+            data = invnormalize_data(yhat, sideinfos, cf.Normalize.name)
+        pp = cf.Decompress.postprocess
+        return preprocess(data, pp.denoise.level, pp.denoise.close, pp.clip)
+
+    @staticmethod
+    def _decode_integer(cf, module_path, sideinfos, device="cuda"):
+        """the fused integer branch of decompress (uint8 / uint16 data under 'minmaxany_a_b'): the stored weights evaluated over the
+        whole grid, as a device tensor [voxels, channels] in the source dtype, WITHOUT corrections.  cf: CompressFramework options."""
+        cf = copy.deepcopy(cf)
         cf.Module.phi.features = sideinfos["phi_features"]
         cf.Module.phi.name = sideinfos["phi_name"]
         # decode in the arithmetic the net was fitted in (side info records it when it is not fp32)
         phi = init_phi({**dict(cf.Module.phi), "precision": str(sideinfos.get("phi_precision", cf.Compress.get("precision", "fp32")))})
         load_model(phi, module_path, "cpu")
         phi.to(device)
-        shape = list(sideinfos["data_shape"])
-        dims = shape[:-1]
         lo, hi = _coords_range(cf.Compress.coords_mode)
-        rng = minmaxany_range(cf.Normalize.name)
-        if rng is not None and sideinfos["dtype"] in ("uint8", "uint16"):
-            kind = "u8" if sideinfos["dtype"] == "uint8" else "u16"
-            out = phi.decode_grid(dims, lo, hi, out_kind=kind, scale=rng, vrange=(sideinfos["min"], sideinfos["max"]))
-            data = out.cpu().numpy().reshape(shape)
-        else:
-            yhat = phi.decode_grid(dims, lo, hi).cpu().reshape(shape)
-            data = invnormalize_data(yhat, sideinfos, cf.Normalize.name)
-        pp = cf.Decompress.postprocess
-        return preprocess(data, pp.denoise.level, pp.denoise.close, pp.clip)
+        kind = "u8" if sideinfos["dtype"] == "uint8" else "u16"
+        return phi.decode_grid(list(sideinfos["data_shape"])[:-1], lo, hi, out_kind=kind, scale=minmaxany_range(cf.Normalize.name),
+                               vrange=(sideinfos["min"], sideinfos["max"]))
 
     def sample_nf(self, coords):
         """main.py:266-268: the fitted network evaluated at `coords` without autograd"""
@@ -233,6 +251,10 @@ class NFGR:
         _region_postprocess_check(dtype, pp)
         data_shape = list(sideinfos["data_shape"])
         dims = data_shape[:-1]
+        if shape is not None and "error_bound" in sideinfos:
+            raise ValueError("a resampled view (shape) of an error-bounded artefact is refused: its corrections (error_bound %s) exist on the "
+                             "fitted grid %s only" % (sideinfos["error_bound"], dims))
+        corr = _load_corrections(cf, module_path, sideinfos)
         if shape is not None:
             shape = [int(v) for v in shape]
             if len(shape) != len(dims) or any(v < 1 for v in shape):
@@ -248,7 +270,13 @@ class NFGR:
         rng = minmaxany_range(cf.Normalize.name)
         if rng is not None and sideinfos["dtype"] in ("uint8", "uint16"):
             kind = "u8" if sideinfos["dtype"] == "uint8" else "u16"
-            data = phi.decode_box(dims, start, stop, stp, lo, hi, out_kind=kind, scale=rng, vrange=(sideinfos["min"], sideinfos["max"])).cpu().numpy()
+            box = phi.decode_box(dims, start, stop, stp, lo, hi, out_kind=kind, scale=rng, vrange=(sideinfos["min"], sideinfos["max"]))
+            if corr is not None:
+                # the block's corrections that fall on the box, as flat indices into it (the channel axis is whole)
+                cout = data_shape[-1]
+                bi, bq = corrections.select(corr[0], corr[1], dims + [cout], start + [0], stop + [cout], stp + [1])
+                corrections.apply(box, bi, bq, corr[2]["bound"])
+            data = box.cpu().numpy()
         else:
             yhat = phi.decode_box(dims, start, stop, stp, lo, hi).cpu()
             data = invnormalize_data(yhat, sideinfos, cf.Normalize.name)
@@ -272,6 +300,9 @@ class NFGR:
         if data is None:
             data = read_img(data_path)
         data = np.asarray(data)
+        bound = error_bound_of(opt)
+        if bound is not None:
+            check_error_bound(opt, data.dtype)      # refused here, before any work: the bound could not be promised
         cube = C_.sampler.cube_len
         cube_vox = cube[0] * cube[1] * cube[2] if data.ndim == 4 else cube[1] * cube[2]
         if C_.sampler.name == "randomcube" and min(data.size, cube_vox) > 80 * 80 * 80:
@@ -292,6 +323,8 @@ class NFGR:
         sideinfos = {**sideinfos, "data_shape": list(pre.shape), "phi_features": feats, "phi_name": opt.Module.phi.name}
         if self.precision != "fp32":
             sideinfos["phi_precision"] = getattr(self, "module_precision", self.precision)      # extra key only off the reference's fp32 path: what THIS net was fitted in
+        if bound is not None:
+            sideinfos["error_bound"] = bound      # extra key only in the error-bounded mode: a decoder that sees it insists on the corrections file
         dims = list(pre.shape[:-1])
         cout = pre.shape[-1]
         tgt = tgt_dev.reshape(-1, cout)
@@ -333,7 +366,8 @@ class NFGR:
                      loss=C_.loss.name, thr=thr, beta=C_.loss.beta, seed=getattr(opt, "_seed", 42), index_stream=index_stream)
         self.sideinfos = sideinfos
         return {"fit": fit, "phi": phi, "data": data, "data_path": data_path, "logdir": logdir, "name": name, "ext": ext,
-                "sideinfos": sideinfos, "theory_size": theory_size, "results": {}}
+                "sideinfos": sideinfos, "theory_size": theory_size, "results": {},
+                "fitted": pre if bound is not None else None}      # the volume the bound is promised against
 
     def checkpoint(self, ctx, steps, loss, evaluate=True):
         """main.py:405-450 at one checkpoint: weight files + sideinfos, optional decode + metrics."""
@@ -345,13 +379,25 @@ class NFGR:
         module_path, side_path = opj(cdir, "module"), opj(cdir, "sideinfos.yaml")
         save_yaml(sideinfos, side_path)
         save_model(ctx["phi"], module_path, self.device)
+        bound, corr_bytes, dec_t = error_bound_of(opt), 0, None
+        if bound is not None:
+            # error-bounded mode, whether or not this checkpoint is evaluated: decode what was just written, store a correction for
+            # every element off by more than the bound (corrections.bin beside `module`), record count and size in the side info
+            dec_t, count, corr_bytes = self._store_corrections(ctx, module_path, sideinfos, bound)
+            sideinfos = {**sideinfos, "corrections": {"count": count, "bytes": corr_bytes}}
+            save_yaml(sideinfos, side_path)
         orig_bytes = os.path.getsize(ctx["data_path"]) if os.path.exists(ctx["data_path"]) else data.nbytes
         side_bytes = os.path.getsize(side_path)
         if Log is not None:
-            Log.log_metrics({"compress_ratio/theory": orig_bytes / (side_bytes + ctx["theory_size"]),
-                             "compress_ratio/actual": orig_bytes / (side_bytes + get_folder_size(module_path))}, steps)
+            Log.log_metrics({"compress_ratio/theory": orig_bytes / (side_bytes + ctx["theory_size"] + corr_bytes),
+                             "compress_ratio/actual": orig_bytes / (side_bytes + get_folder_size(module_path) + corr_bytes)}, steps)
         if C_.decompress and evaluate:
-            dec = NFGR.decompress(_wrap(opt), module_path, sideinfos, self.device)
+            if dec_t is not None:
+                # the corrected decode of the correction step itself (Decompress.postprocess is the identity in this mode)
+                dec = dec_t.cpu().numpy().reshape(sideinfos["data_shape"])
+            else:
+                dec = NFGR.decompress(_wrap(opt), module_path, sideinfos, self.device)
+            del dec_t
             if opt.Decompress.keep_decompressed:
                 ddir = opj(sdir, "decompressed")
                 os.makedirs(ddir, exist_ok=True)
@@ -369,10 +415,25 @@ class NFGR:
                     Log.log_metrics({k: v for k, v in perf.items() if k != "steps"}, steps)
             else:
                 perf = eval_performance(steps, data, dec, Log, opt.Decompress.mse, opt.Decompress.psnr, opt.Decompress.ssim)
+            if bound is not None:
+                perf["max_abs_error"] = int(np.abs(dec.astype(np.int64) - data.astype(np.int64)).max())
+                if Log is not None:
+                    Log.log_metrics({"max_abs_error": perf["max_abs_error"]}, steps)
             perf["loss"] = float(loss.item())
             _append_csv(opj(ctx["logdir"], "performance.csv"), perf)
             ctx["results"][steps] = perf
         # (which step directories survive is compress()'s business: main.py:452-453 / -stepstore)
+
+    def _store_corrections(self, ctx, module_path, sideinfos, bound):
+        """decode the artefact FROM THE FILES just written (the path NFGR.decompress takes: a `half` artefact is corrected against
+        what its stored weights decode to), find the corrections on the device, write them beside `module`, apply them.
+        Returns (corrected decode as a device tensor [voxels, channels], number of corrections, bytes of the file)."""
+        dec_t = NFGR._decode_integer(self.opt, module_path, sideinfos, self.device)
+        src_t = torch.from_numpy(np.ascontiguousarray(ctx["fitted"])).to(self.device)
+        idx, q = corrections.find(dec_t, src_t, bound)
+        nbytes = corrections.write(corrections.path_for(module_path), idx, q, bound, dec_t.numel(), sideinfos["dtype"])
+        corrections.apply(dec_t, idx, q, bound)
+        return dec_t, int(idx.numel()), nbytes
 
     def compress(self, data_path, data=None, logdir=None, evaluate=True):
         """main.py:322-454.  The loop body runs inside libbrief_hip.so: one brief_siren_fit call covers every step up to
@@ -450,6 +511,8 @@ class NFGR:
         assert data.ndim == self.opt.Module.phi.coords_channel + 1, "The data dimension {} is inconsistent with the neural network input {}!".format(data.ndim - 1, self.opt.Module.phi.coords_channel)
         assert data.shape[-1] == self.opt.Module.phi.data_channel, "The number of data channels {} is inconsistent with the output of neural network {}!".format(data.shape[-1], self.opt.Module.phi.data_channel)
         name, ext = ops(opb(data_path))
+        if error_bound_of(self.opt) is not None:
+            check_error_bound(self.opt, data.dtype)      # before partitioning (every block's prepare_fit would refuse it too)
         checkpoints = parse_checkpoints(C_.checkpoints, C_.max_steps)
         chunks, owner, src, orig_sideinfos = self._partition_blocks(data, data_path, name, ext)
         self.block_order = [c["name"] for i, c in enumerate(chunks) if owner[i] == rank]      # the order this rank's nets were initialised in
@@ -561,8 +624,11 @@ class NFGR:
                 else:
                     CopyDir(opj(srcd, "module"), opj(mdst, "module"))
                 shutil.copy(opj(srcd, "sideinfos.yaml"), opj(sdst, "sideinfos.yaml"))
+                if os.path.isfile(opj(srcd, corrections.FILE_NAME)):      # error-bounded mode: the block's corrections travel beside its `module`
+                    shutil.copy(opj(srcd, corrections.FILE_NAME), opj(mdst, corrections.FILE_NAME))
             ctx["fit"] = None
             ctx["phi"] = None
+            ctx["fitted"] = None
 
     @staticmethod
     def _fit_step_synchronous(blocks, checkpoints, marks, on_mark, cotrain):
@@ -607,6 +673,7 @@ class NFGR:
             side = load_yaml(opj(step_dir, "compressed", "sideinfos", c["name"], "sideinfos.yaml"))
             y0, y1, x0, x1 = r["h"][0], r["h"][1] + 1, r["w"][0], r["w"][1] + 1
             if fused:
+                corr = _load_corrections(self.opt, mod, side)
                 cf = copy.deepcopy(self.opt)
                 cf.Module.phi.features = side["phi_features"]
                 cf.Module.phi.name = side.get("phi_name", cf.Module.phi.name)
@@ -618,6 +685,11 @@ class NFGR:
                 off, cnt = ((za - bz0) * plane, (zb - za) * plane) if three_d else (0, plane)
                 part = phi.decode_grid(dims, lo, hi, offset=off, count=cnt, out_kind="u8" if tdt == torch.uint8 else "u16",
                                        scale=minmaxany_range(self.opt.Normalize.name), vrange=(side["min"], side["max"]))
+                if corr is not None:
+                    # the block's corrections inside this z-range: a contiguous range of its flattened elements
+                    e0 = off * part.shape[-1]
+                    ci, cq = corrections.select_range(corr[0], corr[1], e0, e0 + part.numel())
+                    corrections.apply(part, ci, cq, corr[2]["bound"], base=e0)
                 if three_d:
                     slab[za - z0:zb - z0, y0:y1, x0:x1] = part.view(zb - za, y1 - y0, x1 - x0, -1)
                 else:
@@ -645,6 +717,8 @@ class NFGR:
         gpu_metrics = data.dtype == np.uint16 and three_d and shape[-1] == 1 and min(shape[1:3]) >= 11
         K = len(checkpoints)
         acc = np.zeros(2 * K + 2, np.float64)        # [SSE_k..., SSIM-sum_k..., slices, elements]
+        bound = error_bound_of(self.opt)
+        worst = np.zeros(K, np.float64)              # error-bounded mode: max |x - x^| per checkpoint over this rank's slab
         keep = bool(self.opt.Decompress.keep_decompressed)
         out_paths = {}
         for k in checkpoints:
@@ -682,11 +756,15 @@ class NFGR:
                     acc[ki] = sse.item()
                     if self.opt.Decompress.ssim:
                         acc[K + ki], _ = gpu_ssim_u16(orig_t, dec_t)
+                    if bound is not None:
+                        worst[ki] = corrections.max_abs_diff(orig_t, dec_t)
                     dec = dec_t.cpu().numpy() if keep else None
                 else:
                     dec = dec_t.cpu().numpy()
                     d64 = dec.astype(np.int64) - orig.astype(np.int64) if np.issubdtype(data.dtype, np.integer) else dec.astype(np.float64) - orig
                     acc[ki] = float((d64 * d64).sum())
+                    if bound is not None:
+                        worst[ki] = float(np.abs(d64).max())
                     if self.opt.Decompress.ssim:
                         if three_d:
                             acc[K + ki] = sum(cal_ssim(orig[i].astype(np.float32), dec[i].astype(np.float32), drange) for i in range(z1 - z0))
@@ -700,6 +778,8 @@ class NFGR:
             acc[2 * K] = float(z1 - z0)
             acc[2 * K + 1] = float(orig.size)
         tot = allreduce_sum(acc, self.device)         # RCCL over xGMI: the one data collective of this path
+        if bound is not None:
+            worst = allreduce_max(worst, self.device)
         if want_mip:
             # projections of the z-slabs: elementwise MAX over the ranks (the data is non-negative; a rank without a row holds zeros)
             zero = [np.zeros(tuple(shape[1:]), data.dtype), np.zeros((nz,) + tuple(shape[2:]), data.dtype), np.zeros((nz, shape[1]) + tuple(shape[3:]), data.dtype)]
@@ -722,9 +802,14 @@ class NFGR:
                     perf["mse"] = tot[ki] / tot[2 * K + 1]
                 if self.opt.Decompress.ssim:
                     perf["ssim"] = tot[K + ki] / tot[2 * K]
+                if bound is not None:
+                    perf["max_abs_error"] = int(worst[ki])
                 orig_bytes = os.path.getsize(data_path) if os.path.exists(data_path) else data.nbytes
                 cdir = opj(sdir, "compressed")
                 theory = get_folder_size(opj(cdir, "sideinfos")) + sum(c["theory_module_size"] for c in chunks)
+                if bound is not None:     # every ratio counts the corrections (compress_ratio/actual does through the folder's size)
+                    theory += sum(os.path.getsize(f) for f in (corrections.path_for(opj(cdir, "module", c["name"], "module")) for c in chunks)
+                                  if os.path.isfile(f))
                 Log.log_metrics({"compress_ratio/theory": orig_bytes / theory,
                                  "compress_ratio/actual": orig_bytes / get_folder_size(cdir)}, k)
                 Log.log_metrics({m: v for m, v in perf.items() if m != "steps"}, k)
@@ -734,6 +819,45 @@ class NFGR:
 
 
 # ------------------------------------------------------------------------------------------ helpers
+def error_bound_of(cf):
+    """Compress.error_bound of a CompressFramework option tree: None (off) or the bound in grey levels of the source dtype"""
+    return corrections.parse_bound(cf.Compress.get("error_bound", None))
+
+
+def check_error_bound(cf, dtype):
+    """the error-bounded mode acts on the integers of the fused decode epilogue: uint8 / uint16 data under a 'minmaxany_a_b'
+    normalisation, and nothing may change values behind it (Decompress.postprocess must be the identity).  Anything else is
+    refused by name: the bound could not be promised."""
+    dtype = np.dtype(dtype)
+    if dtype.name not in ("uint8", "uint16"):
+        raise ValueError("Compress.error_bound supports uint8 / uint16 data only: a bound in grey levels cannot be promised for %s data" % dtype.name)
+    if minmaxany_range(cf.Normalize.name) is None:
+        raise ValueError("Compress.error_bound supports the 'minmaxany_a_b' normalisations only (the fused integer decode): the bound "
+                         "cannot be promised under Normalize.name=%s" % cf.Normalize.name)
+    pp = cf.Decompress.postprocess
+    if not preprocess_is_identity(np.zeros(1, dtype), pp.denoise.level, pp.denoise.close, pp.clip):
+        raise ValueError("Compress.error_bound needs an identity Decompress.postprocess (denoise.level <= 0, a clip that covers the %s range): "
+                         "the bound cannot be promised behind postprocess denoise.level=%s clip=%s" % (dtype.name, pp.denoise.level, list(pp.clip)))
+
+
+def _load_corrections(cf, module_path, sideinfos):
+    """None for an artefact without `error_bound` in its side info; else (idx, q, header) of its corrections file.  A decoder never
+    hands back an unbounded volume silently: a missing or foreign file, or decode options the bound does not hold under, raise."""
+    if "error_bound" not in sideinfos:
+        return None
+    check_error_bound(cf, sideinfos["dtype"])
+    path = corrections.path_for(module_path)
+    if not os.path.isfile(path):
+        raise corrections.CorrectionsError("the side info promises error_bound=%s but %s is missing: refusing to decode an unbounded volume"
+                                           % (sideinfos["error_bound"], path))
+    idx, q, head = corrections.read(path)
+    n = int(np.prod(sideinfos["data_shape"]))
+    if head["bound"] != int(sideinfos["error_bound"]) or head["n"] != n or head["dtype"] != sideinfos["dtype"]:
+        raise corrections.CorrectionsError("%s (bound %d, %d %s elements) does not belong to this artefact (error_bound %s, %d %s elements)"
+                                           % (path, head["bound"], head["n"], head["dtype"], sideinfos["error_bound"], n, sideinfos["dtype"]))
+    return idx, q, head
+
+
 def _region_postprocess_check(dtype, pp):
     """a region equals the slice of the whole decode only where Decompress.postprocess is local to a voxel: the clip and a plain
     threshold are; a denoise through a binary opening (denoise.close) of a non-zero level is not.  (At level <= 0 the opening

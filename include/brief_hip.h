@@ -212,6 +212,26 @@ int brief_sample_indices(int64_t *idx, int64_t n, int64_t pop, uint64_t seed, ui
 /* sum of squared differences of two integer volumes (for PSNR, utils/misc.py:451-456); sse_out: one double */
 int brief_sse_u16(const uint16_t *a, const uint16_t *b, int64_t n, double *sse_out, void *stream);
 
+/* ---- error-bounded mode: stored corrections (csrc/brief_correct.inc) ----------------------------------------------------
+ * dec (the decoded artefact) and src (the volume) are device arrays of n uint8 / uint16 elements (elem_bytes 1 | 2), both 16-byte
+ * aligned.  With m = 2 bound + 1, d = src - dec and q = floor((d + bound) / m) (floor division), q != 0 <=> |d| > bound and
+ * |d - q m| <= bound: the corrections are the (index, q) pairs with q != 0, and clamp(dec + q m, 0, type max) is within `bound`
+ * of src.  Finding them is two passes without atomics (the result is the same on every run, ascending in the index):
+ *   brief_correct_count  counts[c] = number of q != 0 among elements [c E, (c + 1) E) of the arrays, E = brief_correct_chunk_elems
+ *                        (elem_bytes), for the ceil(n / E) chunks;
+ *   (caller)             offsets = exclusive scan of counts (int64), total = their sum;
+ *   brief_correct_emit   writes idx_out[k] = base + element index (int64) and q_out[k] = q (int32), k = 0 .. total - 1.
+ *   brief_correct_apply  out[idx[k] - base] = clamp(out[idx[k] - base] + q[k] m, 0, type max) for `count` corrections with distinct
+ *                        indices in [base, base + n) (others are skipped); out: n elements.
+ * `base` is the index of element 0 of the arrays within the volume they are a part of: indices are 64-bit, base + n <= 2^40.
+ * Limits (BRIEF_ERR_INVALID with a message naming the limit): elem_bytes 1 | 2, bound 0 .. 65535, n >= 1, alignment as above. */
+int64_t brief_correct_chunk_elems(int elem_bytes);
+int brief_correct_count(const void *dec, const void *src, int elem_bytes, int64_t n, int64_t bound, int64_t base, int32_t *counts, void *stream);
+int brief_correct_emit(const void *dec, const void *src, int elem_bytes, int64_t n, int64_t bound, int64_t base, const int64_t *offsets, int64_t total,
+                       int64_t *idx_out, int32_t *q_out, void *stream);
+int brief_correct_apply(void *out, int elem_bytes, int64_t n, const int64_t *idx, const int32_t *q, int64_t count, int64_t bound, int64_t base,
+                        void *stream);
+
 /* cal_ssim of utils/misc.py:458-475 for single-channel uint16 volumes [D,H,W]: per z-slice 2-D SSIM (utils/ssim.py:
  * 11-tap Gaussian `window11`, valid padding, K=(0.01,0.03)).  Writes one double per 16x64 output tile, slice-major
  * (brief_ssim_partial_count of them; tiles of slice z are contiguous); slice mean = sum of its tiles / ((H-10)(W-10)),
