@@ -91,6 +91,10 @@ class TaperFitJob(C.Structure):     # brief_taper_fit_job: brief_fit_job's field
     _fields_ = [("desc", TaperDesc)] + FitJob._fields_[1:]
 
 
+# the network families behind the one host driver of csrc/brief_family_host.inc: (entry prefix, desc, fit job); each has the same entries
+FAMILIES = (("ffn", FfnDesc, FfnFitJob), ("nerf", NerfDesc, NerfFitJob), ("mfn", MfnDesc, MfnFitJob), ("taper", TaperDesc, TaperFitJob))
+FAMILY_ENTRIES = ("param_count", "packed_count", "train_workspace_bytes", "repack", "forward", "forward_box", "train_step", "fit")
+
 LOSS_KIND = {"datal2": 0, "datasmoothl1": 1, "external": 2}
 OPT_KIND = {"Adamax": 0, "Adam": 1, "SGD": 2}
 OUT_F32, OUT_U8, OUT_U16 = 0, 1, 2
@@ -101,15 +105,8 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_siren_fit", "brief_multi_fit",
            "brief_optim_step", "brief_sample_indices", "brief_sse_u16", "brief_profile_enable", "brief_profile_fused", "brief_deblock_edge", "brief_ssim_u16", "brief_ssim_partial_count",
            "brief_sincos_probe", "brief_cu_count",
-           "brief_ffn_param_count", "brief_ffn_packed_count", "brief_ffn_train_workspace_bytes", "brief_ffn_repack", "brief_ffn_forward",
-           "brief_ffn_forward_box", "brief_ffn_train_step", "brief_ffn_fit",
-           "brief_nerf_param_count", "brief_nerf_packed_count", "brief_nerf_train_workspace_bytes", "brief_nerf_repack", "brief_nerf_forward",
-           "brief_nerf_forward_box", "brief_nerf_train_step", "brief_nerf_fit",
-           "brief_mfn_param_count", "brief_mfn_packed_count", "brief_mfn_train_workspace_bytes", "brief_mfn_repack", "brief_mfn_forward",
-           "brief_mfn_forward_box", "brief_mfn_train_step", "brief_mfn_fit",
-           "brief_taper_param_count", "brief_taper_packed_count", "brief_taper_train_workspace_bytes", "brief_taper_repack",
-           "brief_taper_forward", "brief_taper_forward_box", "brief_taper_train_step", "brief_taper_fit",
-           "brief_correct_chunk_elems", "brief_correct_count", "brief_correct_emit", "brief_correct_apply"]
+           "brief_correct_chunk_elems", "brief_correct_count", "brief_correct_emit", "brief_correct_apply"] \
+    + ["brief_%s_%s" % (prefix, entry) for prefix, _, _ in FAMILIES for entry in FAMILY_ENTRIES]
 
 
 def needs_build():
@@ -192,50 +189,18 @@ def lib():
     L.brief_cu_count.restype = C.c_int
     L.brief_profile_enable.argtypes = [C.c_int]
     L.brief_profile_fused.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    fp = C.POINTER(FfnDesc)
-    for name in ("brief_ffn_param_count", "brief_ffn_packed_count"):
-        getattr(L, name).restype = C.c_int64
-        getattr(L, name).argtypes = [fp]
-    L.brief_ffn_train_workspace_bytes.restype = C.c_int64
-    L.brief_ffn_train_workspace_bytes.argtypes = [fp, C.c_int64]
-    L.brief_ffn_repack.argtypes = [fp, vp, vp, vp]
-    L.brief_ffn_forward.argtypes = [fp, vp, gp, bp, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
-    L.brief_ffn_forward_box.argtypes = [fp, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
-    L.brief_ffn_train_step.argtypes = [fp, vp, gp, bp, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, C.c_int64, vp]
-    L.brief_ffn_fit.argtypes = [C.POINTER(FfnFitJob), C.c_int64, vp]
-    np_ = C.POINTER(NerfDesc)
-    for name in ("brief_nerf_param_count", "brief_nerf_packed_count"):
-        getattr(L, name).restype = C.c_int64
-        getattr(L, name).argtypes = [np_]
-    L.brief_nerf_train_workspace_bytes.restype = C.c_int64
-    L.brief_nerf_train_workspace_bytes.argtypes = [np_, C.c_int64]
-    L.brief_nerf_repack.argtypes = [np_, vp, vp, vp]
-    L.brief_nerf_forward.argtypes = [np_, vp, gp, bp, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
-    L.brief_nerf_forward_box.argtypes = [np_, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
-    L.brief_nerf_train_step.argtypes = [np_, vp, gp, bp, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, C.c_int64, vp]
-    L.brief_nerf_fit.argtypes = [C.POINTER(NerfFitJob), C.c_int64, vp]
-    mp_ = C.POINTER(MfnDesc)
-    for name in ("brief_mfn_param_count", "brief_mfn_packed_count"):
-        getattr(L, name).restype = C.c_int64
-        getattr(L, name).argtypes = [mp_]
-    L.brief_mfn_train_workspace_bytes.restype = C.c_int64
-    L.brief_mfn_train_workspace_bytes.argtypes = [mp_, C.c_int64]
-    L.brief_mfn_repack.argtypes = [mp_, vp, vp, vp]
-    L.brief_mfn_forward.argtypes = [mp_, vp, gp, bp, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
-    L.brief_mfn_forward_box.argtypes = [mp_, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
-    L.brief_mfn_train_step.argtypes = [mp_, vp, gp, bp, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, C.c_int64, vp]
-    L.brief_mfn_fit.argtypes = [C.POINTER(MfnFitJob), C.c_int64, vp]
-    tp_ = C.POINTER(TaperDesc)
-    for name in ("brief_taper_param_count", "brief_taper_packed_count"):
-        getattr(L, name).restype = C.c_int64
-        getattr(L, name).argtypes = [tp_]
-    L.brief_taper_train_workspace_bytes.restype = C.c_int64
-    L.brief_taper_train_workspace_bytes.argtypes = [tp_, C.c_int64]
-    L.brief_taper_repack.argtypes = [tp_, vp, vp, vp]
-    L.brief_taper_forward.argtypes = [tp_, vp, gp, bp, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
-    L.brief_taper_forward_box.argtypes = [tp_, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
-    L.brief_taper_train_step.argtypes = [tp_, vp, gp, bp, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, C.c_int64, vp]
-    L.brief_taper_fit.argtypes = [C.POINTER(TaperFitJob), C.c_int64, vp]
+    for prefix, Desc, Job in FAMILIES:      # the same eight entries per family (csrc/brief_family_host.inc)
+        fp, f = C.POINTER(Desc), (lambda name: getattr(L, "brief_%s_%s" % (prefix, name)))
+        for name in ("param_count", "packed_count", "train_workspace_bytes"):
+            f(name).restype = C.c_int64
+        f("param_count").argtypes = [fp]
+        f("packed_count").argtypes = [fp]
+        f("train_workspace_bytes").argtypes = [fp, C.c_int64]
+        f("repack").argtypes = [fp, vp, vp, vp]
+        f("forward").argtypes = [fp, vp, gp, bp, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
+        f("forward_box").argtypes = [fp, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, vp]
+        f("train_step").argtypes = [fp, vp, gp, bp, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, C.c_int64, vp]
+        f("fit").argtypes = [C.POINTER(Job), C.c_int64, vp]
     L.brief_correct_chunk_elems.restype = C.c_int64
     L.brief_correct_chunk_elems.argtypes = [C.c_int]
     L.brief_correct_count.argtypes = [vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp, vp]

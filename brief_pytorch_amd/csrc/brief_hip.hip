@@ -19,6 +19,8 @@
 // One translation unit: this file holds the C-ABI and the launch logic, the kernels live in the *.inc files included below
 // (brief_device.inc shared definitions, brief_fused.inc k_fused, brief_lean.inc k_lean, brief_small.inc k_small, brief_wgrad.inc k_wgrad,
 //  brief_x3.inc split precision, brief_reduce.inc optimizer + k_reduce, brief_bf16.inc the bf16 path, brief_aux.inc repack / metrics / deblocking).
+// The families with kernels of their own (brief_ffn.inc, brief_nerf.inc, brief_mfn.inc, brief_taper.inc) share ONE host driver and keep their
+// C-ABI entries in brief_family_host.inc, included at the end of this file.
 //
 //   k_fused<NT,TRAIN>  coords -> layer0 -> hidden layers -> head -> loss -> dgrad chain.
 //                      TRAIN stores Z_l (phases w z reduced to revolutions) and D_l (deltas) as [feature][sample]
@@ -609,6 +611,20 @@ static void fill_grid(GridArgs &g, const brief_grid_desc *grid)
     }
     g.fast = total < 4294967296.0;
 }
+// a checked box (check_box) as kernel arguments: the axes past ndim are one voxel wide
+static void fill_box(BoxArgs &bx, const brief_grid_box *box)
+{
+    double total = 1.0;
+    for (int a = 0; a < 3; ++a) {
+        const bool used = a < box->grid.ndim;
+        bx.start[a] = used ? box->start[a] : 0;
+        bx.step[a] = used ? box->step[a] : 1;
+        bx.extent[a] = used ? box->extent[a] : 1;
+        bx.magic[a] = ~(uint64_t)0 / (uint64_t)bx.extent[a] + 1;
+        total *= (double)bx.extent[a];
+    }
+    bx.fast = total < 4294967296.0;      // every extent is below 2^31: the product is exact in double wherever it is below 2^53
+}
 
 // One launch, optionally with a start / stop event pair bound to the DISPATCH itself (hipExtLaunchKernel: the timestamps are the
 // kernel's own begin and end): the live timing of the dominant kernel (brief_profile_*) then costs no marker packets on the stream
@@ -759,11 +775,11 @@ static bool prof_live()
     return g_prof_on && g_prof_n < kProfSlots && g_prof_dev == current_device() && dev_state() && dev_state()->prof_init;
 }
 
-static int check_batch(const brief_siren_desc *d, const brief_grid_desc *grid, const brief_batch_desc *b, bool train)
+static int check_batch(int cin, const brief_grid_desc *grid, const brief_batch_desc *b, bool train)
 {
     if (!b || b->n < 1) return fail(BRIEF_ERR_INVALID, "empty batch");
     if (!b->coords) {
-        if (!grid || grid->ndim != d->cin) return fail(BRIEF_ERR_INVALID, "grid.ndim must equal coords_channel when coords is NULL");
+        if (!grid || grid->ndim != cin) return fail(BRIEF_ERR_INVALID, "grid.ndim must equal coords_channel when coords is NULL");
         for (int a = 0; a < grid->ndim; ++a)
             if (grid->dims[a] < 1) return fail(BRIEF_ERR_INVALID, "bad grid dims");
     }
@@ -773,10 +789,10 @@ static int check_batch(const brief_siren_desc *d, const brief_grid_desc *grid, c
 
 // a box of brief_siren_forward_box: ndim == cin, every dim 1 .. 2^31 - 1, and on every axis extent >= 1, step >= 1, start >= 0 and
 // start + step (extent - 1) < dims.  *voxels: the box's voxel count (saturated at 2^63 - 1; every axis is below 2^31)
-static int check_box(const brief_siren_desc *d, const brief_grid_box *box, int64_t *voxels)
+static int check_box(int cin, const brief_grid_box *box, int64_t *voxels)
 {
     if (!box) return fail(BRIEF_ERR_INVALID, "null box");
-    if (box->grid.ndim != d->cin) return fail(BRIEF_ERR_INVALID, "box grid.ndim must equal coords_channel");
+    if (box->grid.ndim != cin) return fail(BRIEF_ERR_INVALID, "box grid.ndim must equal coords_channel");
     unsigned __int128 total = 1;
     for (int a = 0; a < box->grid.ndim; ++a) {
         const int64_t dim = box->grid.dims[a], st = box->start[a], sp = box->step[a], ex = box->extent[a];
@@ -851,7 +867,7 @@ int brief_siren_forward_ws(const brief_siren_desc *d, const float *packed, const
                            float scale_min, float scale_max, double vmin, double vmax, void *workspace, int64_t workspace_bytes, void *stream)
 {
     if (int rc = check_desc(d)) return rc;
-    if (int rc = check_batch(d, grid, batch, false)) return rc;
+    if (int rc = check_batch(d->cin, grid, batch, false)) return rc;
     if (int rc = check_forward(d, batch->n, packed, out, out_kind, workspace, workspace_bytes)) return rc;
     FusedArgs fa;
     forward_args(fa, d, packed, batch->n, out, out_kind, scale_min, scale_max, vmin, vmax, workspace);
@@ -867,7 +883,7 @@ int brief_siren_forward_box(const brief_siren_desc *d, const float *packed, cons
 {
     if (int rc = check_desc(d)) return rc;
     int64_t voxels = 0;
-    if (int rc = check_box(d, box, &voxels)) return rc;
+    if (int rc = check_box(d->cin, box, &voxels)) return rc;
     if (n < 1) return fail(BRIEF_ERR_INVALID, "empty batch");
     if (offset < 0 || offset > voxels - n) return fail(BRIEF_ERR_INVALID, "offset + n exceeds the box's voxel count");
     if (int rc = check_forward(d, n, packed, out, out_kind, workspace, workspace_bytes)) return rc;
@@ -876,14 +892,7 @@ int brief_siren_forward_box(const brief_siren_desc *d, const float *packed, cons
     forward_args(fa, d, packed, n, out, out_kind, scale_min, scale_max, vmin, vmax, workspace);
     fa.offset = offset;
     fill_grid(fa.grid, &box->grid);
-    for (int a = 0; a < 3; ++a) {
-        const bool used = a < box->grid.ndim;
-        fa.box.start[a] = used ? box->start[a] : 0;
-        fa.box.step[a] = used ? box->step[a] : 1;
-        fa.box.extent[a] = used ? box->extent[a] : 1;
-        fa.box.magic[a] = ~(uint64_t)0 / (uint64_t)fa.box.extent[a] + 1;
-    }
-    fa.box.fast = voxels < ((int64_t)1 << 32);
+    fill_box(fa.box, box);
     return launch_forward<true>(fa, (hipStream_t)stream);
 }
 
@@ -933,7 +942,7 @@ static int train_step_impl(const brief_siren_desc *d, const float *packed, const
 {
     std::lock_guard<std::recursive_mutex> state_lock(g_state_mu);      // (the side-stream plans below: see g_state_mu)
     if (int rc = check_desc(d)) return rc;
-    if (int rc = check_batch(d, grid, batch, true)) return rc;
+    if (int rc = check_batch(d->cin, grid, batch, true)) return rc;
     if (!packed || !grads || !loss_out || !workspace) return fail(BRIEF_ERR_INVALID, "null buffer");
     if (loss_kind < BRIEF_LOSS_L2 || loss_kind > BRIEF_LOSS_EXTERNAL) return fail(BRIEF_ERR_INVALID, "bad loss_kind");
     if (d->precision == BRIEF_PREC_BF16 ? (int64_t)32 * brief_nt(*d) * npad16(batch->n) * 2 >= ((int64_t)1 << 31)
@@ -1604,1204 +1613,4 @@ int brief_correct_apply(void *out, int elem_bytes, int64_t n, const int64_t *idx
 
 }   // extern "C"
 
-// =============================================================================================
-// FFN (Fourier-feature network, brief_ffn.inc): train step = k_ffn_fwd<TRAIN> + k_ffn_wgrad + k_ffn_reduce (+ k_ffn_repack after an update)
-static int check_ffn_desc(const brief_ffn_desc *d)
-{
-    if (!d) return fail(BRIEF_ERR_INVALID, "null desc");
-    if (d->cin != 2 && d->cin != 3) return fail(BRIEF_ERR_INVALID, "FFN: coords_channel must be 2 or 3");
-    if (d->cout < 1 || d->cout > 4) return fail(BRIEF_ERR_INVALID, "FFN: data_channel must be 1..4");
-    if (d->layers < 2) return fail(BRIEF_ERR_INVALID, "FFN: layers must be >= 2");
-    if (d->features < 1 || d->features > 1024) return fail(BRIEF_ERR_INVALID, "FFN: features must be 1..1024 on the fused path");
-    if (d->embsize < 1 || d->embsize > 512) return fail(BRIEF_ERR_INVALID, "FFN: embsize must be 1..512 on the fused path");
-    if (d->reserved != 0) return fail(BRIEF_ERR_INVALID, "FFN: reserved must be 0 (skip connections are not supported)");
-    return 0;
-}
-
-static int ffn_lds_bytes(const brief_ffn_desc &d)
-{
-    const FfnLayout l = ffn_layout(d);
-    return (int)sizeof(float) * (32 * (l.K0 > l.FP ? l.K0 : l.FP) + 128);
-}
-// persistent grid: up to two workgroups per CU (one wave per SIMD each), fewer when the LDS image does not fit twice
-static int ffn_grid(const brief_ffn_desc &d, int64_t n)
-{
-    const int64_t tiles = (n + 31) / 32;
-    const int by_lds = (160 * 1024) / ffn_lds_bytes(d);
-    const int64_t cap = (int64_t)kCUs * (by_lds < 2 ? (by_lds > 0 ? by_lds : 1) : 2);
-    return (int)(tiles < cap ? tiles : cap);
-}
-static const int64_t kFfnLossParts = 4096;      // >= any ffn_grid
-struct FfnWs { int64_t npad, H, D, EMB, G, lpart, slabs, total, chunk; int nsplit, waves; };
-static void ffn_wgrad_layer_shape(const brief_ffn_desc &d, int l, int &arows, int &brows)
-{
-    const FfnLayout lay = ffn_layout(d);
-    arows = l == d.layers - 1 ? d.cout : d.features;
-    brows = l == 0 ? lay.K0 : d.features;
-}
-static FfnWs ffn_ws_layout(const brief_ffn_desc &d, int64_t n)
-{
-    const FfnLayout lay = ffn_layout(d);
-    FfnWs w;
-    w.npad = (n + 31) / 32 * 32;
-    const int64_t plane = (int64_t)lay.FP * w.npad;
-    w.H = 0;
-    w.D = w.H + (int64_t)(d.layers - 1) * plane;
-    w.EMB = w.D + (int64_t)(d.layers - 1) * plane;
-    w.G = w.EMB + (int64_t)lay.K0 * w.npad;
-    w.lpart = w.G + 4 * w.npad;
-    w.slabs = w.lpart + kFfnLossParts;
-    w.waves = 0;
-    for (int l = 0; l < d.layers; ++l) {
-        int ar, br;
-        ffn_wgrad_layer_shape(d, l, ar, br);
-        w.waves += ((ar + 63) / 64) * ((br + 63) / 64);
-    }
-    const int64_t wgs = (w.waves + 3) / 4;
-    int64_t ns = (8 * (int64_t)kCUs + wgs - 1) / wgs;      // K-splits: about eight workgroups per CU (the latency of the plane loads needs waves in flight)
-    if (ns > 64) ns = 64;
-    if (ns > w.npad / 256) ns = w.npad / 256;
-    if (ns < 1) ns = 1;
-    w.chunk = (w.npad / ns + 31) / 32 * 32;
-    w.nsplit = (int)((w.npad + w.chunk - 1) / w.chunk);
-    const int64_t mlp = ffn_canon_count(d) - ffn_canon_w0(d);
-    w.total = w.slabs + (int64_t)w.nsplit * mlp;
-    return w;
-}
-
-template <bool TRAIN, bool BOX>
-static int launch_ffn_fwd(const FfnArgs &fa, int grid, hipStream_t st)
-{
-    const int mtw = (fa.nt + 3) / 4;
-    const int lds = ffn_lds_bytes(fa.d);
-    const void *fn = nullptr;
-    switch (mtw) {
-#define FFN_CASE(M) case M: fn = (const void *)k_ffn_fwd<M, TRAIN, BOX>; break;
-        FFN_CASE(1) FFN_CASE(2) FFN_CASE(3) FFN_CASE(4) FFN_CASE(5) FFN_CASE(6) FFN_CASE(7) FFN_CASE(8)
-#undef FFN_CASE
-        default: return fail(BRIEF_ERR_INVALID, "FFN: features must be 1..1024 on the fused path");
-    }
-    if (int rc = dev_attr_once(fn, lds)) return rc;
-    switch (mtw) {
-#define FFN_CASE(M) case M: hipLaunchKernelGGL((k_ffn_fwd<M, TRAIN, BOX>), dim3(grid), dim3(256), lds, st, fa); break;
-        FFN_CASE(1) FFN_CASE(2) FFN_CASE(3) FFN_CASE(4) FFN_CASE(5) FFN_CASE(6) FFN_CASE(7) FFN_CASE(8)
-#undef FFN_CASE
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-static void ffn_forward_args(FfnArgs &fa, const brief_ffn_desc *d, const float *packed, int64_t n, void *out, int out_kind,
-                             float scale_min, float scale_max, double vmin, double vmax)
-{
-    memset(&fa, 0, sizeof(fa));
-    const FfnLayout lay = ffn_layout(*d);
-    fa.d = *d; fa.nt = lay.nt; fa.EP = lay.EP; fa.pk = packed;
-    fa.n = n; fa.npad = (n + 31) / 32 * 32;
-    fa.out = out; fa.out_kind = out_kind;
-    fa.scale_min = scale_min;
-    fa.den = (float)((double)scale_max - (double)scale_min);
-    fa.span = (float)(vmax - vmin);
-    fa.vmin = (float)vmin;
-}
-
-struct FfnUpdate { OptimScalars opt; float *params, *s1, *s2, *pk; };
-
-static int ffn_train_impl(const brief_ffn_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
-                          int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
-                          void *workspace, int64_t workspace_bytes, void *stream, const FfnUpdate *upd)
-{
-    if (int rc = check_ffn_desc(d)) return rc;
-    brief_siren_desc sd;      // check_batch reads cin only
-    memset(&sd, 0, sizeof(sd));
-    sd.cin = d->cin;
-    if (int rc = check_batch(&sd, grid, batch, true)) return rc;
-    if (!packed || !grads || !loss_out || !workspace) return fail(BRIEF_ERR_INVALID, "null buffer");
-    if (loss_kind < BRIEF_LOSS_L2 || loss_kind > BRIEF_LOSS_EXTERNAL) return fail(BRIEF_ERR_INVALID, "bad loss_kind");
-    const FfnWs w = ffn_ws_layout(*d, batch->n);
-    if (workspace_bytes < w.total * (int64_t)sizeof(float)) return fail(BRIEF_ERR_WORKSPACE, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    float *ws = (float *)workspace;
-    const FfnLayout lay = ffn_layout(*d);
-    FfnArgs fa;
-    ffn_forward_args(fa, d, packed, batch->n, nullptr, 0, 0.f, 1.f, 0.0, 1.0);
-    fa.coords = batch->coords; fa.targets = batch->targets; fa.weights = batch->weights;
-    fa.idx = batch->idx; fa.offset = batch->offset;
-    if (!batch->idx && batch->rng_pop > 0) { fa.rng_pop = (uint64_t)batch->rng_pop; fa.rng_seed = batch->rng_seed; fa.rng_step = batch->rng_step; }
-    fill_grid(fa.grid, grid);
-    fa.loss_kind = loss_kind; fa.thr = thr; fa.beta = beta;
-    fa.inv_count = (float)(1.0 / ((double)batch->n * d->cout));
-    fa.H = ws + w.H; fa.D = ws + w.D; fa.EMB = ws + w.EMB; fa.G = ws + w.G; fa.lpart = ws + w.lpart;
-    fa.npad = w.npad; fa.yhat_out = yhat_out;
-    const int grid1 = ffn_grid(*d, batch->n);
-    const bool prof = prof_live();
-    hipEvent_t *pev = prof ? dev_state()->prof_ev : nullptr;
-    if (prof) HIP_TRY(hipEventRecord(pev[2 * g_prof_n], st));
-    if (int rc = launch_ffn_fwd<true, false>(fa, grid1, st)) return rc;
-    if (prof) { HIP_TRY(hipEventRecord(pev[2 * g_prof_n + 1], st)); ++g_prof_n; }
-    // weight gradients, at most FFN_WGRAD_LAYERS layers per launch
-    const int64_t bv = ffn_canon_w0(*d), mlp = ffn_canon_count(*d) - bv;
-    const int64_t plane = (int64_t)lay.FP * w.npad;
-    for (int l0 = 0; l0 < d->layers; l0 += FFN_WGRAD_LAYERS) {
-        FfnWgradArgs wa;
-        memset(&wa, 0, sizeof(wa));
-        wa.EP = lay.EP; wa.E = d->embsize; wa.npad = w.npad; wa.chunk = w.chunk; wa.mlp = mlp; wa.slabs = ws + w.slabs;
-        int waves = 0;
-        for (int l = l0; l < d->layers && l < l0 + FFN_WGRAD_LAYERS; ++l) {
-            FfnWgradLayer &Ly = wa.lay[l - l0];
-            ffn_wgrad_layer_shape(*d, l, Ly.arows, Ly.brows);
-            Ly.mb = (Ly.arows + 63) / 64; Ly.nb = (Ly.brows + 63) / 64;
-            Ly.wave_begin = waves;
-            waves += Ly.mb * Ly.nb;
-            if (l == d->layers - 1) {
-                Ly.A = ws + w.G;
-                Ly.B = ws + w.H + (int64_t)(d->layers - 2) * plane;
-                Ly.w_off = ffn_canon_head(*d) - bv; Ly.ldw = d->features;
-                Ly.b_off = Ly.w_off + (int64_t)d->cout * d->features;
-            } else if (l == 0) {
-                Ly.A = ws + w.D; Ly.B = ws + w.EMB; Ly.emb = 1;
-                Ly.w_off = 0; Ly.ldw = 2 * d->embsize;
-                Ly.b_off = 2 * (int64_t)d->embsize * d->features;
-            } else {
-                Ly.A = ws + w.D + (int64_t)l * plane;
-                Ly.B = ws + w.H + (int64_t)(l - 1) * plane;
-                Ly.w_off = ffn_canon_hidden(*d, l) - bv; Ly.ldw = d->features;
-                Ly.b_off = Ly.w_off + (int64_t)d->features * d->features;
-            }
-        }
-        wa.nlayers = (d->layers - l0) < FFN_WGRAD_LAYERS ? (d->layers - l0) : FFN_WGRAD_LAYERS;
-        wa.waves = waves;
-        hipLaunchKernelGGL(k_ffn_wgrad, dim3((unsigned)((waves + 3) / 4), (unsigned)w.nsplit), dim3(256), 0, st, wa);
-        HIP_TRY(hipGetLastError());
-    }
-    const int64_t nred = mlp > bv ? mlp : bv;
-    OptimScalars o;
-    memset(&o, 0, sizeof(o));
-    if (upd) o = upd->opt;
-    hipLaunchKernelGGL(k_ffn_reduce, dim3((unsigned)((nred + 255) / 256)), dim3(256), 0, st, (const float *)(ws + w.slabs), w.nsplit, mlp, bv, grads,
-                       (const float *)(ws + w.lpart), grid1, loss_kind == BRIEF_LOSS_EXTERNAL ? 0.f : fa.inv_count, loss_out,
-                       upd ? 1 : 0, o, upd ? upd->params : nullptr, upd ? upd->s1 : nullptr, upd ? upd->s2 : nullptr);
-    HIP_TRY(hipGetLastError());
-    if (upd) {
-        hipLaunchKernelGGL(k_ffn_repack, dim3((unsigned)((lay.total + 255) / 256)), dim3(256), 0, st, *d, (const float *)upd->params, upd->pk);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
-}
-
-extern "C" {
-
-int64_t brief_ffn_param_count(const brief_ffn_desc *d) { return check_ffn_desc(d) ? -1 : ffn_canon_count(*d); }
-int64_t brief_ffn_packed_count(const brief_ffn_desc *d) { return check_ffn_desc(d) ? -1 : ffn_layout(*d).total; }
-int64_t brief_ffn_train_workspace_bytes(const brief_ffn_desc *d, int64_t n)
-{
-    if (check_ffn_desc(d)) return -1;
-    if (n < 1) { fail(BRIEF_ERR_INVALID, "empty batch"); return -1; }
-    return ffn_ws_layout(*d, n).total * (int64_t)sizeof(float);
-}
-
-int brief_ffn_repack(const brief_ffn_desc *d, const float *params, float *packed, void *stream)
-{
-    if (int rc = check_ffn_desc(d)) return rc;
-    if (!params || !packed) return fail(BRIEF_ERR_INVALID, "null buffer");
-    const int64_t total = ffn_layout(*d).total;
-    hipLaunchKernelGGL(k_ffn_repack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *d, params, packed);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int brief_ffn_forward(const brief_ffn_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
-                      void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream)
-{
-    if (int rc = check_ffn_desc(d)) return rc;
-    brief_siren_desc sd;
-    memset(&sd, 0, sizeof(sd));
-    sd.cin = d->cin;
-    if (int rc = check_batch(&sd, grid, batch, false)) return rc;
-    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
-    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
-    FfnArgs fa;
-    ffn_forward_args(fa, d, packed, batch->n, out, out_kind, scale_min, scale_max, vmin, vmax);
-    fa.coords = batch->coords; fa.idx = batch->idx; fa.offset = batch->offset;
-    fill_grid(fa.grid, grid);
-    return launch_ffn_fwd<false, false>(fa, ffn_grid(*d, batch->n), (hipStream_t)stream);
-}
-
-int brief_ffn_forward_box(const brief_ffn_desc *d, const float *packed, const brief_grid_box *box, int64_t offset, int64_t n,
-                          void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream)
-{
-    if (int rc = check_ffn_desc(d)) return rc;
-    brief_siren_desc sd;
-    memset(&sd, 0, sizeof(sd));
-    sd.cin = d->cin;
-    int64_t voxels = 0;
-    if (int rc = check_box(&sd, box, &voxels)) return rc;
-    if (n < 1) return fail(BRIEF_ERR_INVALID, "empty batch");
-    if (offset < 0 || offset > voxels - n) return fail(BRIEF_ERR_INVALID, "offset + n exceeds the box's voxel count");
-    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
-    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
-    FfnArgs fa;
-    ffn_forward_args(fa, d, packed, n, out, out_kind, scale_min, scale_max, vmin, vmax);
-    fa.offset = offset;
-    fill_grid(fa.grid, &box->grid);
-    double total = 1.0;
-    for (int a = 0; a < 3; ++a) {
-        const bool on = a < box->grid.ndim;
-        fa.box.start[a] = on ? box->start[a] : 0;
-        fa.box.step[a] = on ? box->step[a] : 1;
-        fa.box.extent[a] = on ? box->extent[a] : 1;
-        fa.box.magic[a] = ~(uint64_t)0 / (uint64_t)fa.box.extent[a] + 1;
-        total *= (double)fa.box.extent[a];
-    }
-    fa.box.fast = total < 4294967296.0;
-    return launch_ffn_fwd<false, true>(fa, ffn_grid(*d, n), (hipStream_t)stream);
-}
-
-int brief_ffn_train_step(const brief_ffn_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
-                         int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
-                         void *workspace, int64_t workspace_bytes, void *stream)
-{
-    return ffn_train_impl(d, packed, grid, batch, loss_kind, thr, beta, grads, loss_out, yhat_out, workspace, workspace_bytes, stream, nullptr);
-}
-
-int brief_ffn_fit(const brief_ffn_fit_job *j, int64_t steps, void *stream)
-{
-    if (!j) return fail(BRIEF_ERR_INVALID, "null job");
-    if (int rc = check_ffn_desc(&j->desc)) return rc;
-    if (steps < 0) return fail(BRIEF_ERR_INVALID, "bad step count");
-    if (j->batch.idx && j->idx_stride <= 0) return fail(BRIEF_ERR_INVALID, "brief_ffn_fit needs idx_stride > 0 with batch.idx (one index set per step)");
-    if (j->batch.idx && j->idx_stride < j->batch.n) return fail(BRIEF_ERR_INVALID, "idx_stride is smaller than the batch");
-    if (!j->params || !j->packed || !j->grads || !j->loss_out || !j->workspace) return fail(BRIEF_ERR_INVALID, "null buffer");
-    if (j->t0 < 0) return fail(BRIEF_ERR_INVALID, "bad step count");
-    if (j->n_milestones < 0 || (j->n_milestones > 0 && !j->milestones)) return fail(BRIEF_ERR_INVALID, "bad lr milestones");
-    if (j->optim_kind < BRIEF_OPT_ADAMAX || j->optim_kind > BRIEF_OPT_SGD) return fail(BRIEF_ERR_INVALID, "bad optimizer kind");
-    if (j->optim_kind != BRIEF_OPT_SGD && (!j->state1 || !j->state2)) return fail(BRIEF_ERR_INVALID, "optimizer state required");
-    hipStream_t st = (hipStream_t)stream;
-    // the schedule fields mean what they mean in brief_fit_job: brief_siren_fit's rule (fit_job_lr) evaluates them
-    brief_fit_job sched;
-    memset(&sched, 0, sizeof(sched));
-    sched.milestones = j->milestones; sched.n_milestones = j->n_milestones; sched.gamma = j->gamma; sched.t0 = j->t0;
-    sched.lr_table = j->lr_table;
-    double lr = j->lr;
-    for (int64_t k = 0; k < steps; ++k) {
-        const int64_t t = j->t0 + 1 + k;
-        fit_job_lr(&sched, t, k, &lr);
-        brief_batch_desc b = j->batch;
-        if (b.idx) b.idx = b.idx + k * j->idx_stride;
-        else if (b.rng_pop > 0) b.rng_step = (uint64_t)t;
-        FfnUpdate up;
-        up.opt = optim_scalars(j->optim_kind, lr, j->beta1_table ? j->beta1_table[k] : j->beta1, j->beta2, j->eps, t);
-        up.params = j->params; up.s1 = j->state1; up.s2 = j->state2; up.pk = j->packed;
-        if (int rc = ffn_train_impl(&j->desc, j->packed, &j->grid, &b, j->loss_kind, j->thr, j->beta, j->grads,
-                                    j->loss_log ? j->loss_log + k : j->loss_out, nullptr, j->workspace, j->workspace_bytes, (void *)st, &up))
-            return rc;
-    }
-    if (j->loss_log && steps > 0)
-        HIP_TRY(hipMemcpyAsync(j->loss_out, j->loss_log + steps - 1, sizeof(float), hipMemcpyDeviceToDevice, st));
-    return 0;
-}
-
-}   // extern "C"
-
-// =============================================================================================
-// NeRF (positional-encoding network, brief_nerf.inc): train step = k_nerf_fwd<TRAIN> + k_nerf_wgrad + k_ffn_reduce (bv = 0)
-// (+ k_nerf_repack after an update)
-static int check_nerf_desc(const brief_nerf_desc *d)
-{
-    if (!d) return fail(BRIEF_ERR_INVALID, "null desc");
-    if (d->cin != 2 && d->cin != 3) return fail(BRIEF_ERR_INVALID, "NeRF: coords_channel must be 2 or 3");
-    if (d->cout < 1 || d->cout > 4) return fail(BRIEF_ERR_INVALID, "NeRF: data_channel must be 1..4");
-    if (d->skip != 0 && d->skip != 1) return fail(BRIEF_ERR_INVALID, "NeRF: skip must be 0 or 1");
-    if (d->layers < 2) return fail(BRIEF_ERR_INVALID, "NeRF: layers must be >= 2");
-    if (d->skip && d->layers < 3) return fail(BRIEF_ERR_INVALID, "NeRF: layers must be >= 3 with skip");
-    if (d->features < 1 || d->features > 1024) return fail(BRIEF_ERR_INVALID, "NeRF: features must be 1..1024 on the fused path");
-    if (d->frequencies < 0 || d->frequencies > 16) return fail(BRIEF_ERR_INVALID, "NeRF: frequencies must be 0..16 on the fused path");
-    return 0;
-}
-
-static int nerf_lds_bytes(const brief_nerf_desc &d)
-{
-    const NerfLayout l = nerf_layout(d);
-    return (int)sizeof(float) * (32 * (l.DP + l.FP) + 128);
-}
-// persistent grid: up to two workgroups per CU (one wave per SIMD each), fewer when the LDS image does not fit twice
-static int nerf_grid(const brief_nerf_desc &d, int64_t n)
-{
-    const int64_t tiles = (n + 31) / 32;
-    const int by_lds = (160 * 1024) / nerf_lds_bytes(d);
-    const int64_t cap = (int64_t)kCUs * (by_lds < 2 ? (by_lds > 0 ? by_lds : 1) : 2);
-    return (int)(tiles < cap ? tiles : cap);
-}
-struct NerfWs { int64_t npad, H, D, ENC, G, lpart, slabs, total, chunk; int nsplit, waves; };
-// weight-gradient block i (0 .. nerf_wgrad_count - 1) of the net, in canonical order: W0 | per hidden layer (the skip layer's encoding
-// columns first) | head; planes at the workspace offsets of w (ws == nullptr: shapes only), wave_begin left to the caller
-static int nerf_wgrad_count(const brief_nerf_desc &d) { return d.layers + (d.skip ? 1 : 0); }
-static NerfWgradBlock nerf_wgrad_block(const brief_nerf_desc &d, const NerfWs &w, float *ws, int i)
-{
-    const NerfLayout lay = nerf_layout(d);
-    const int F = d.features, L = d.layers;
-    const int64_t plane = (int64_t)lay.FP * w.npad;
-    int64_t A, B, w_off, b_off;
-    int arows = F, brows = F, ldw = F;
-    if (i == 0) {
-        A = w.D; B = w.ENC; brows = lay.d; ldw = lay.d; w_off = 0; b_off = (int64_t)F * lay.d;
-    } else if (i == nerf_wgrad_count(d) - 1) {
-        A = w.G; B = w.H + (int64_t)(L - 2) * plane; arows = d.cout;
-        w_off = nerf_canon_head(d); b_off = w_off + (int64_t)d.cout * F;
-    } else {
-        const bool past = lay.sl && i > lay.sl;                        // block index i: layer i, or i - 1 past the skip layer's extra block
-        const int l = past ? i - 1 : i;
-        const bool enc = lay.sl && i == lay.sl;                        // the skip layer's encoding columns
-        const int coff = l == lay.sl ? lay.d : 0;
-        const int64_t c = nerf_canon_hidden(d, l);
-        A = w.D + (int64_t)l * plane; ldw = F + coff;
-        if (enc) { B = w.ENC; brows = lay.d; w_off = c; b_off = -1; }
-        else { B = w.H + (int64_t)(l - 1) * plane; w_off = c + coff; b_off = c + (int64_t)F * ldw; }
-    }
-    NerfWgradBlock b;
-    memset(&b, 0, sizeof(b));
-    b.A = ws ? ws + A : nullptr; b.B = ws ? ws + B : nullptr;
-    b.arows = arows; b.brows = brows;
-    b.mb = (arows + 63) / 64; b.nb = (brows + 63) / 64;
-    b.w_off = w_off; b.b_off = b_off; b.ldw = ldw;
-    return b;
-}
-static NerfWs nerf_ws_layout(const brief_nerf_desc &d, int64_t n)
-{
-    const NerfLayout lay = nerf_layout(d);
-    NerfWs w;
-    w.npad = (n + 31) / 32 * 32;
-    const int64_t plane = (int64_t)lay.FP * w.npad;
-    w.H = 0;
-    w.D = w.H + (int64_t)(d.layers - 1) * plane;
-    w.ENC = w.D + (int64_t)(d.layers - 1) * plane;
-    w.G = w.ENC + (int64_t)lay.DP * w.npad;
-    w.lpart = w.G + 4 * w.npad;
-    w.slabs = w.lpart + kFfnLossParts;
-    w.waves = 0;
-    for (int i = 0; i < nerf_wgrad_count(d); ++i) {
-        const NerfWgradBlock b = nerf_wgrad_block(d, w, nullptr, i);
-        w.waves += b.mb * b.nb;
-    }
-    const int64_t wgs = (w.waves + 3) / 4;
-    int64_t ns = (8 * (int64_t)kCUs + wgs - 1) / wgs;      // K-splits: about eight workgroups per CU (as k_ffn_wgrad)
-    if (ns > 64) ns = 64;
-    if (ns > w.npad / 256) ns = w.npad / 256;
-    if (ns < 1) ns = 1;
-    w.chunk = (w.npad / ns + 31) / 32 * 32;
-    w.nsplit = (int)((w.npad + w.chunk - 1) / w.chunk);
-    w.total = w.slabs + (int64_t)w.nsplit * nerf_canon_count(d);
-    return w;
-}
-
-template <bool TRAIN, bool BOX>
-static int launch_nerf_fwd(const NerfArgs &na, int grid, hipStream_t st)
-{
-    const int mtw = (na.nt + 3) / 4;
-    const int lds = nerf_lds_bytes(na.d);
-    const void *fn = nullptr;
-    switch (mtw) {
-#define NERF_CASE(M) case M: fn = (const void *)k_nerf_fwd<M, TRAIN, BOX>; break;
-        NERF_CASE(1) NERF_CASE(2) NERF_CASE(3) NERF_CASE(4) NERF_CASE(5) NERF_CASE(6) NERF_CASE(7) NERF_CASE(8)
-#undef NERF_CASE
-        default: return fail(BRIEF_ERR_INVALID, "NeRF: features must be 1..1024 on the fused path");
-    }
-    if (int rc = dev_attr_once(fn, lds)) return rc;
-    switch (mtw) {
-#define NERF_CASE(M) case M: hipLaunchKernelGGL((k_nerf_fwd<M, TRAIN, BOX>), dim3(grid), dim3(256), lds, st, na); break;
-        NERF_CASE(1) NERF_CASE(2) NERF_CASE(3) NERF_CASE(4) NERF_CASE(5) NERF_CASE(6) NERF_CASE(7) NERF_CASE(8)
-#undef NERF_CASE
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-static void nerf_forward_args(NerfArgs &na, const brief_nerf_desc *d, const float *packed, int64_t n, void *out, int out_kind,
-                              float scale_min, float scale_max, double vmin, double vmax)
-{
-    memset(&na, 0, sizeof(na));
-    const NerfLayout lay = nerf_layout(*d);
-    na.d = *d; na.nt = lay.nt; na.DP = lay.DP; na.pk = packed;
-    na.n = n; na.npad = (n + 31) / 32 * 32;
-    na.out = out; na.out_kind = out_kind;
-    na.scale_min = scale_min;
-    na.den = (float)((double)scale_max - (double)scale_min);
-    na.span = (float)(vmax - vmin);
-    na.vmin = (float)vmin;
-}
-
-static int nerf_train_impl(const brief_nerf_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
-                           int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
-                           void *workspace, int64_t workspace_bytes, void *stream, const FfnUpdate *upd)
-{
-    if (int rc = check_nerf_desc(d)) return rc;
-    brief_siren_desc sd;      // check_batch reads cin only
-    memset(&sd, 0, sizeof(sd));
-    sd.cin = d->cin;
-    if (int rc = check_batch(&sd, grid, batch, true)) return rc;
-    if (!packed || !grads || !loss_out || !workspace) return fail(BRIEF_ERR_INVALID, "null buffer");
-    if (loss_kind < BRIEF_LOSS_L2 || loss_kind > BRIEF_LOSS_EXTERNAL) return fail(BRIEF_ERR_INVALID, "bad loss_kind");
-    const NerfWs w = nerf_ws_layout(*d, batch->n);
-    if (workspace_bytes < w.total * (int64_t)sizeof(float)) return fail(BRIEF_ERR_WORKSPACE, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    float *ws = (float *)workspace;
-    const NerfLayout lay = nerf_layout(*d);
-    NerfArgs na;
-    nerf_forward_args(na, d, packed, batch->n, nullptr, 0, 0.f, 1.f, 0.0, 1.0);
-    na.coords = batch->coords; na.targets = batch->targets; na.weights = batch->weights;
-    na.idx = batch->idx; na.offset = batch->offset;
-    if (!batch->idx && batch->rng_pop > 0) { na.rng_pop = (uint64_t)batch->rng_pop; na.rng_seed = batch->rng_seed; na.rng_step = batch->rng_step; }
-    fill_grid(na.grid, grid);
-    na.loss_kind = loss_kind; na.thr = thr; na.beta = beta;
-    na.inv_count = (float)(1.0 / ((double)batch->n * d->cout));
-    na.H = ws + w.H; na.D = ws + w.D; na.ENC = ws + w.ENC; na.G = ws + w.G; na.lpart = ws + w.lpart;
-    na.npad = w.npad; na.yhat_out = yhat_out;
-    const int grid1 = nerf_grid(*d, batch->n);
-    const bool prof = prof_live();
-    hipEvent_t *pev = prof ? dev_state()->prof_ev : nullptr;
-    if (prof) HIP_TRY(hipEventRecord(pev[2 * g_prof_n], st));
-    if (int rc = launch_nerf_fwd<true, false>(na, grid1, st)) return rc;
-    if (prof) { HIP_TRY(hipEventRecord(pev[2 * g_prof_n + 1], st)); ++g_prof_n; }
-    // weight gradients, at most NERF_WGRAD_BLOCKS blocks per launch
-    const int64_t mlp = nerf_canon_count(*d);
-    const int nblocks = nerf_wgrad_count(*d);
-    for (int b0 = 0; b0 < nblocks; b0 += NERF_WGRAD_BLOCKS) {
-        NerfWgradArgs wa;
-        memset(&wa, 0, sizeof(wa));
-        wa.npad = w.npad; wa.chunk = w.chunk; wa.mlp = mlp; wa.slabs = ws + w.slabs;
-        wa.nblocks = (nblocks - b0) < NERF_WGRAD_BLOCKS ? (nblocks - b0) : NERF_WGRAD_BLOCKS;
-        int waves = 0;
-        for (int i = 0; i < wa.nblocks; ++i) {
-            wa.blk[i] = nerf_wgrad_block(*d, w, ws, b0 + i);
-            wa.blk[i].wave_begin = waves;
-            waves += wa.blk[i].mb * wa.blk[i].nb;
-        }
-        wa.waves = waves;
-        hipLaunchKernelGGL(k_nerf_wgrad, dim3((unsigned)((waves + 3) / 4), (unsigned)w.nsplit), dim3(256), 0, st, wa);
-        HIP_TRY(hipGetLastError());
-    }
-    OptimScalars o;
-    memset(&o, 0, sizeof(o));
-    if (upd) o = upd->opt;
-    hipLaunchKernelGGL(k_ffn_reduce, dim3((unsigned)((mlp + 255) / 256)), dim3(256), 0, st, (const float *)(ws + w.slabs), w.nsplit, mlp, (int64_t)0,
-                       grads, (const float *)(ws + w.lpart), grid1, loss_kind == BRIEF_LOSS_EXTERNAL ? 0.f : na.inv_count, loss_out,
-                       upd ? 1 : 0, o, upd ? upd->params : nullptr, upd ? upd->s1 : nullptr, upd ? upd->s2 : nullptr);
-    HIP_TRY(hipGetLastError());
-    if (upd) {
-        hipLaunchKernelGGL(k_nerf_repack, dim3((unsigned)((lay.total + 255) / 256)), dim3(256), 0, st, *d, (const float *)upd->params, upd->pk);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
-}
-
-extern "C" {
-
-int64_t brief_nerf_param_count(const brief_nerf_desc *d) { return check_nerf_desc(d) ? -1 : nerf_canon_count(*d); }
-int64_t brief_nerf_packed_count(const brief_nerf_desc *d) { return check_nerf_desc(d) ? -1 : nerf_layout(*d).total; }
-int64_t brief_nerf_train_workspace_bytes(const brief_nerf_desc *d, int64_t n)
-{
-    if (check_nerf_desc(d)) return -1;
-    if (n < 1) { fail(BRIEF_ERR_INVALID, "empty batch"); return -1; }
-    return nerf_ws_layout(*d, n).total * (int64_t)sizeof(float);
-}
-
-int brief_nerf_repack(const brief_nerf_desc *d, const float *params, float *packed, void *stream)
-{
-    if (int rc = check_nerf_desc(d)) return rc;
-    if (!params || !packed) return fail(BRIEF_ERR_INVALID, "null buffer");
-    const int64_t total = nerf_layout(*d).total;
-    hipLaunchKernelGGL(k_nerf_repack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *d, params, packed);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int brief_nerf_forward(const brief_nerf_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
-                       void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream)
-{
-    if (int rc = check_nerf_desc(d)) return rc;
-    brief_siren_desc sd;
-    memset(&sd, 0, sizeof(sd));
-    sd.cin = d->cin;
-    if (int rc = check_batch(&sd, grid, batch, false)) return rc;
-    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
-    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
-    NerfArgs na;
-    nerf_forward_args(na, d, packed, batch->n, out, out_kind, scale_min, scale_max, vmin, vmax);
-    na.coords = batch->coords; na.idx = batch->idx; na.offset = batch->offset;
-    fill_grid(na.grid, grid);
-    return launch_nerf_fwd<false, false>(na, nerf_grid(*d, batch->n), (hipStream_t)stream);
-}
-
-int brief_nerf_forward_box(const brief_nerf_desc *d, const float *packed, const brief_grid_box *box, int64_t offset, int64_t n,
-                           void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream)
-{
-    if (int rc = check_nerf_desc(d)) return rc;
-    brief_siren_desc sd;
-    memset(&sd, 0, sizeof(sd));
-    sd.cin = d->cin;
-    int64_t voxels = 0;
-    if (int rc = check_box(&sd, box, &voxels)) return rc;
-    if (n < 1) return fail(BRIEF_ERR_INVALID, "empty batch");
-    if (offset < 0 || offset > voxels - n) return fail(BRIEF_ERR_INVALID, "offset + n exceeds the box's voxel count");
-    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
-    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
-    NerfArgs na;
-    nerf_forward_args(na, d, packed, n, out, out_kind, scale_min, scale_max, vmin, vmax);
-    na.offset = offset;
-    fill_grid(na.grid, &box->grid);
-    double total = 1.0;
-    for (int a = 0; a < 3; ++a) {
-        const bool on = a < box->grid.ndim;
-        na.box.start[a] = on ? box->start[a] : 0;
-        na.box.step[a] = on ? box->step[a] : 1;
-        na.box.extent[a] = on ? box->extent[a] : 1;
-        na.box.magic[a] = ~(uint64_t)0 / (uint64_t)na.box.extent[a] + 1;
-        total *= (double)na.box.extent[a];
-    }
-    na.box.fast = total < 4294967296.0;
-    return launch_nerf_fwd<false, true>(na, nerf_grid(*d, n), (hipStream_t)stream);
-}
-
-int brief_nerf_train_step(const brief_nerf_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
-                          int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
-                          void *workspace, int64_t workspace_bytes, void *stream)
-{
-    return nerf_train_impl(d, packed, grid, batch, loss_kind, thr, beta, grads, loss_out, yhat_out, workspace, workspace_bytes, stream, nullptr);
-}
-
-int brief_nerf_fit(const brief_nerf_fit_job *j, int64_t steps, void *stream)
-{
-    if (!j) return fail(BRIEF_ERR_INVALID, "null job");
-    if (int rc = check_nerf_desc(&j->desc)) return rc;
-    if (steps < 0) return fail(BRIEF_ERR_INVALID, "bad step count");
-    if (j->batch.idx && j->idx_stride <= 0) return fail(BRIEF_ERR_INVALID, "brief_nerf_fit needs idx_stride > 0 with batch.idx (one index set per step)");
-    if (j->batch.idx && j->idx_stride < j->batch.n) return fail(BRIEF_ERR_INVALID, "idx_stride is smaller than the batch");
-    if (!j->params || !j->packed || !j->grads || !j->loss_out || !j->workspace) return fail(BRIEF_ERR_INVALID, "null buffer");
-    if (j->t0 < 0) return fail(BRIEF_ERR_INVALID, "bad step count");
-    if (j->n_milestones < 0 || (j->n_milestones > 0 && !j->milestones)) return fail(BRIEF_ERR_INVALID, "bad lr milestones");
-    if (j->optim_kind < BRIEF_OPT_ADAMAX || j->optim_kind > BRIEF_OPT_SGD) return fail(BRIEF_ERR_INVALID, "bad optimizer kind");
-    if (j->optim_kind != BRIEF_OPT_SGD && (!j->state1 || !j->state2)) return fail(BRIEF_ERR_INVALID, "optimizer state required");
-    hipStream_t st = (hipStream_t)stream;
-    // the schedule fields mean what they mean in brief_fit_job: brief_siren_fit's rule (fit_job_lr) evaluates them
-    brief_fit_job sched;
-    memset(&sched, 0, sizeof(sched));
-    sched.milestones = j->milestones; sched.n_milestones = j->n_milestones; sched.gamma = j->gamma; sched.t0 = j->t0;
-    sched.lr_table = j->lr_table;
-    double lr = j->lr;
-    for (int64_t k = 0; k < steps; ++k) {
-        const int64_t t = j->t0 + 1 + k;
-        fit_job_lr(&sched, t, k, &lr);
-        brief_batch_desc b = j->batch;
-        if (b.idx) b.idx = b.idx + k * j->idx_stride;
-        else if (b.rng_pop > 0) b.rng_step = (uint64_t)t;
-        FfnUpdate up;
-        up.opt = optim_scalars(j->optim_kind, lr, j->beta1_table ? j->beta1_table[k] : j->beta1, j->beta2, j->eps, t);
-        up.params = j->params; up.s1 = j->state1; up.s2 = j->state2; up.pk = j->packed;
-        if (int rc = nerf_train_impl(&j->desc, j->packed, &j->grid, &b, j->loss_kind, j->thr, j->beta, j->grads,
-                                     j->loss_log ? j->loss_log + k : j->loss_out, nullptr, j->workspace, j->workspace_bytes, (void *)st, &up))
-            return rc;
-    }
-    if (j->loss_log && steps > 0)
-        HIP_TRY(hipMemcpyAsync(j->loss_out, j->loss_log + steps - 1, sizeof(float), hipMemcpyDeviceToDevice, st));
-    return 0;
-}
-
-}   // extern "C"
-
-// =============================================================================================
-// MFN (multiplicative filter networks, brief_mfn.inc): train step = k_mfn_fwd<TRAIN> + k_mfn_wgrad + k_ffn_reduce (bv = 0)
-// (+ k_mfn_repack after an update)
-static int check_mfn_desc(const brief_mfn_desc *d)
-{
-    if (!d) return fail(BRIEF_ERR_INVALID, "null desc");
-    if (d->cin != 2 && d->cin != 3) return fail(BRIEF_ERR_INVALID, "MFN: coords_channel must be 2 or 3");
-    if (d->cout < 1 || d->cout > 4) return fail(BRIEF_ERR_INVALID, "MFN: data_channel must be 1..4");
-    if (d->layers < 2) return fail(BRIEF_ERR_INVALID, "MFN: layers must be >= 2");
-    if (d->features < 1 || d->features > 1024) return fail(BRIEF_ERR_INVALID, "MFN: features must be 1..1024 on the fused path");
-    if (d->filter != 0 && d->filter != 1) return fail(BRIEF_ERR_INVALID, "MFN: filter must be 0 (Fourier) or 1 (Gabor)");
-    if (d->output_act != 0 && d->output_act != 1) return fail(BRIEF_ERR_INVALID, "MFN: output_act must be 0 or 1");
-    return 0;
-}
-
-static int mfn_lds_bytes(const brief_mfn_desc &d)
-{
-    const MfnLayout l = mfn_layout(d);
-    return (int)sizeof(float) * (32 * l.FP + 128);
-}
-// persistent grid: up to two workgroups per CU (one wave per SIMD each), fewer when the LDS image does not fit twice
-static int mfn_grid(const brief_mfn_desc &d, int64_t n)
-{
-    const int64_t tiles = (n + 31) / 32;
-    const int by_lds = (160 * 1024) / mfn_lds_bytes(d);
-    const int64_t cap = (int64_t)kCUs * (by_lds < 2 ? (by_lds > 0 ? by_lds : 1) : 2);
-    return (int)(tiles < cap ? tiles : cap);
-}
-struct MfnWs { int64_t npad, Z, U, DU, DA, Q, XP, G, lpart, slabs, total, chunk; int nsplit, waves; };
-// weight-gradient block i (0 .. mfn_wgrad_count - 1) of the net: hidden layers | head | per filter (W / b, then Gabor's mu / gamma);
-// planes at the workspace offsets of w (ws == nullptr: shapes only), wave_begin left to the caller
-static int mfn_wgrad_count(const brief_mfn_desc &d) { return d.layers - 1 + (d.layers - 1) * (d.filter ? 2 : 1); }
-static MfnWgradBlock mfn_wgrad_block(const brief_mfn_desc &d, const MfnWs &w, float *ws, const float *packed, int i)
-{
-    const MfnLayout lay = mfn_layout(d);
-    const int F = d.features, L = d.layers, cin = d.cin;
-    const int64_t plane = (int64_t)lay.FP * w.npad;
-    int64_t A, B, w_off, b_off;
-    int arows = F, brows = F, ldw = F, gabor = 0;
-    const float *fg = nullptr;
-    if (i < L - 2) {                                                   // hidden layer l = i + 1
-        const int l = i + 1;
-        A = w.DU + (int64_t)(l - 1) * plane; B = w.Z + (int64_t)(l - 1) * plane;
-        w_off = mfn_canon_hidden(d, l); b_off = w_off + (int64_t)F * F;
-    } else if (i == L - 2) {                                           // head
-        A = w.G; B = w.Z + (int64_t)(L - 2) * plane; arows = d.cout;
-        w_off = mfn_canon_head(d); b_off = w_off + (int64_t)d.cout * F;
-    } else {
-        const int per = d.filter ? 2 : 1, j = i - (L - 1), fi = j / per;
-        B = w.XP; ldw = cin;
-        if (j % per == 0) {                                            // filter fi: Wf / bf
-            A = w.DA + (int64_t)fi * plane; brows = cin;
-            w_off = mfn_canon_filter_w(d, fi); b_off = w_off + (int64_t)F * cin;
-        } else {                                                       // Gabor filter fi: mu / gamma
-            A = w.Q + (int64_t)fi * plane; brows = cin + 2;
-            w_off = mfn_canon_filter(d, fi); b_off = -1; gabor = 1;
-            fg = packed ? packed + lay.filt + (int64_t)fi * lay.filt_stride + 4 * (int64_t)lay.FP : nullptr;
-        }
-    }
-    MfnWgradBlock b;
-    memset(&b, 0, sizeof(b));
-    b.A = ws ? ws + A : nullptr; b.B = ws ? ws + B : nullptr;
-    b.arows = arows; b.brows = brows;
-    b.mb = (arows + 63) / 64; b.nb = (brows + 63) / 64;
-    b.w_off = w_off; b.b_off = b_off; b.ldw = ldw;
-    b.gabor = gabor; b.fg = fg;
-    return b;
-}
-static MfnWs mfn_ws_layout(const brief_mfn_desc &d, int64_t n)
-{
-    const MfnLayout lay = mfn_layout(d);
-    MfnWs w;
-    w.npad = (n + 31) / 32 * 32;
-    const int64_t plane = (int64_t)lay.FP * w.npad;
-    const int nf = d.layers - 1, nh = d.layers - 2;
-    w.Z = 0;
-    w.U = w.Z + nf * plane;
-    w.DU = w.U + nh * plane;
-    w.DA = w.DU + nh * plane;
-    w.Q = w.DA + nf * plane;
-    w.XP = w.Q + (d.filter ? nf : 0) * plane;
-    w.G = w.XP + 5 * w.npad;
-    w.lpart = w.G + 4 * w.npad;
-    w.slabs = w.lpart + kFfnLossParts;
-    w.waves = 0;
-    for (int i = 0; i < mfn_wgrad_count(d); ++i) {
-        const MfnWgradBlock b = mfn_wgrad_block(d, w, nullptr, nullptr, i);
-        w.waves += b.mb * b.nb;
-    }
-    const int64_t wgs = (w.waves + 3) / 4;
-    int64_t ns = (8 * (int64_t)kCUs + wgs - 1) / wgs;      // K-splits: about eight workgroups per CU (as k_ffn_wgrad)
-    if (ns > 64) ns = 64;
-    if (ns > w.npad / 256) ns = w.npad / 256;
-    if (ns < 1) ns = 1;
-    w.chunk = (w.npad / ns + 31) / 32 * 32;
-    w.nsplit = (int)((w.npad + w.chunk - 1) / w.chunk);
-    w.total = w.slabs + (int64_t)w.nsplit * mfn_canon_count(d);
-    return w;
-}
-
-template <bool TRAIN, bool BOX, bool GABOR>
-static int launch_mfn_fwd_kind(const MfnArgs &ma, int grid, hipStream_t st)
-{
-    const int mtw = (ma.nt + 3) / 4;
-    const int lds = mfn_lds_bytes(ma.d);
-    const void *fn = nullptr;
-    switch (mtw) {
-#define MFN_CASE(M) case M: fn = (const void *)k_mfn_fwd<M, TRAIN, BOX, GABOR>; break;
-        MFN_CASE(1) MFN_CASE(2) MFN_CASE(3) MFN_CASE(4) MFN_CASE(5) MFN_CASE(6) MFN_CASE(7) MFN_CASE(8)
-#undef MFN_CASE
-        default: return fail(BRIEF_ERR_INVALID, "MFN: features must be 1..1024 on the fused path");
-    }
-    if (int rc = dev_attr_once(fn, lds)) return rc;
-    switch (mtw) {
-#define MFN_CASE(M) case M: hipLaunchKernelGGL((k_mfn_fwd<M, TRAIN, BOX, GABOR>), dim3(grid), dim3(256), lds, st, ma); break;
-        MFN_CASE(1) MFN_CASE(2) MFN_CASE(3) MFN_CASE(4) MFN_CASE(5) MFN_CASE(6) MFN_CASE(7) MFN_CASE(8)
-#undef MFN_CASE
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-template <bool TRAIN, bool BOX>
-static int launch_mfn_fwd(const MfnArgs &ma, int grid, hipStream_t st)
-{
-    return ma.d.filter ? launch_mfn_fwd_kind<TRAIN, BOX, true>(ma, grid, st) : launch_mfn_fwd_kind<TRAIN, BOX, false>(ma, grid, st);
-}
-
-static void mfn_forward_args(MfnArgs &ma, const brief_mfn_desc *d, const float *packed, int64_t n, void *out, int out_kind,
-                             float scale_min, float scale_max, double vmin, double vmax)
-{
-    memset(&ma, 0, sizeof(ma));
-    const MfnLayout lay = mfn_layout(*d);
-    ma.d = *d; ma.nt = lay.nt; ma.pk = packed;
-    ma.n = n; ma.npad = (n + 31) / 32 * 32;
-    ma.out = out; ma.out_kind = out_kind;
-    ma.scale_min = scale_min;
-    ma.den = (float)((double)scale_max - (double)scale_min);
-    ma.span = (float)(vmax - vmin);
-    ma.vmin = (float)vmin;
-}
-
-static int mfn_train_impl(const brief_mfn_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
-                          int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
-                          void *workspace, int64_t workspace_bytes, void *stream, const FfnUpdate *upd)
-{
-    if (int rc = check_mfn_desc(d)) return rc;
-    brief_siren_desc sd;      // check_batch reads cin only
-    memset(&sd, 0, sizeof(sd));
-    sd.cin = d->cin;
-    if (int rc = check_batch(&sd, grid, batch, true)) return rc;
-    if (!packed || !grads || !loss_out || !workspace) return fail(BRIEF_ERR_INVALID, "null buffer");
-    if (loss_kind < BRIEF_LOSS_L2 || loss_kind > BRIEF_LOSS_EXTERNAL) return fail(BRIEF_ERR_INVALID, "bad loss_kind");
-    const MfnWs w = mfn_ws_layout(*d, batch->n);
-    if (workspace_bytes < w.total * (int64_t)sizeof(float)) return fail(BRIEF_ERR_WORKSPACE, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    float *ws = (float *)workspace;
-    const MfnLayout lay = mfn_layout(*d);
-    MfnArgs ma;
-    mfn_forward_args(ma, d, packed, batch->n, nullptr, 0, 0.f, 1.f, 0.0, 1.0);
-    ma.coords = batch->coords; ma.targets = batch->targets; ma.weights = batch->weights;
-    ma.idx = batch->idx; ma.offset = batch->offset;
-    if (!batch->idx && batch->rng_pop > 0) { ma.rng_pop = (uint64_t)batch->rng_pop; ma.rng_seed = batch->rng_seed; ma.rng_step = batch->rng_step; }
-    fill_grid(ma.grid, grid);
-    ma.loss_kind = loss_kind; ma.thr = thr; ma.beta = beta;
-    ma.inv_count = (float)(1.0 / ((double)batch->n * d->cout));
-    ma.Z = ws + w.Z; ma.U = ws + w.U; ma.DU = ws + w.DU; ma.DA = ws + w.DA; ma.Q = ws + w.Q; ma.XP = ws + w.XP; ma.G = ws + w.G;
-    ma.lpart = ws + w.lpart;
-    ma.npad = w.npad; ma.yhat_out = yhat_out;
-    const int grid1 = mfn_grid(*d, batch->n);
-    const bool prof = prof_live();
-    hipEvent_t *pev = prof ? dev_state()->prof_ev : nullptr;
-    if (prof) HIP_TRY(hipEventRecord(pev[2 * g_prof_n], st));
-    if (int rc = launch_mfn_fwd<true, false>(ma, grid1, st)) return rc;
-    if (prof) { HIP_TRY(hipEventRecord(pev[2 * g_prof_n + 1], st)); ++g_prof_n; }
-    // weight gradients, at most MFN_WGRAD_BLOCKS blocks per launch
-    const int64_t mlp = mfn_canon_count(*d);
-    const int nblocks = mfn_wgrad_count(*d);
-    for (int b0 = 0; b0 < nblocks; b0 += MFN_WGRAD_BLOCKS) {
-        MfnWgradArgs wa;
-        memset(&wa, 0, sizeof(wa));
-        wa.npad = w.npad; wa.chunk = w.chunk; wa.mlp = mlp; wa.slabs = ws + w.slabs;
-        wa.cin = d->cin; wa.FP = lay.FP;
-        wa.nblocks = (nblocks - b0) < MFN_WGRAD_BLOCKS ? (nblocks - b0) : MFN_WGRAD_BLOCKS;
-        int waves = 0;
-        for (int i = 0; i < wa.nblocks; ++i) {
-            wa.blk[i] = mfn_wgrad_block(*d, w, ws, packed, b0 + i);
-            wa.blk[i].wave_begin = waves;
-            waves += wa.blk[i].mb * wa.blk[i].nb;
-        }
-        wa.waves = waves;
-        hipLaunchKernelGGL(k_mfn_wgrad, dim3((unsigned)((waves + 3) / 4), (unsigned)w.nsplit), dim3(256), 0, st, wa);
-        HIP_TRY(hipGetLastError());
-    }
-    OptimScalars o;
-    memset(&o, 0, sizeof(o));
-    if (upd) o = upd->opt;
-    hipLaunchKernelGGL(k_ffn_reduce, dim3((unsigned)((mlp + 255) / 256)), dim3(256), 0, st, (const float *)(ws + w.slabs), w.nsplit, mlp, (int64_t)0,
-                       grads, (const float *)(ws + w.lpart), grid1, loss_kind == BRIEF_LOSS_EXTERNAL ? 0.f : ma.inv_count, loss_out,
-                       upd ? 1 : 0, o, upd ? upd->params : nullptr, upd ? upd->s1 : nullptr, upd ? upd->s2 : nullptr);
-    HIP_TRY(hipGetLastError());
-    if (upd) {
-        hipLaunchKernelGGL(k_mfn_repack, dim3((unsigned)((lay.total + 255) / 256)), dim3(256), 0, st, *d, (const float *)upd->params, upd->pk);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
-}
-
-extern "C" {
-
-int64_t brief_mfn_param_count(const brief_mfn_desc *d) { return check_mfn_desc(d) ? -1 : mfn_canon_count(*d); }
-int64_t brief_mfn_packed_count(const brief_mfn_desc *d) { return check_mfn_desc(d) ? -1 : mfn_layout(*d).total; }
-int64_t brief_mfn_train_workspace_bytes(const brief_mfn_desc *d, int64_t n)
-{
-    if (check_mfn_desc(d)) return -1;
-    if (n < 1) { fail(BRIEF_ERR_INVALID, "empty batch"); return -1; }
-    return mfn_ws_layout(*d, n).total * (int64_t)sizeof(float);
-}
-
-int brief_mfn_repack(const brief_mfn_desc *d, const float *params, float *packed, void *stream)
-{
-    if (int rc = check_mfn_desc(d)) return rc;
-    if (!params || !packed) return fail(BRIEF_ERR_INVALID, "null buffer");
-    const int64_t total = mfn_layout(*d).total;
-    hipLaunchKernelGGL(k_mfn_repack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *d, params, packed);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int brief_mfn_forward(const brief_mfn_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
-                      void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream)
-{
-    if (int rc = check_mfn_desc(d)) return rc;
-    brief_siren_desc sd;
-    memset(&sd, 0, sizeof(sd));
-    sd.cin = d->cin;
-    if (int rc = check_batch(&sd, grid, batch, false)) return rc;
-    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
-    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
-    MfnArgs ma;
-    mfn_forward_args(ma, d, packed, batch->n, out, out_kind, scale_min, scale_max, vmin, vmax);
-    ma.coords = batch->coords; ma.idx = batch->idx; ma.offset = batch->offset;
-    fill_grid(ma.grid, grid);
-    return launch_mfn_fwd<false, false>(ma, mfn_grid(*d, batch->n), (hipStream_t)stream);
-}
-
-int brief_mfn_forward_box(const brief_mfn_desc *d, const float *packed, const brief_grid_box *box, int64_t offset, int64_t n,
-                          void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream)
-{
-    if (int rc = check_mfn_desc(d)) return rc;
-    brief_siren_desc sd;
-    memset(&sd, 0, sizeof(sd));
-    sd.cin = d->cin;
-    int64_t voxels = 0;
-    if (int rc = check_box(&sd, box, &voxels)) return rc;
-    if (n < 1) return fail(BRIEF_ERR_INVALID, "empty batch");
-    if (offset < 0 || offset > voxels - n) return fail(BRIEF_ERR_INVALID, "offset + n exceeds the box's voxel count");
-    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
-    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
-    MfnArgs ma;
-    mfn_forward_args(ma, d, packed, n, out, out_kind, scale_min, scale_max, vmin, vmax);
-    ma.offset = offset;
-    fill_grid(ma.grid, &box->grid);
-    double total = 1.0;
-    for (int a = 0; a < 3; ++a) {
-        const bool on = a < box->grid.ndim;
-        ma.box.start[a] = on ? box->start[a] : 0;
-        ma.box.step[a] = on ? box->step[a] : 1;
-        ma.box.extent[a] = on ? box->extent[a] : 1;
-        ma.box.magic[a] = ~(uint64_t)0 / (uint64_t)ma.box.extent[a] + 1;
-        total *= (double)ma.box.extent[a];
-    }
-    ma.box.fast = total < 4294967296.0;
-    return launch_mfn_fwd<false, true>(ma, mfn_grid(*d, n), (hipStream_t)stream);
-}
-
-int brief_mfn_train_step(const brief_mfn_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
-                         int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
-                         void *workspace, int64_t workspace_bytes, void *stream)
-{
-    return mfn_train_impl(d, packed, grid, batch, loss_kind, thr, beta, grads, loss_out, yhat_out, workspace, workspace_bytes, stream, nullptr);
-}
-
-int brief_mfn_fit(const brief_mfn_fit_job *j, int64_t steps, void *stream)
-{
-    if (!j) return fail(BRIEF_ERR_INVALID, "null job");
-    if (int rc = check_mfn_desc(&j->desc)) return rc;
-    if (steps < 0) return fail(BRIEF_ERR_INVALID, "bad step count");
-    if (j->batch.idx && j->idx_stride <= 0) return fail(BRIEF_ERR_INVALID, "brief_mfn_fit needs idx_stride > 0 with batch.idx (one index set per step)");
-    if (j->batch.idx && j->idx_stride < j->batch.n) return fail(BRIEF_ERR_INVALID, "idx_stride is smaller than the batch");
-    if (!j->params || !j->packed || !j->grads || !j->loss_out || !j->workspace) return fail(BRIEF_ERR_INVALID, "null buffer");
-    if (j->t0 < 0) return fail(BRIEF_ERR_INVALID, "bad step count");
-    if (j->n_milestones < 0 || (j->n_milestones > 0 && !j->milestones)) return fail(BRIEF_ERR_INVALID, "bad lr milestones");
-    if (j->optim_kind < BRIEF_OPT_ADAMAX || j->optim_kind > BRIEF_OPT_SGD) return fail(BRIEF_ERR_INVALID, "bad optimizer kind");
-    if (j->optim_kind != BRIEF_OPT_SGD && (!j->state1 || !j->state2)) return fail(BRIEF_ERR_INVALID, "optimizer state required");
-    hipStream_t st = (hipStream_t)stream;
-    // the schedule fields mean what they mean in brief_fit_job: brief_siren_fit's rule (fit_job_lr) evaluates them
-    brief_fit_job sched;
-    memset(&sched, 0, sizeof(sched));
-    sched.milestones = j->milestones; sched.n_milestones = j->n_milestones; sched.gamma = j->gamma; sched.t0 = j->t0;
-    sched.lr_table = j->lr_table;
-    double lr = j->lr;
-    for (int64_t k = 0; k < steps; ++k) {
-        const int64_t t = j->t0 + 1 + k;
-        fit_job_lr(&sched, t, k, &lr);
-        brief_batch_desc b = j->batch;
-        if (b.idx) b.idx = b.idx + k * j->idx_stride;
-        else if (b.rng_pop > 0) b.rng_step = (uint64_t)t;
-        FfnUpdate up;
-        up.opt = optim_scalars(j->optim_kind, lr, j->beta1_table ? j->beta1_table[k] : j->beta1, j->beta2, j->eps, t);
-        up.params = j->params; up.s1 = j->state1; up.s2 = j->state2; up.pk = j->packed;
-        if (int rc = mfn_train_impl(&j->desc, j->packed, &j->grid, &b, j->loss_kind, j->thr, j->beta, j->grads,
-                                    j->loss_log ? j->loss_log + k : j->loss_out, nullptr, j->workspace, j->workspace_bytes, (void *)st, &up))
-            return rc;
-    }
-    if (j->loss_log && steps > 0)
-        HIP_TRY(hipMemcpyAsync(j->loss_out, j->loss_log + steps - 1, sizeof(float), hipMemcpyDeviceToDevice, st));
-    return 0;
-}
-
-}   // extern "C"
-
-// =============================================================================================
-// Tapered SIRENs (SIREN_Pyramid, SIRENFT, SIRENPS; brief_taper.inc): train step = k_taper_fwd<TRAIN> + k_taper_wgrad + k_ffn_reduce
-// (bv = 0) (+ k_taper_repack after an update)
-static int check_taper_desc(const brief_taper_desc *d)
-{
-    if (!d) return fail(BRIEF_ERR_INVALID, "null desc");
-    if (d->cin != 2 && d->cin != 3) return fail(BRIEF_ERR_INVALID, "tapered SIREN: coords_channel must be 2 or 3");
-    if (d->cout < 1 || d->cout > 4) return fail(BRIEF_ERR_INVALID, "tapered SIREN: data_channel must be 1..4");
-    if (d->layers < 3 || d->layers > BRIEF_TAPER_MAX_LAYERS) return fail(BRIEF_ERR_INVALID, "tapered SIREN: layers must be 3..16");
-    if (d->output_act != 0 && d->output_act != 1) return fail(BRIEF_ERR_INVALID, "tapered SIREN: output_act must be 0 or 1");
-    for (int l = 0; l < d->layers - 1; ++l)
-        if (d->widths[l] < 1 || d->widths[l] > 1024) return fail(BRIEF_ERR_INVALID, "tapered SIREN: every hidden width must be 1..1024 on the fused path");
-    return 0;
-}
-
-static int taper_lds_bytes(const TaperLayout &l) { return (int)sizeof(float) * (1024 * l.ntmax + 128); }
-// persistent grid: up to two workgroups per CU (one wave per SIMD each), fewer when the LDS image does not fit twice
-static int taper_grid(const TaperLayout &l, int64_t n)
-{
-    const int64_t tiles = (n + 31) / 32;
-    const int by_lds = (160 * 1024) / taper_lds_bytes(l);
-    const int64_t cap = (int64_t)kCUs * (by_lds < 2 ? (by_lds > 0 ? by_lds : 1) : 2);
-    return (int)(tiles < cap ? tiles : cap);
-}
-struct TaperWs { int64_t npad, Z, D, X, G, lpart, slabs, total, chunk; int nsplit, waves; };
-// weight-gradient block of Linear i (0 .. layers - 1) in canonical order; planes at the workspace offsets of w (ws == nullptr: shapes
-// only), wave_begin left to the caller
-static TaperWgradBlock taper_wgrad_block(const TaperLayout &lay, const TaperWs &w, float *ws, int i)
-{
-    const int L = lay.L;
-    const int64_t A = i == L - 1 ? w.G : w.D + (int64_t)lay.row0[i] * w.npad;
-    const int64_t B = i == 0 ? w.X : w.Z + (int64_t)lay.row0[i - 1] * w.npad;
-    TaperWgradBlock b;
-    memset(&b, 0, sizeof(b));
-    b.A = ws ? ws + A : nullptr; b.B = ws ? ws + B : nullptr;
-    b.arows = lay.out[i]; b.brows = lay.in[i];
-    b.mb = (b.arows + 63) / 64; b.nb = (b.brows + 63) / 64;
-    b.bsin = i > 0;
-    b.w_off = lay.canon[i]; b.b_off = lay.canon[i] + (int64_t)lay.out[i] * lay.in[i]; b.ldw = lay.in[i];
-    return b;
-}
-static TaperWs taper_ws_layout(const TaperLayout &lay, int64_t n)
-{
-    TaperWs w;
-    w.npad = (n + 31) / 32 * 32;
-    w.Z = 0;
-    w.D = w.Z + (int64_t)lay.rows * w.npad;
-    w.X = w.D + (int64_t)lay.rows * w.npad;
-    w.G = w.X + 4 * w.npad;
-    w.lpart = w.G + 4 * w.npad;
-    w.slabs = w.lpart + kFfnLossParts;
-    w.waves = 0;
-    for (int i = 0; i < lay.L; ++i) {
-        const TaperWgradBlock b = taper_wgrad_block(lay, w, nullptr, i);
-        w.waves += b.mb * b.nb;
-    }
-    const int64_t wgs = (w.waves + 3) / 4;
-    int64_t ns = (8 * (int64_t)kCUs + wgs - 1) / wgs;      // K-splits: about eight workgroups per CU (as k_ffn_wgrad)
-    if (ns > 64) ns = 64;
-    if (ns > w.npad / 256) ns = w.npad / 256;
-    if (ns < 1) ns = 1;
-    w.chunk = (w.npad / ns + 31) / 32 * 32;
-    w.nsplit = (int)((w.npad + w.chunk - 1) / w.chunk);
-    w.total = w.slabs + (int64_t)w.nsplit * lay.count;
-    return w;
-}
-
-template <bool TRAIN, bool BOX>
-static int launch_taper_fwd(const TaperArgs &ta, int grid, hipStream_t st)
-{
-    const int mtw = (ta.lay.ntmax + 3) / 4;
-    const int lds = taper_lds_bytes(ta.lay);
-    const void *fn = nullptr;
-    switch (mtw) {
-#define TAPER_CASE(M) case M: fn = (const void *)k_taper_fwd<M, TRAIN, BOX>; break;
-        TAPER_CASE(1) TAPER_CASE(2) TAPER_CASE(3) TAPER_CASE(4) TAPER_CASE(5) TAPER_CASE(6) TAPER_CASE(7) TAPER_CASE(8)
-#undef TAPER_CASE
-        default: return fail(BRIEF_ERR_INVALID, "tapered SIREN: every hidden width must be 1..1024 on the fused path");
-    }
-    if (int rc = dev_attr_once(fn, lds)) return rc;
-    switch (mtw) {
-#define TAPER_CASE(M) case M: hipLaunchKernelGGL((k_taper_fwd<M, TRAIN, BOX>), dim3(grid), dim3(256), lds, st, ta); break;
-        TAPER_CASE(1) TAPER_CASE(2) TAPER_CASE(3) TAPER_CASE(4) TAPER_CASE(5) TAPER_CASE(6) TAPER_CASE(7) TAPER_CASE(8)
-#undef TAPER_CASE
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-static void taper_forward_args(TaperArgs &ta, const brief_taper_desc *d, const float *packed, int64_t n, void *out, int out_kind,
-                               float scale_min, float scale_max, double vmin, double vmax)
-{
-    memset(&ta, 0, sizeof(ta));
-    ta.d = *d; ta.lay = taper_layout(*d); ta.pk = packed;
-    ta.n = n; ta.npad = (n + 31) / 32 * 32;
-    ta.out = out; ta.out_kind = out_kind;
-    ta.scale_min = scale_min;
-    ta.den = (float)((double)scale_max - (double)scale_min);
-    ta.span = (float)(vmax - vmin);
-    ta.vmin = (float)vmin;
-}
-
-static int taper_train_impl(const brief_taper_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
-                            int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
-                            void *workspace, int64_t workspace_bytes, void *stream, const FfnUpdate *upd)
-{
-    if (int rc = check_taper_desc(d)) return rc;
-    brief_siren_desc sd;      // check_batch reads cin only
-    memset(&sd, 0, sizeof(sd));
-    sd.cin = d->cin;
-    if (int rc = check_batch(&sd, grid, batch, true)) return rc;
-    if (!packed || !grads || !loss_out || !workspace) return fail(BRIEF_ERR_INVALID, "null buffer");
-    if (loss_kind < BRIEF_LOSS_L2 || loss_kind > BRIEF_LOSS_EXTERNAL) return fail(BRIEF_ERR_INVALID, "bad loss_kind");
-    TaperArgs ta;
-    taper_forward_args(ta, d, packed, batch->n, nullptr, 0, 0.f, 1.f, 0.0, 1.0);
-    const TaperLayout &lay = ta.lay;
-    const TaperWs w = taper_ws_layout(lay, batch->n);
-    if (workspace_bytes < w.total * (int64_t)sizeof(float)) return fail(BRIEF_ERR_WORKSPACE, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    float *ws = (float *)workspace;
-    ta.coords = batch->coords; ta.targets = batch->targets; ta.weights = batch->weights;
-    ta.idx = batch->idx; ta.offset = batch->offset;
-    if (!batch->idx && batch->rng_pop > 0) { ta.rng_pop = (uint64_t)batch->rng_pop; ta.rng_seed = batch->rng_seed; ta.rng_step = batch->rng_step; }
-    fill_grid(ta.grid, grid);
-    ta.loss_kind = loss_kind; ta.thr = thr; ta.beta = beta;
-    ta.inv_count = (float)(1.0 / ((double)batch->n * d->cout));
-    ta.Z = ws + w.Z; ta.D = ws + w.D; ta.X = ws + w.X; ta.G = ws + w.G; ta.lpart = ws + w.lpart;
-    ta.npad = w.npad; ta.yhat_out = yhat_out;
-    const int grid1 = taper_grid(lay, batch->n);
-    const bool prof = prof_live();
-    hipEvent_t *pev = prof ? dev_state()->prof_ev : nullptr;
-    if (prof) HIP_TRY(hipEventRecord(pev[2 * g_prof_n], st));
-    if (int rc = launch_taper_fwd<true, false>(ta, grid1, st)) return rc;
-    if (prof) { HIP_TRY(hipEventRecord(pev[2 * g_prof_n + 1], st)); ++g_prof_n; }
-    // weight gradients: one rectangular block per Linear, all in one launch (layers <= BRIEF_TAPER_MAX_LAYERS)
-    const int64_t mlp = lay.count;
-    TaperWgradArgs wa;
-    memset(&wa, 0, sizeof(wa));
-    wa.npad = w.npad; wa.chunk = w.chunk; wa.mlp = mlp; wa.slabs = ws + w.slabs;
-    wa.nblocks = lay.L;
-    int waves = 0;
-    for (int i = 0; i < wa.nblocks; ++i) {
-        wa.blk[i] = taper_wgrad_block(lay, w, ws, i);
-        wa.blk[i].wave_begin = waves;
-        waves += wa.blk[i].mb * wa.blk[i].nb;
-    }
-    wa.waves = waves;
-    hipLaunchKernelGGL(k_taper_wgrad, dim3((unsigned)((waves + 3) / 4), (unsigned)w.nsplit), dim3(256), 0, st, wa);
-    HIP_TRY(hipGetLastError());
-    OptimScalars o;
-    memset(&o, 0, sizeof(o));
-    if (upd) o = upd->opt;
-    hipLaunchKernelGGL(k_ffn_reduce, dim3((unsigned)((mlp + 255) / 256)), dim3(256), 0, st, (const float *)(ws + w.slabs), w.nsplit, mlp, (int64_t)0,
-                       grads, (const float *)(ws + w.lpart), grid1, loss_kind == BRIEF_LOSS_EXTERNAL ? 0.f : ta.inv_count, loss_out,
-                       upd ? 1 : 0, o, upd ? upd->params : nullptr, upd ? upd->s1 : nullptr, upd ? upd->s2 : nullptr);
-    HIP_TRY(hipGetLastError());
-    if (upd) {
-        hipLaunchKernelGGL(k_taper_repack, dim3((unsigned)((lay.total + 255) / 256)), dim3(256), 0, st, *d, lay, (const float *)upd->params, upd->pk);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
-}
-
-extern "C" {
-
-int64_t brief_taper_param_count(const brief_taper_desc *d) { return check_taper_desc(d) ? -1 : taper_layout(*d).count; }
-int64_t brief_taper_packed_count(const brief_taper_desc *d) { return check_taper_desc(d) ? -1 : taper_layout(*d).total; }
-int64_t brief_taper_train_workspace_bytes(const brief_taper_desc *d, int64_t n)
-{
-    if (check_taper_desc(d)) return -1;
-    if (n < 1) { fail(BRIEF_ERR_INVALID, "empty batch"); return -1; }
-    return taper_ws_layout(taper_layout(*d), n).total * (int64_t)sizeof(float);
-}
-
-int brief_taper_repack(const brief_taper_desc *d, const float *params, float *packed, void *stream)
-{
-    if (int rc = check_taper_desc(d)) return rc;
-    if (!params || !packed) return fail(BRIEF_ERR_INVALID, "null buffer");
-    const TaperLayout lay = taper_layout(*d);
-    hipLaunchKernelGGL(k_taper_repack, dim3((unsigned)((lay.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *d, lay, params, packed);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int brief_taper_forward(const brief_taper_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
-                        void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream)
-{
-    if (int rc = check_taper_desc(d)) return rc;
-    brief_siren_desc sd;
-    memset(&sd, 0, sizeof(sd));
-    sd.cin = d->cin;
-    if (int rc = check_batch(&sd, grid, batch, false)) return rc;
-    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
-    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
-    TaperArgs ta;
-    taper_forward_args(ta, d, packed, batch->n, out, out_kind, scale_min, scale_max, vmin, vmax);
-    ta.coords = batch->coords; ta.idx = batch->idx; ta.offset = batch->offset;
-    fill_grid(ta.grid, grid);
-    return launch_taper_fwd<false, false>(ta, taper_grid(ta.lay, batch->n), (hipStream_t)stream);
-}
-
-int brief_taper_forward_box(const brief_taper_desc *d, const float *packed, const brief_grid_box *box, int64_t offset, int64_t n,
-                            void *out, int out_kind, float scale_min, float scale_max, double vmin, double vmax, void *stream)
-{
-    if (int rc = check_taper_desc(d)) return rc;
-    brief_siren_desc sd;
-    memset(&sd, 0, sizeof(sd));
-    sd.cin = d->cin;
-    int64_t voxels = 0;
-    if (int rc = check_box(&sd, box, &voxels)) return rc;
-    if (n < 1) return fail(BRIEF_ERR_INVALID, "empty batch");
-    if (offset < 0 || offset > voxels - n) return fail(BRIEF_ERR_INVALID, "offset + n exceeds the box's voxel count");
-    if (!packed || !out) return fail(BRIEF_ERR_INVALID, "null buffer");
-    if (out_kind < BRIEF_OUT_F32 || out_kind > BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "bad out_kind");
-    TaperArgs ta;
-    taper_forward_args(ta, d, packed, n, out, out_kind, scale_min, scale_max, vmin, vmax);
-    ta.offset = offset;
-    fill_grid(ta.grid, &box->grid);
-    double total = 1.0;
-    for (int a = 0; a < 3; ++a) {
-        const bool on = a < box->grid.ndim;
-        ta.box.start[a] = on ? box->start[a] : 0;
-        ta.box.step[a] = on ? box->step[a] : 1;
-        ta.box.extent[a] = on ? box->extent[a] : 1;
-        ta.box.magic[a] = ~(uint64_t)0 / (uint64_t)ta.box.extent[a] + 1;
-        total *= (double)ta.box.extent[a];
-    }
-    ta.box.fast = total < 4294967296.0;
-    return launch_taper_fwd<false, true>(ta, taper_grid(ta.lay, n), (hipStream_t)stream);
-}
-
-int brief_taper_train_step(const brief_taper_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
-                           int loss_kind, float thr, float beta, float *grads, float *loss_out, float *yhat_out,
-                           void *workspace, int64_t workspace_bytes, void *stream)
-{
-    return taper_train_impl(d, packed, grid, batch, loss_kind, thr, beta, grads, loss_out, yhat_out, workspace, workspace_bytes, stream, nullptr);
-}
-
-int brief_taper_fit(const brief_taper_fit_job *j, int64_t steps, void *stream)
-{
-    if (!j) return fail(BRIEF_ERR_INVALID, "null job");
-    if (int rc = check_taper_desc(&j->desc)) return rc;
-    if (steps < 0) return fail(BRIEF_ERR_INVALID, "bad step count");
-    if (j->batch.idx && j->idx_stride <= 0) return fail(BRIEF_ERR_INVALID, "brief_taper_fit needs idx_stride > 0 with batch.idx (one index set per step)");
-    if (j->batch.idx && j->idx_stride < j->batch.n) return fail(BRIEF_ERR_INVALID, "idx_stride is smaller than the batch");
-    if (!j->params || !j->packed || !j->grads || !j->loss_out || !j->workspace) return fail(BRIEF_ERR_INVALID, "null buffer");
-    if (j->t0 < 0) return fail(BRIEF_ERR_INVALID, "bad step count");
-    if (j->n_milestones < 0 || (j->n_milestones > 0 && !j->milestones)) return fail(BRIEF_ERR_INVALID, "bad lr milestones");
-    if (j->optim_kind < BRIEF_OPT_ADAMAX || j->optim_kind > BRIEF_OPT_SGD) return fail(BRIEF_ERR_INVALID, "bad optimizer kind");
-    if (j->optim_kind != BRIEF_OPT_SGD && (!j->state1 || !j->state2)) return fail(BRIEF_ERR_INVALID, "optimizer state required");
-    hipStream_t st = (hipStream_t)stream;
-    // the schedule fields mean what they mean in brief_fit_job: brief_siren_fit's rule (fit_job_lr) evaluates them
-    brief_fit_job sched;
-    memset(&sched, 0, sizeof(sched));
-    sched.milestones = j->milestones; sched.n_milestones = j->n_milestones; sched.gamma = j->gamma; sched.t0 = j->t0;
-    sched.lr_table = j->lr_table;
-    double lr = j->lr;
-    for (int64_t k = 0; k < steps; ++k) {
-        const int64_t t = j->t0 + 1 + k;
-        fit_job_lr(&sched, t, k, &lr);
-        brief_batch_desc b = j->batch;
-        if (b.idx) b.idx = b.idx + k * j->idx_stride;
-        else if (b.rng_pop > 0) b.rng_step = (uint64_t)t;
-        FfnUpdate up;
-        up.opt = optim_scalars(j->optim_kind, lr, j->beta1_table ? j->beta1_table[k] : j->beta1, j->beta2, j->eps, t);
-        up.params = j->params; up.s1 = j->state1; up.s2 = j->state2; up.pk = j->packed;
-        if (int rc = taper_train_impl(&j->desc, j->packed, &j->grid, &b, j->loss_kind, j->thr, j->beta, j->grads,
-                                      j->loss_log ? j->loss_log + k : j->loss_out, nullptr, j->workspace, j->workspace_bytes, (void *)st, &up))
-            return rc;
-    }
-    if (j->loss_log && steps > 0)
-        HIP_TRY(hipMemcpyAsync(j->loss_out, j->loss_log + steps - 1, sizeof(float), hipMemcpyDeviceToDevice, st));
-    return 0;
-}
-
-}   // extern "C"
+#include "brief_family_host.inc"      // FFN, NeRF, MFN, tapered SIRENs: one host driver, four traits structs and their C-ABI entries

@@ -80,6 +80,10 @@ struct NerfArgs {
 // ---- the tile helpers of brief_ffn.inc (ffn_box_coords, ffn_chain, ffn_bias, ffn_write_image, ffn_stash), restated under NeRF names:
 // calling the FFN helpers from a second kernel family changed the register allocation of the existing k_ffn_fwd instantiations, so the
 // NeRF kernels carry their own copies and every FFN kernel compiles to the code it had before this file existed.
+// (Measured again with four families in the file, the NeRF, MFN and taper copies replaced by calls to the ffn_* helpers: 88 of the 330
+// kernels compile to other code, 24 k_ffn_fwd instantiations whose source did not change among them; k_mfn_fwd<1|2, false, ., .> gains
+// 4 VGPRs, k_mfn_fwd<8, false, false, false> goes from 144 to 76 bytes of scratch, k_ffn_fwd<7|8, false, false> change instruction
+// counts.  So the copies stay; what the families share is their host side, brief_family_host.inc.)
 // box-linear index b -> coordinates (the arithmetic of box_coords, on the box of NerfArgs): bit-identical to the whole-grid decode
 __device__ __forceinline__ void nerf_box_coords(const GridArgs &g, const BoxArgs &bx, int cin, int64_t b, float &x0, float &x1, float &x2)
 {

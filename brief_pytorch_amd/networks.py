@@ -434,7 +434,7 @@ class SIREN:
         if self._ws is None or self._ws.numel() * 4 < need:
             self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
 
-    # ---- the C-ABI entries of this net kind (FFN overrides them)
+    # ---- the C-ABI entries of this net kind (_FusedFamily overrides them)
     def _abi_packed_count(self):
         return _lib.lib().brief_packed_count(C.byref(self.desc))
 
@@ -486,13 +486,93 @@ class SIREN:
             raise NotImplementedError("SIREN(res=True) is unsupported on the fused path")
 
 
-class FFN(SIREN):
+class _FusedFamily(SIREN):
+    """what FFN, NeRF, the MFNs and the tapered SIRENs share: kernels of their own, fp32 only, behind the C-ABI entries brief_<family>_*
+    (one host driver: csrc/brief_family_host.inc), and a fit job type of their own.  A family names its entries and itself."""
+
+    _abi = None                              # "brief_<family>_": the prefix of the family's C-ABI entries
+    _fit_job, _fit_entry = None, None        # brief_*_fit_job type and brief_*_fit entry (Fitter, fit_step)
+    _family = None                           # the family's name in half()'s warning
+    _warned_half = set()                     # families that have warned
+
+    def _set_precision(self, precision):
+        return self
+
+    def float(self):
+        return self
+
+    def half(self):
+        """no low-precision kernels: the net stays in fp32 (NFGR keeps the reference's 2-bytes-per-parameter budget and records
+        phi_precision: fp32)"""
+        if self._family not in _FusedFamily._warned_half:
+            _FusedFamily._warned_half.add(self._family)
+            logging.warning("%s.half(): there are no low-precision %s kernels; the net stays in fp32" % (type(self).kind, self._family))
+        return self
+
+    def _forward_scratch(self, n):
+        return None, 0
+
+    # ---- C-ABI entries
+    def _entry(self, name):
+        return getattr(_lib.lib(), self._abi + name)
+
+    def _abi_packed_count(self):
+        return self._entry("packed_count")(C.byref(self.desc))
+
+    def _abi_repack(self):
+        return self._entry("repack")(C.byref(self.desc), _lib.ptr(self.params), _lib.ptr(self.packed), _lib.stream_ptr())
+
+    def _abi_forward(self, grid, batch, out, kind, scale, vrange, n):
+        return self._entry("forward")(C.byref(self.desc), _lib.ptr(self.packed), C.byref(grid) if grid is not None else None,
+                                      C.byref(batch), _lib.ptr(out), kind, float(scale[0]), float(scale[1]),
+                                      float(vrange[0]), float(vrange[1]), _lib.stream_ptr())
+
+    def _abi_forward_box(self, box, off, cnt, out, kind, scale, vrange):
+        return self._entry("forward_box")(C.byref(self.desc), _lib.ptr(self.packed), C.byref(box), off, cnt, _lib.ptr(out),
+                                          kind, float(scale[0]), float(scale[1]), float(vrange[0]), float(vrange[1]),
+                                          _lib.stream_ptr())
+
+    def _abi_train_ws_bytes(self, n):
+        return self._entry("train_workspace_bytes")(C.byref(self.desc), int(n))
+
+    def _abi_train_step(self, g, b, loss_kind, thr, beta, yhat):
+        return self._entry("train_step")(
+            C.byref(self.desc), _lib.ptr(self.packed), C.byref(g) if g is not None else None, C.byref(b),
+            loss_kind, float(thr), float(beta), _lib.ptr(self.grads), _lib.ptr(self._loss), _lib.ptr(yhat),
+            _lib.ptr(self._ws), self._ws.numel() * 4, _lib.stream_ptr())
+
+    def fit_step(self, n, targets, opt_kind, s1, s2, lr, t, idx=None, weights=None, grid=None, offset=0,
+                 loss="datal2", thr=0.0, beta=0.01, betas=(0.9, 0.999), eps=1e-8, rng=None):
+        """train_step + optimizer update of the MLP span + refresh of the packed copy: one step of the family's brief_*_fit"""
+        self._require_gpu()
+        self.sync_packed()
+        self.ensure_train_buffers(n)
+        dims, lo, hi = grid
+        g = self._grid(dims, lo, hi)
+        pop, seed, step = rng if (rng is not None and idx is None) else (0, 0, 0)
+        dev = self.params.device
+        b = _lib.BatchDesc(None, _dev_ptr(targets, torch.float32, "targets", dev), _dev_ptr(weights, torch.float32, "weights", dev),
+                           _dev_ptr(idx, torch.int64, "idx", dev), int(offset), int(n), int(pop), int(seed), 0)
+        j = self._fit_job()
+        j.desc, j.grid, j.batch = self.desc, g, b
+        j.params, j.packed, j.state1, j.state2 = self.params.data_ptr(), self.packed.data_ptr(), _lib.ptr(s1), _lib.ptr(s2)
+        j.grads, j.loss_out, j.loss_log = self.grads.data_ptr(), self._loss.data_ptr(), None
+        j.workspace, j.workspace_bytes = self._ws.data_ptr(), self._ws.numel() * 4
+        j.loss_kind, j.optim_kind, j.thr, j.beta = _lib.LOSS_KIND[loss], int(opt_kind), float(thr), float(beta)
+        j.lr, j.beta1, j.beta2, j.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
+        j.n_milestones, j.gamma, j.t0 = 0, 1.0, int(t) - 1
+        j.idx_stride = int(n) if idx is not None else 0      # (in-kernel draws of step t are keyed by rng_step = t0 + 1 = t)
+        _lib.check(getattr(_lib.lib(), self._fit_entry)(C.byref(j), 1, _lib.stream_ptr()))
+        return self._loss
+
+
+class FFN(_FusedFamily):
     """reference: utils/Networks.py:138-207 (FourierFeatureEmbedding + FFN), skip=False.  Parameters live in one canonical buffer
     [bvals | W0 b0 | hidden | head] (include/brief_hip.h, brief_ffn_desc); bvals is fixed: its gradient is zero and the optimizer
     (brief_ffn_fit) updates the MLP span only."""
 
     kind = "FFN"
-    _fit_job, _fit_entry = _lib.FfnFitJob, "brief_ffn_fit"      # brief_*_fit_job type and brief_*_fit entry (Fitter, fit_step)
+    _abi, _fit_job, _fit_entry, _family = "brief_ffn_", _lib.FfnFitJob, "brief_ffn_fit", "FFN"
 
     def __init__(self, coords_channel=3, data_channel=1, embsize=256, scale=10, features=256, layers=5, skip=False,
                  device=None, precision="fp32", **kwargs):
@@ -567,73 +647,6 @@ class FFN(SIREN):
             self.fourierfeature_embedding.bvals.data = sd["fourierfeature_embedding.bvals"]
         SIREN.load_state_dict(self, sd)
 
-    def _set_precision(self, precision):
-        return self
-
-    def float(self):
-        return self
-
-    def half(self):
-        """no low-precision FFN kernels: the net stays in fp32 (NFGR keeps the reference's 2-bytes-per-parameter budget and records
-        phi_precision: fp32)"""
-        if not getattr(FFN, "_warned_half", False):
-            FFN._warned_half = True
-            logging.warning("FFN.half(): there are no low-precision FFN kernels; the net stays in fp32")
-        return self
-
-    def _forward_scratch(self, n):
-        return None, 0
-
-    # ---- C-ABI entries
-    def _abi_packed_count(self):
-        return _lib.lib().brief_ffn_packed_count(C.byref(self.desc))
-
-    def _abi_repack(self):
-        return _lib.lib().brief_ffn_repack(C.byref(self.desc), _lib.ptr(self.params), _lib.ptr(self.packed), _lib.stream_ptr())
-
-    def _abi_forward(self, grid, batch, out, kind, scale, vrange, n):
-        return _lib.lib().brief_ffn_forward(C.byref(self.desc), _lib.ptr(self.packed), C.byref(grid) if grid is not None else None,
-                                            C.byref(batch), _lib.ptr(out), kind, float(scale[0]), float(scale[1]),
-                                            float(vrange[0]), float(vrange[1]), _lib.stream_ptr())
-
-    def _abi_forward_box(self, box, off, cnt, out, kind, scale, vrange):
-        return _lib.lib().brief_ffn_forward_box(C.byref(self.desc), _lib.ptr(self.packed), C.byref(box), off, cnt, _lib.ptr(out),
-                                                kind, float(scale[0]), float(scale[1]), float(vrange[0]), float(vrange[1]),
-                                                _lib.stream_ptr())
-
-    def _abi_train_ws_bytes(self, n):
-        return _lib.lib().brief_ffn_train_workspace_bytes(C.byref(self.desc), int(n))
-
-    def _abi_train_step(self, g, b, loss_kind, thr, beta, yhat):
-        return _lib.lib().brief_ffn_train_step(
-            C.byref(self.desc), _lib.ptr(self.packed), C.byref(g) if g is not None else None, C.byref(b),
-            loss_kind, float(thr), float(beta), _lib.ptr(self.grads), _lib.ptr(self._loss), _lib.ptr(yhat),
-            _lib.ptr(self._ws), self._ws.numel() * 4, _lib.stream_ptr())
-
-    def fit_step(self, n, targets, opt_kind, s1, s2, lr, t, idx=None, weights=None, grid=None, offset=0,
-                 loss="datal2", thr=0.0, beta=0.01, betas=(0.9, 0.999), eps=1e-8, rng=None):
-        """train_step + optimizer update of the MLP span + refresh of the packed copy: one step of brief_ffn_fit (brief_nerf_fit)"""
-        self._require_gpu()
-        self.sync_packed()
-        self.ensure_train_buffers(n)
-        dims, lo, hi = grid
-        g = self._grid(dims, lo, hi)
-        pop, seed, step = rng if (rng is not None and idx is None) else (0, 0, 0)
-        dev = self.params.device
-        b = _lib.BatchDesc(None, _dev_ptr(targets, torch.float32, "targets", dev), _dev_ptr(weights, torch.float32, "weights", dev),
-                           _dev_ptr(idx, torch.int64, "idx", dev), int(offset), int(n), int(pop), int(seed), 0)
-        j = self._fit_job()
-        j.desc, j.grid, j.batch = self.desc, g, b
-        j.params, j.packed, j.state1, j.state2 = self.params.data_ptr(), self.packed.data_ptr(), _lib.ptr(s1), _lib.ptr(s2)
-        j.grads, j.loss_out, j.loss_log = self.grads.data_ptr(), self._loss.data_ptr(), None
-        j.workspace, j.workspace_bytes = self._ws.data_ptr(), self._ws.numel() * 4
-        j.loss_kind, j.optim_kind, j.thr, j.beta = _lib.LOSS_KIND[loss], int(opt_kind), float(thr), float(beta)
-        j.lr, j.beta1, j.beta2, j.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
-        j.n_milestones, j.gamma, j.t0 = 0, 1.0, int(t) - 1
-        j.idx_stride = int(n) if idx is not None else 0      # (in-kernel draws of step t are keyed by rng_step = t0 + 1 = t)
-        _lib.check(getattr(_lib.lib(), self._fit_entry)(C.byref(j), 1, _lib.stream_ptr()))
-        return self._loss
-
     # ---- budget -> width (utils/Networks.py:188-207)
     @staticmethod
     def calc_param_count(coords_channel, data_channel, features, embsize=256, layers=5, skip=False, **kwargs):
@@ -661,14 +674,14 @@ class FFN(SIREN):
             raise NotImplementedError("FFN(skip=True) is unsupported on the fused path")
 
 
-class NeRF(FFN):
+class NeRF(_FusedFamily):
     """reference: utils/Networks.py:64-136 (PosEncodingNeRF + NeRF).  Parameters live in one canonical buffer in state_dict() order
     [W0 b0 | hidden | head] (include/brief_hip.h, brief_nerf_desc); with skip the hidden layer sl = (layers - 1) // 2 is
     Linear(d + F, F) on cat[encoding, h].  The encoding has no parameters; the whole buffer is trained.  Like FFN it has fp32 kernels
     only (half() / low-precision modes run in fp32 with a warning)."""
 
     kind = "NeRF"
-    _fit_job, _fit_entry = _lib.NerfFitJob, "brief_nerf_fit"
+    _abi, _fit_job, _fit_entry, _family = "brief_nerf_", _lib.NerfFitJob, "brief_nerf_fit", "NeRF"
 
     def __init__(self, coords_channel=3, data_channel=1, frequencies=10, features=256, layers=5, skip=True,
                  device=None, precision="fp32", **kwargs):
@@ -738,46 +751,6 @@ class NeRF(FFN):
             parts += [w.reshape(-1), b]
         return torch.cat(parts).contiguous()
 
-    def state_dict(self):
-        return SIREN.state_dict(self)
-
-    def load_state_dict(self, sd):
-        SIREN.load_state_dict(self, sd)
-
-    def half(self):
-        """no low-precision NeRF kernels: the net stays in fp32 (NFGR keeps the reference's 2-bytes-per-parameter budget and records
-        phi_precision: fp32)"""
-        if not getattr(NeRF, "_warned_half", False):
-            NeRF._warned_half = True
-            logging.warning("NeRF.half(): there are no low-precision NeRF kernels; the net stays in fp32")
-        return self
-
-    # ---- C-ABI entries
-    def _abi_packed_count(self):
-        return _lib.lib().brief_nerf_packed_count(C.byref(self.desc))
-
-    def _abi_repack(self):
-        return _lib.lib().brief_nerf_repack(C.byref(self.desc), _lib.ptr(self.params), _lib.ptr(self.packed), _lib.stream_ptr())
-
-    def _abi_forward(self, grid, batch, out, kind, scale, vrange, n):
-        return _lib.lib().brief_nerf_forward(C.byref(self.desc), _lib.ptr(self.packed), C.byref(grid) if grid is not None else None,
-                                             C.byref(batch), _lib.ptr(out), kind, float(scale[0]), float(scale[1]),
-                                             float(vrange[0]), float(vrange[1]), _lib.stream_ptr())
-
-    def _abi_forward_box(self, box, off, cnt, out, kind, scale, vrange):
-        return _lib.lib().brief_nerf_forward_box(C.byref(self.desc), _lib.ptr(self.packed), C.byref(box), off, cnt, _lib.ptr(out),
-                                                 kind, float(scale[0]), float(scale[1]), float(vrange[0]), float(vrange[1]),
-                                                 _lib.stream_ptr())
-
-    def _abi_train_ws_bytes(self, n):
-        return _lib.lib().brief_nerf_train_workspace_bytes(C.byref(self.desc), int(n))
-
-    def _abi_train_step(self, g, b, loss_kind, thr, beta, yhat):
-        return _lib.lib().brief_nerf_train_step(
-            C.byref(self.desc), _lib.ptr(self.packed), C.byref(g) if g is not None else None, C.byref(b),
-            loss_kind, float(thr), float(beta), _lib.ptr(self.grads), _lib.ptr(self._loss), _lib.ptr(yhat),
-            _lib.ptr(self._ws), self._ws.numel() * 4, _lib.stream_ptr())
-
     # ---- budget -> width (utils/Networks.py:118-136)
     @staticmethod
     def calc_param_count(coords_channel, data_channel, features, frequencies, layers, skip, **kwargs):
@@ -799,13 +772,13 @@ class NeRF(FFN):
         return round((-b + math.sqrt(b ** 2 - 4 * a * c)) / (2 * a))
 
 
-class _MFNBase(FFN):
+class _MFNBase(_FusedFamily):
     """reference: utils/Networks.py:648-799 (MFNBase + FourierLayer / GaborLayer).  Parameters live in one canonical buffer in
     state_dict() order [linear.i (W b) | output_linear | per filter: (mu gamma) linear] (include/brief_hip.h, brief_mfn_desc); the whole
     buffer is trained.  `linear[i]`, `output_linear`, `filters[i].linear` and `filters[i].mu` / `.gamma` are windows into it.  There is
     no `.net`: ModelSave takes its state_dict branch (one torch.save file), as it does for the reference's MFN.  fp32 kernels only."""
 
-    _fit_job, _fit_entry = _lib.MfnFitJob, "brief_mfn_fit"
+    _abi, _fit_job, _fit_entry, _family = "brief_mfn_", _lib.MfnFitJob, "brief_mfn_fit", "MFN"
     GABOR = False
 
     def __init__(self, coords_channel=3, features=256, data_channel=1, layers=5, input_scale=256.0, weight_scale=1.0, bias=True,
@@ -923,40 +896,6 @@ class _MFNBase(FFN):
             self.params[o:o + v.numel()].copy_(v.reshape(-1).to(self.params.device))
         self._stale = True
 
-    def half(self):
-        """no low-precision MFN kernels: the net stays in fp32 (NFGR keeps the reference's 2-bytes-per-parameter budget and records
-        phi_precision: fp32)"""
-        if not getattr(_MFNBase, "_warned_half", False):
-            _MFNBase._warned_half = True
-            logging.warning("%s.half(): there are no low-precision MFN kernels; the net stays in fp32" % type(self).kind)
-        return self
-
-    # ---- C-ABI entries
-    def _abi_packed_count(self):
-        return _lib.lib().brief_mfn_packed_count(C.byref(self.desc))
-
-    def _abi_repack(self):
-        return _lib.lib().brief_mfn_repack(C.byref(self.desc), _lib.ptr(self.params), _lib.ptr(self.packed), _lib.stream_ptr())
-
-    def _abi_forward(self, grid, batch, out, kind, scale, vrange, n):
-        return _lib.lib().brief_mfn_forward(C.byref(self.desc), _lib.ptr(self.packed), C.byref(grid) if grid is not None else None,
-                                            C.byref(batch), _lib.ptr(out), kind, float(scale[0]), float(scale[1]),
-                                            float(vrange[0]), float(vrange[1]), _lib.stream_ptr())
-
-    def _abi_forward_box(self, box, off, cnt, out, kind, scale, vrange):
-        return _lib.lib().brief_mfn_forward_box(C.byref(self.desc), _lib.ptr(self.packed), C.byref(box), off, cnt, _lib.ptr(out),
-                                                kind, float(scale[0]), float(scale[1]), float(vrange[0]), float(vrange[1]),
-                                                _lib.stream_ptr())
-
-    def _abi_train_ws_bytes(self, n):
-        return _lib.lib().brief_mfn_train_workspace_bytes(C.byref(self.desc), int(n))
-
-    def _abi_train_step(self, g, b, loss_kind, thr, beta, yhat):
-        return _lib.lib().brief_mfn_train_step(
-            C.byref(self.desc), _lib.ptr(self.packed), C.byref(g) if g is not None else None, C.byref(b),
-            loss_kind, float(thr), float(beta), _lib.ptr(self.grads), _lib.ptr(self._loss), _lib.ptr(yhat),
-            _lib.ptr(self._ws), self._ws.numel() * 4, _lib.stream_ptr())
-
     # ---- budget -> width (utils/Networks.py:721-731, 787-797)
     FILTER_PARAMS = 1       # per feature and filter: (cin + 1) x FILTER_PARAMS
 
@@ -1009,13 +948,13 @@ class MFNGabor(_MFNBase):
         return MFNGabor._features(param_count, coords_channel, data_channel, layers)
 
 
-class _TaperBase(FFN):
+class _TaperBase(_FusedFamily):
     """the tapered SIRENs of the reference (utils/Networks.py:316-552): a SIREN whose every Linear has its own width and every sine its
     own w0.  Parameters live in one canonical buffer in state_dict() order (W_l b_l per Linear); `.net[l][0].weight / .bias`, the
     state_dict keys, the init replay and the raw weight-l-out-in / bias-l-n artefact are SIREN's.  The subclasses give the widths and the
     budget rules.  fp32 kernels only (include/brief_hip.h, brief_taper_desc)."""
 
-    _fit_job, _fit_entry = _lib.TaperFitJob, "brief_taper_fit"
+    _abi, _fit_job, _fit_entry, _family = "brief_taper_", _lib.TaperFitJob, "brief_taper_fit", "tapered-SIREN"
     MAX_LAYERS, MAX_WIDTH = _lib.TAPER_MAX_LAYERS, 1024
 
     def _setup(self, coords_channel, data_channel, features, layers, w0, res, output_act, device, precision, widths, w0s):
@@ -1078,49 +1017,6 @@ class _TaperBase(FFN):
             raise ValueError("%s: a layer of width %d (layer widths %s): every hidden width must be >= 1" % (name, min(widths), widths))
         if max(widths) > _TaperBase.MAX_WIDTH:
             raise NotImplementedError("%s: every hidden width must be 1..1024 on the fused path (layer widths %s)" % (name, widths))
-
-    def _reference_init(self):
-        return SIREN._reference_init(self)
-
-    def state_dict(self):
-        return SIREN.state_dict(self)
-
-    def load_state_dict(self, sd):
-        SIREN.load_state_dict(self, sd)
-
-    def half(self):
-        """no low-precision kernels for the tapered nets: the net stays in fp32 (NFGR keeps the reference's 2-bytes-per-parameter budget
-        and records phi_precision: fp32)"""
-        if not getattr(_TaperBase, "_warned_half", False):
-            _TaperBase._warned_half = True
-            logging.warning("%s.half(): there are no low-precision kernels for the tapered SIRENs; the net stays in fp32" % type(self).kind)
-        return self
-
-    # ---- C-ABI entries
-    def _abi_packed_count(self):
-        return _lib.lib().brief_taper_packed_count(C.byref(self.desc))
-
-    def _abi_repack(self):
-        return _lib.lib().brief_taper_repack(C.byref(self.desc), _lib.ptr(self.params), _lib.ptr(self.packed), _lib.stream_ptr())
-
-    def _abi_forward(self, grid, batch, out, kind, scale, vrange, n):
-        return _lib.lib().brief_taper_forward(C.byref(self.desc), _lib.ptr(self.packed), C.byref(grid) if grid is not None else None,
-                                              C.byref(batch), _lib.ptr(out), kind, float(scale[0]), float(scale[1]),
-                                              float(vrange[0]), float(vrange[1]), _lib.stream_ptr())
-
-    def _abi_forward_box(self, box, off, cnt, out, kind, scale, vrange):
-        return _lib.lib().brief_taper_forward_box(C.byref(self.desc), _lib.ptr(self.packed), C.byref(box), off, cnt, _lib.ptr(out),
-                                                  kind, float(scale[0]), float(scale[1]), float(vrange[0]), float(vrange[1]),
-                                                  _lib.stream_ptr())
-
-    def _abi_train_ws_bytes(self, n):
-        return _lib.lib().brief_taper_train_workspace_bytes(C.byref(self.desc), int(n))
-
-    def _abi_train_step(self, g, b, loss_kind, thr, beta, yhat):
-        return _lib.lib().brief_taper_train_step(
-            C.byref(self.desc), _lib.ptr(self.packed), C.byref(g) if g is not None else None, C.byref(b),
-            loss_kind, float(thr), float(beta), _lib.ptr(self.grads), _lib.ptr(self._loss), _lib.ptr(yhat),
-            _lib.ptr(self._ws), self._ws.numel() * 4, _lib.stream_ptr())
 
     @staticmethod
     def _count(cin, cout, widths):
