@@ -105,7 +105,8 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_siren_fit", "brief_multi_fit",
            "brief_optim_step", "brief_sample_indices", "brief_sse_u16", "brief_profile_enable", "brief_profile_fused", "brief_deblock_edge", "brief_ssim_u16", "brief_ssim_partial_count",
            "brief_sincos_probe", "brief_cu_count",
-           "brief_correct_chunk_elems", "brief_correct_count", "brief_correct_emit", "brief_correct_apply"] \
+           "brief_correct_chunk_elems", "brief_correct_count", "brief_correct_emit", "brief_correct_apply",
+           "brief_mip_accumulate"] \
     + ["brief_%s_%s" % (prefix, entry) for prefix, _, _ in FAMILIES for entry in FAMILY_ENTRIES]
 
 
@@ -206,6 +207,8 @@ def lib():
     L.brief_correct_count.argtypes = [vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp, vp]
     L.brief_correct_emit.argtypes = [vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int64, vp, vp, vp]
     L.brief_correct_apply.argtypes = [vp, C.c_int, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp]
+    i3 = C.POINTER(C.c_int64)
+    L.brief_mip_accumulate.argtypes = [vp, C.c_int, i3, C.c_int32, vp, vp, vp, i3, i3, vp]
     _LIB = L
     return L
 

@@ -36,6 +36,7 @@
 //   brief_bf16.inc     k16 / k_wgrad16 / k_reduce16: the same path on v_mfma_f32_32x32x16_bf16 (BRIEF_PREC_BF16).
 //   k_sample, k_sse_u16, k_ssim_u16, k_deblock_edge: index stream, metrics and the deblocking filter.
 //   brief_correct.inc  k_correct_count / k_correct_emit / k_correct_apply: the stored corrections of the error-bounded mode.
+//   brief_mip.inc      k_mip_rows / k_mip_cols: max-intensity projections of a decoded box, folded into three images.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
@@ -61,6 +62,7 @@
 #include "brief_mfn.inc"        // MFN: k_mfn_fwd, k_mfn_wgrad, k_mfn_repack
 #include "brief_taper.inc"      // tapered SIRENs: k_taper_fwd, k_taper_wgrad, k_taper_repack
 #include "brief_correct.inc"    // error-bounded mode: k_correct_count, k_correct_emit, k_correct_apply
+#include "brief_mip.inc"        // max-intensity projections: k_mip_rows, k_mip_cols
 
 // =============================================================================================
 // C-ABI
@@ -1607,6 +1609,64 @@ int brief_correct_apply(void *out, int elem_bytes, int64_t n, const int64_t *idx
         else
             hipLaunchKernelGGL(k_correct_apply<uint16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (uint16_t *)out, n, idx + k0, q + k0, cnt, m, base);
     }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- max-intensity projections (brief_mip.inc)
+static const int64_t kMipMaxElems = (int64_t)1 << 40;
+static const int64_t kMipMaxAxis = ((int64_t)1 << 31) - 1;
+static int mip_waves(int64_t n, int cap)                           // waves that split a loop of n rows: a power of two, kMipUnroll rows each
+{
+    int w = 1;
+    while (w < cap && (int64_t)w * 2 * kMipUnroll <= n) w *= 2;
+    return w;
+}
+extern "C++" {
+template <typename T>
+static void mip_launch(const void *src, const int64_t *ext, int C, void *mip_d, void *mip_h, void *mip_w, const int64_t *org, const int64_t *frame,
+                       hipStream_t st)
+{
+    constexpr int VEC = 16 / (int)sizeof(T);
+    const int64_t e0 = ext[0], e1 = ext[1], L = ext[2] * C, nseg = (L + 64 * VEC - 1) / (64 * VEC);
+    const int vec = ((uintptr_t)src & 15) == 0 && (L * (int64_t)sizeof(T)) % 16 == 0;
+    const int64_t cap = (int64_t)kCUs * 256;
+    const dim3 g_rows((unsigned)(e1 < cap ? e1 : cap)), b_rows(64 * mip_waves(e0, 8));
+    const T *s = (const T *)src;
+    T *d = (T *)mip_d, *w = (T *)mip_w;
+#define MIP_ROWS(CH) hipLaunchKernelGGL((k_mip_rows<T, CH>), g_rows, b_rows, 0, st, s, e0, e1, L, vec, d, w, org[0], org[1], org[2], frame[1], frame[2])
+    switch (C) {
+    case 1: MIP_ROWS(1); break;
+    case 2: MIP_ROWS(2); break;
+    case 3: MIP_ROWS(3); break;
+    default: MIP_ROWS(4); break;
+    }
+#undef MIP_ROWS
+    const int64_t pieces = e0 * nseg;
+    hipLaunchKernelGGL(k_mip_cols<T>, dim3((unsigned)(pieces < cap ? pieces : cap)), dim3(64 * mip_waves(e1, kMipMaxWaves)), 0, st, s, e0, e1, L, vec,
+                       (T *)mip_h, org[0], org[2], frame[2], C);
+}
+}   // extern "C++"
+
+int brief_mip_accumulate(const void *src, int elem_kind, const int64_t extent[3], int32_t channels, void *mip_d, void *mip_h, void *mip_w,
+                         const int64_t origin[3], const int64_t frame[3], void *stream)
+{
+    if (!src || !extent || !mip_d || !mip_h || !mip_w || !origin || !frame) return fail(BRIEF_ERR_INVALID, "mip: null buffer");
+    if (elem_kind != BRIEF_OUT_U8 && elem_kind != BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "mip: elem_kind must be BRIEF_OUT_U8 (1) or BRIEF_OUT_U16 (2)");
+    if (channels < 1 || channels > 4) return fail(BRIEF_ERR_INVALID, "mip: channels must be 1..4");
+    for (int a = 0; a < 3; ++a) {
+        if (extent[a] < 1 || frame[a] < 1) return fail(BRIEF_ERR_INVALID, "mip: every extent and frame entry must be >= 1");
+        if (frame[a] > kMipMaxAxis) return fail(BRIEF_ERR_INVALID, "mip: a frame entry above 2^31 - 1");
+        if (origin[a] < 0 || origin[a] > frame[a] - extent[a]) return fail(BRIEF_ERR_INVALID, "mip: origin + extent must lie inside the frame (origin >= 0)");
+    }
+    // (every entry is below 2^31 here, so a product of two fits 64 bits)
+    if (extent[0] * extent[1] > kMipMaxElems / (extent[2] * channels) || frame[1] * frame[2] > kMipMaxElems / channels ||
+        frame[0] * frame[2] > kMipMaxElems / channels || frame[0] * frame[1] > kMipMaxElems / channels)
+        return fail(BRIEF_ERR_INVALID, "mip: a box or an image of more than 2^40 elements");
+    if (elem_kind == BRIEF_OUT_U8)
+        mip_launch<uint8_t>(src, extent, channels, mip_d, mip_h, mip_w, origin, frame, (hipStream_t)stream);
+    else
+        mip_launch<uint16_t>(src, extent, channels, mip_d, mip_h, mip_w, origin, frame, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return 0;
 }

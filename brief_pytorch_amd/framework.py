@@ -291,6 +291,22 @@ class NFGR:
         return decompress_divide_region(opt if opt is not None else _wrap(self.opt), orig_sideinfos_path, module_save_dir, sideinfos_save_dir,
                                         region, step, self.device)
 
+    # ---- projection decode: the three max-intensity projections of a region without the volume (brief_pytorch_amd/mip.py)
+    @staticmethod
+    def decompress_mip(opt, module_path, sideinfos, region=None, step=1, device="cuda"):
+        """mip_ops(NFGR.decompress_region(opt, module_path, sideinfos, region, step)) bit for bit, as numpy (mip_d, mip_h, mip_w),
+        decoded chunk by chunk and folded on the device: the volume is never held.  region=None: the whole grid.
+        Decompress.postprocess acts on the images (monotone maps commute with max); see mip.decompress_mip for the envelope."""
+        from . import mip
+        return mip.decompress_mip(opt, module_path, sideinfos, region, step, device)
+
+    def decompress_divide_mip(self, orig_sideinfos_path, module_save_dir, sideinfos_save_dir, region=None, step=1, opt=None):
+        """mip_ops(decompress_divide_region(...)) bit for bit: only the blocks that meet the region are decoded, each folded into
+        the full images at its output offset (mip.decompress_divide_mip)"""
+        from . import mip
+        return mip.decompress_divide_mip(opt if opt is not None else _wrap(self.opt), orig_sideinfos_path, module_save_dir, sideinfos_save_dir,
+                                         region, step, self.device)
+
     # ---- SingleTask encode (main.py:322-454)
     def prepare_fit(self, data_path, data=None, logdir=None):
         """everything main.py:322-384 sets up before the loop: preprocess, loss weights, normalise, size the
@@ -1028,3 +1044,9 @@ class _CubeIndexStream:
         if not hasattr(self, "_local_dev"):
             self._local_dev = self.local.to(self.device)
         return (org[:, :, None] + self._local_dev[None, None, :]).reshape(int(steps), -1).contiguous()
+
+
+def decompress_divide_mip(opt, orig_sideinfos, module_dir, sideinfos_dir, region=None, step=1, device="cuda"):
+    """the three max-intensity projections of a region of a stored DivideTask artefact (mip.decompress_divide_mip); opt: the whole option tree"""
+    from . import mip
+    return mip.decompress_divide_mip(opt, orig_sideinfos, module_dir, sideinfos_dir, region, step, device)

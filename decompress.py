@@ -7,6 +7,12 @@ The artefact kind is read from the directory: a `sideinfos/` directory of blocks
 `sideinfos.yaml` beside `module` a SingleTask one.  2-D data takes `--region y0:y1,x0:x1`.  A part of the region may be
 `a:b`, `a:`, `:b`, `:` or `a:b:s` (numpy slice semantics; out-of-range bounds are refused, not clipped).  `--shape`
 (SingleTask only) evaluates the net on a linspace grid of that spatial shape, and the region indexes that grid.
+
+    python decompress.py -p <run yaml> -c <.../compressed> --region :,:,: --mip -o out.tif
+
+`--mip` writes the three max-intensity projections of the region (out_mip_d.tif, out_mip_h.tif, out_mip_w.tif) instead of the
+region itself: it is decoded chunk by chunk on the GPU and folded into the three images, the volume is never held (3-D uint8 /
+uint16 artefacts; not with `--shape`).
 """
 import argparse
 import os
@@ -24,8 +30,12 @@ def main(argv=None):
     ap.add_argument("--region", required=True, help="z0:z1,y0:y1,x0:x1 (3-D) or y0:y1,x0:x1 (2-D)")
     ap.add_argument("--step", type=int, default=1, help="stride of every axis whose part has none (default 1)")
     ap.add_argument("--shape", default=None, help="D,H,W: decode a resampled view on a grid of this shape (SingleTask)")
+    ap.add_argument("--mip", action="store_true", help="write the region's three max-intensity projections <out>_mip_{d,h,w}<ext> instead of the region")
     ap.add_argument("-o", required=True, help="output file (.tif / .tiff / .npy / .png / .jpg)")
     args = ap.parse_args(argv)
+    if args.mip and args.shape:
+        from brief_pytorch_amd.mip import SHAPE_REFUSAL
+        raise SystemExit("--mip --shape: " + SHAPE_REFUSAL)
 
     import torch
     from brief_pytorch_amd import config
@@ -37,6 +47,8 @@ def main(argv=None):
     region = parse_region(args.region)
     shape = parse_shape(args.shape) if args.shape else None
     divide = os.path.isdir(os.path.join(args.c, "sideinfos"))
+    if args.mip:
+        return _mip(args, opt, region, divide)
     t0 = time.perf_counter()
     if divide:
         if shape is not None:
@@ -51,6 +63,29 @@ def main(argv=None):
     save_img(args.o, data)
     print("%s region %s: shape %s, dtype %s, decoded in %.3f s -> %s" % ("DivideTask" if divide else "SingleTask", args.region,
                                                                           tuple(data.shape), data.dtype, dt, args.o))
+    return 0
+
+
+def _mip(args, opt, region, divide):
+    import torch
+    from brief_pytorch_amd.framework import NFGR, decompress_divide_mip
+    from brief_pytorch_amd.misc import save_mips
+    t0 = time.perf_counter()
+    try:
+        if divide:
+            mips = decompress_divide_mip(opt, os.path.join(args.c, "sideinfos.yaml"), os.path.join(args.c, "module"),
+                                         os.path.join(args.c, "sideinfos"), region, args.step)
+        else:
+            mips = NFGR.decompress_mip(opt, os.path.join(args.c, "module"), os.path.join(args.c, "sideinfos.yaml"), region, args.step)
+    except ValueError as e:                                       # a refusal (2-D data, dtype, normalisation, postprocess, region)
+        raise SystemExit("--mip: %s" % e)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    stem, ext = os.path.splitext(os.path.basename(args.o))
+    save_mips(mips, os.path.dirname(args.o) or ".", stem, ext)
+    print("%s region %s: max-intensity projections d %s, h %s, w %s, dtype %s, decoded in %.3f s -> %s_mip_{d,h,w}%s" % (
+        "DivideTask" if divide else "SingleTask", args.region, tuple(mips[0].shape), tuple(mips[1].shape), tuple(mips[2].shape), mips[0].dtype,
+        dt, os.path.splitext(args.o)[0], ext))
     return 0
 
 

@@ -232,6 +232,19 @@ int brief_correct_emit(const void *dec, const void *src, int elem_bytes, int64_t
 int brief_correct_apply(void *out, int elem_bytes, int64_t n, const int64_t *idx, const int32_t *q, int64_t count, int64_t bound, int64_t base,
                         void *stream);
 
+/* ---- max-intensity projections (csrc/brief_mip.inc) -------------------------------------------------------------------------
+ * fold a dense decoded box src[e0][e1][e2][channels] (uint8 | uint16) into three projection images by elementwise MAX:
+ *   mip_d[I1][I2][c] = max(mip_d, max over axis 0),  mip_h[I0][I2][c] = max(.., axis 1),  mip_w[I0][I1][c] = max(.., axis 2)
+ * the box sits at `origin` inside the image frame `frame` = (I0, I1, I2); images are dense, caller-initialised (0 = identity) */
+/* All three images are read-modify-write, so the chunks of a region and the blocks of a partition can be folded one after another on
+ * one stream (calls that share an image must not run concurrently).  Exact and the same bits on every run; no atomics and no scratch.
+ * Two launches, each reading the box once.  16-byte loads when src is 16-byte aligned and extent[2] * channels * element size is a
+ * multiple of 16.  Limits (BRIEF_ERR_INVALID with a message naming the limit): no null buffer, elem_kind BRIEF_OUT_U8 | BRIEF_OUT_U16,
+ * channels 1 .. 4, every extent and frame entry >= 1 (frame entries <= 2^31 - 1), origin >= 0 and origin + extent <= frame on every
+ * axis, the box and each image at most 2^40 elements. */
+int brief_mip_accumulate(const void *src, int elem_kind /* BRIEF_OUT_U8 | BRIEF_OUT_U16 */, const int64_t extent[3], int32_t channels,
+                         void *mip_d, void *mip_h, void *mip_w, const int64_t origin[3], const int64_t frame[3], void *stream);
+
 /* cal_ssim of utils/misc.py:458-475 for single-channel uint16 volumes [D,H,W]: per z-slice 2-D SSIM (utils/ssim.py:
  * 11-tap Gaussian `window11`, valid padding, K=(0.01,0.03)).  Writes one double per 16x64 output tile, slice-major
  * (brief_ssim_partial_count of them; tiles of slice z are contiguous); slice mean = sum of its tiles / ((H-10)(W-10)),
