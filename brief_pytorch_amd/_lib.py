@@ -79,6 +79,13 @@ class MfnFitJob(C.Structure):       # brief_mfn_fit_job: brief_fit_job's fields 
     _fields_ = [("desc", MfnDesc)] + FitJob._fields_[1:]
 
 
+QUANT_MAX_TENSORS = 64             # BRIEF_QUANT_MAX_TENSORS
+
+
+class QuantSpan(C.Structure):       # brief_quant_span
+    _fields_ = [("offset", C.c_int64), ("count", C.c_int64)]
+
+
 TAPER_MAX_LAYERS = 16              # BRIEF_TAPER_MAX_LAYERS
 
 
@@ -106,7 +113,8 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_optim_step", "brief_sample_indices", "brief_sse_u16", "brief_profile_enable", "brief_profile_fused", "brief_deblock_edge", "brief_ssim_u16", "brief_ssim_partial_count",
            "brief_sincos_probe", "brief_cu_count",
            "brief_correct_chunk_elems", "brief_correct_count", "brief_correct_emit", "brief_correct_apply",
-           "brief_mip_accumulate"] \
+           "brief_mip_accumulate",
+           "brief_quant_workspace_bytes", "brief_quant_ranges", "brief_quant_apply", "brief_quant_decode"] \
     + ["brief_%s_%s" % (prefix, entry) for prefix, _, _ in FAMILIES for entry in FAMILY_ENTRIES]
 
 
@@ -209,6 +217,12 @@ def lib():
     L.brief_correct_apply.argtypes = [vp, C.c_int, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp]
     i3 = C.POINTER(C.c_int64)
     L.brief_mip_accumulate.argtypes = [vp, C.c_int, i3, C.c_int32, vp, vp, vp, i3, i3, vp]
+    sp = C.POINTER(QuantSpan)
+    L.brief_quant_workspace_bytes.restype = C.c_int64
+    L.brief_quant_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+    L.brief_quant_ranges.argtypes = [vp, sp, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp]
+    L.brief_quant_apply.argtypes = [vp, sp, C.c_int32, C.c_int32, vp, vp, vp, vp]
+    L.brief_quant_decode.argtypes = [vp, sp, C.c_int32, vp, vp, vp]
     _LIB = L
     return L
 

@@ -37,6 +37,7 @@
 //   k_sample, k_sse_u16, k_ssim_u16, k_deblock_edge: index stream, metrics and the deblocking filter.
 //   brief_correct.inc  k_correct_count / k_correct_emit / k_correct_apply: the stored corrections of the error-bounded mode.
 //   brief_mip.inc      k_mip_rows / k_mip_cols: max-intensity projections of a decoded box, folded into three images.
+//   brief_quant.inc    k_quant_minmax / k_quant_fold / k_quant_apply / k_quant_decode: the 2..16-bit weight quantiser of the quantised artefact.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
@@ -63,6 +64,7 @@
 #include "brief_taper.inc"      // tapered SIRENs: k_taper_fwd, k_taper_wgrad, k_taper_repack
 #include "brief_correct.inc"    // error-bounded mode: k_correct_count, k_correct_emit, k_correct_apply
 #include "brief_mip.inc"        // max-intensity projections: k_mip_rows, k_mip_cols
+#include "brief_quant.inc"      // weight quantisation: k_quant_minmax, k_quant_fold, k_quant_apply, k_quant_decode
 
 // =============================================================================================
 // C-ABI
@@ -1667,6 +1669,99 @@ int brief_mip_accumulate(const void *src, int elem_kind, const int64_t extent[3]
         mip_launch<uint8_t>(src, extent, channels, mip_d, mip_h, mip_w, origin, frame, (hipStream_t)stream);
     else
         mip_launch<uint16_t>(src, extent, channels, mip_d, mip_h, mip_w, origin, frame, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- weight quantisation (brief_quant.inc)
+static const int64_t kQuantMaxElems = (int64_t)1 << 40;
+// the caller's spans, checked and in offset order, as kernel arguments: with_gaps adds the gaps between them as segments of their own
+// (tensor = -1); `chunk` is the launch's elements per workgroup
+static int quant_segments(const brief_quant_span *tensors, int32_t ntensors, bool with_gaps, int chunk, QuantSegs *q)
+{
+    if (ntensors < 1 || ntensors > BRIEF_QUANT_MAX_TENSORS) return fail(BRIEF_ERR_INVALID, "quantise: ntensors must be 1..64");
+    if (!tensors) return fail(BRIEF_ERR_INVALID, "quantise: null buffer");
+    int order[BRIEF_QUANT_MAX_TENSORS];
+    for (int i = 0; i < ntensors; ++i) {
+        if (tensors[i].count < 1) return fail(BRIEF_ERR_INVALID, "quantise: every span must hold at least one element (count >= 1)");
+        if (tensors[i].offset < 0) return fail(BRIEF_ERR_INVALID, "quantise: a span with a negative offset");
+        if (tensors[i].count > kQuantMaxElems || tensors[i].offset > kQuantMaxElems - tensors[i].count)
+            return fail(BRIEF_ERR_INVALID, "quantise: a span must end at or below element 2^40");
+        int k = i;                                                 // insertion sort by offset
+        while (k > 0 && tensors[order[k - 1]].offset > tensors[i].offset) { order[k] = order[k - 1]; --k; }
+        order[k] = i;
+    }
+    memset(q, 0, sizeof(*q));
+    int n = 0;
+    int64_t chunks = 0, end = 0;
+    for (int i = 0; i < ntensors; ++i) {
+        const brief_quant_span &t = tensors[order[i]];
+        if (i > 0 && t.offset < end) return fail(BRIEF_ERR_INVALID, "quantise: overlapping spans");
+        if (i > 0 && with_gaps && t.offset > end) {
+            q->off[n] = end; q->cnt[n] = t.offset - end; q->tensor[n] = -1; q->first_chunk[n] = (int32_t)chunks;
+            chunks += (q->cnt[n] + chunk - 1) / chunk; ++n;
+        }
+        q->off[n] = t.offset; q->cnt[n] = t.count; q->tensor[n] = (int16_t)order[i]; q->first_chunk[n] = (int32_t)chunks;
+        chunks += (t.count + chunk - 1) / chunk; ++n;
+        end = t.offset + t.count;
+        if (chunks > 0x7fffffff) return fail(BRIEF_ERR_INVALID, "quantise: more chunks than one launch holds");
+    }
+    q->first_chunk[n] = (int32_t)chunks;
+    q->n = n;
+    return 0;
+}
+static int check_quant_bits(int32_t bits)
+{
+    return bits < 2 || bits > 16 ? fail(BRIEF_ERR_INVALID, "quantise: bits must be 2..16") : 0;
+}
+
+int64_t brief_quant_workspace_bytes(int64_t total_count, int32_t ntensors)
+{
+    if (total_count < 1 || ntensors < 1 || ntensors > BRIEF_QUANT_MAX_TENSORS) return -1;
+    return (total_count / kQuantRangeChunk + ntensors) * (int64_t)sizeof(float2);      // >= the chunks of any such table: one partial each
+}
+
+int brief_quant_ranges(const float *params, const brief_quant_span *tensors, int32_t ntensors, int32_t bits, float *lo_step, void *workspace,
+                       int64_t workspace_bytes, void *stream)
+{
+    if (int rc = check_quant_bits(bits)) return rc;
+    QuantSegs q;
+    if (int rc = quant_segments(tensors, ntensors, false, kQuantRangeChunk, &q)) return rc;
+    if (!params || !lo_step || !workspace) return fail(BRIEF_ERR_INVALID, "quantise: null buffer");
+    if (((uintptr_t)params & 3) || ((uintptr_t)lo_step & 7) || ((uintptr_t)workspace & 7))
+        return fail(BRIEF_ERR_INVALID, "quantise: params must be 4-byte, lo_step and the workspace 8-byte aligned");
+    const int chunks = q.first_chunk[q.n];
+    if (workspace_bytes < (int64_t)chunks * (int64_t)sizeof(float2))
+        return fail(BRIEF_ERR_WORKSPACE, "quantise: workspace too small (brief_quant_workspace_bytes)");
+    hipLaunchKernelGGL(k_quant_minmax, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream, q, params, (float2 *)workspace);
+    hipLaunchKernelGGL(k_quant_fold, dim3((unsigned)q.n), dim3(64), 0, (hipStream_t)stream, q, (const float2 *)workspace, (int)bits, (float2 *)lo_step);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_quant_apply(const float *params, const brief_quant_span *tensors, int32_t ntensors, int32_t bits, const float *lo_step, float *qparams,
+                      uint16_t *codes, void *stream)
+{
+    if (int rc = check_quant_bits(bits)) return rc;
+    QuantSegs q;
+    if (int rc = quant_segments(tensors, ntensors, true, kQuantApplyChunk, &q)) return rc;
+    if (!params || !lo_step || (!qparams && !codes)) return fail(BRIEF_ERR_INVALID, "quantise: null buffer");
+    if (((uintptr_t)params & 3) || ((uintptr_t)qparams & 3) || ((uintptr_t)codes & 1) || ((uintptr_t)lo_step & 7))
+        return fail(BRIEF_ERR_INVALID, "quantise: params / qparams must be 4-byte, codes 2-byte and lo_step 8-byte aligned");
+    hipLaunchKernelGGL(k_quant_apply, dim3((unsigned)q.first_chunk[q.n]), dim3(256), 0, (hipStream_t)stream, q, params, (int)bits, (const float2 *)lo_step,
+                       qparams, codes);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_quant_decode(const uint16_t *codes, const brief_quant_span *tensors, int32_t ntensors, const float *lo_step, float *params_out, void *stream)
+{
+    QuantSegs q;
+    if (int rc = quant_segments(tensors, ntensors, false, kQuantApplyChunk, &q)) return rc;
+    if (!codes || !lo_step || !params_out) return fail(BRIEF_ERR_INVALID, "quantise: null buffer");
+    if (((uintptr_t)params_out & 3) || ((uintptr_t)codes & 1) || ((uintptr_t)lo_step & 7))
+        return fail(BRIEF_ERR_INVALID, "quantise: params_out must be 4-byte, codes 2-byte and lo_step 8-byte aligned");
+    hipLaunchKernelGGL(k_quant_decode, dim3((unsigned)q.first_chunk[q.n]), dim3(256), 0, (hipStream_t)stream, q, codes, (const float2 *)lo_step, params_out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -81,8 +81,11 @@ def _is_siren(module):
 class Fitter:
     def __init__(self, module, targets, dims, coords_range=(-1.0, 1.0), weights=None, sampler="randompoint",
                  sample_size=100000, optimizer="Adamax", lr=1e-3, scheduler=None, loss="datal2", thr=0.0, beta=0.01,
-                 seed=42, index_stream=None):
+                 seed=42, index_stream=None, quantize=None):
+        """quantize = (bits, first_step): run() takes every optimizer step after step `first_step` on the quantised weights
+        (run_quantised); None: never."""
         self.m = module
+        self.quantize = None if quantize is None else (int(quantize[0]), int(quantize[1]))
         for what, t in (("targets", targets), ("weights", weights)):
             # the kernels read these through raw pointers as contiguous f32 (a float64 weight map, e.g. parse_weight's
             # 'exp_x_v' on integer data, would be silently reinterpreted)
@@ -192,6 +195,12 @@ class Fitter:
         sampler or a replayed stream is attached): same results, bit for bit, as calling step() that many times.  Returns
         the device loss of the last step, or the per-step loss tensor if log."""
         steps, logs = int(steps), []
+        if self.quantize is not None:
+            plain = min(max(self.quantize[1] - self.t, 0), steps)      # steps of this call in front of the quantised phase
+            if plain < steps:
+                head = self.run(plain, log) if plain > 0 else None     # (plain <= quantize[1] - t: that call stays plain)
+                tail = self.run_quantised(steps - plain, self.quantize[0], log)
+                return (torch.cat([head, tail]) if head is not None else tail) if log else tail
         while True:
             k = min(steps, self.max_steps_per_call())
             j, loss_log = self.job(k, log)
@@ -204,6 +213,36 @@ class Fitter:
             if steps <= 0:
                 break
         return (torch.cat(logs) if len(logs) > 1 else logs[0]) if log else self.m._loss
+
+    def run_quantised(self, steps, bits, log=False):
+        """`steps` optimizer steps on the QUANTISED weights with a straight-through update of the fp32 masters: forward and backward
+        see deq(code(params)) (every tensor quantised with its range of that moment, `bits` bits), the gradient is applied to params
+        unchanged.  Step counter, lr schedule, optimizer state and sample stream continue from where run() / step() left them.  Each
+        step is five enqueue-only calls on the current stream, nothing crosses to the host:
+            brief_quant_ranges, brief_quant_apply -> qparams, the net's repack (qparams -> packed), the net's train_step on packed,
+            brief_optim_step on params.
+        Afterwards the fragment-ordered copy is marked stale, so the next decode or plain step rebuilds it from the masters.
+        Returns the device loss of the last step, or the per-step loss tensor if log."""
+        m, L = self.m, _lib.lib()
+        steps = int(steps)
+        m._require_gpu()
+        loss_log = torch.zeros(max(steps, 1), dtype=torch.float32, device=m.params.device) if log else None
+        grid = (self.dims, self.range[0], self.range[1])
+        rnd = self.sampler == "randompoint" and self.index_stream is None
+        for k in range(steps):
+            t = self.t + 1
+            m.pack_from(m.fake_quantise(bits))
+            idx = self.index_stream(t) if self.index_stream is not None else None
+            m.train_step(self.n, self.targets, idx=idx, weights=self.weights, grid=grid, loss=self.loss_name, thr=self.thr, beta=self.beta,
+                         rng=(self.pop, self.seed, t) if rnd else None)
+            b1 = self.beta1_at(t)
+            _lib.check(L.brief_optim_step(self.opt, _lib.ptr(m.params), _lib.ptr(m.grads), _lib.ptr(self.s1), _lib.ptr(self.s2), m.params.numel(),
+                                          self.lr_at(t), 0.9 if b1 is None else b1, 0.999, 1e-8, t, _lib.stream_ptr()))
+            if log:
+                loss_log[k:k + 1].copy_(m._loss)
+            self.t = t
+        m.mark_packed_stale()
+        return loss_log[:steps] if log else m._loss
 
     def step(self):
         """one optimisation step; returns the device loss tensor (no sync)."""
@@ -241,6 +280,13 @@ class MultiFitter:
             return res
         if not self.fitters:
             return []
+        # the quantised fine-tune runs fitter by fitter on the single-net path; the steps in front of it stay co-trained
+        quant = [f.quantize[1] - f.t for f in self.fitters if f.quantize is not None]
+        if quant and min(quant) < int(steps):
+            plain = max(min(quant), 0)
+            head = self.run(plain, log) if plain > 0 else None
+            tail = [f.run(int(steps) - plain, log) for f in self.fitters]
+            return [torch.cat([h, t]) for h, t in zip(head, tail)] if (log and head is not None) else tail
         steps, logs = int(steps), [[] for _ in self.fitters]
         while True:
             share = sum(1 for f in self.fitters if f.index_stream is not None)

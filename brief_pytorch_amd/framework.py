@@ -18,7 +18,7 @@ from os.path import splitext as ops
 import numpy as np
 import torch
 
-from . import _lib, config, corrections
+from . import _lib, config, corrections, quantize
 from . import region as region_mod
 from .fit import Fitter
 from .io import (get_folder_size, get_type_max, invnormalize_data, minmaxany_range, normalize_data, normalize_data_device, range_limit, save_yaml,
@@ -87,6 +87,8 @@ class NFGR:
             self.precision = "bf16"
         if opt.Compress.loss.name not in ("datal2", "datasmoothl1"):
             raise NotImplementedError(opt.Compress.loss.name)
+        # optional key of this build: {bits, finetune_steps} — the artefact is module/quantized.bin (quantize.py); refused here, before any work
+        self.quantize = quantize_of(opt)
         if not opt.Compress.gpu or not torch.cuda.is_available():
             raise _lib.BriefError("NFGR on this build runs on a ROCm GPU only (Compress.gpu must be true); there is no CPU fallback")
         self.device = "cuda"
@@ -141,7 +143,13 @@ class NFGR:
         (init_module, the DivideTask cost model, sideinfos phi_name) sees the net that is really built."""
         if opt.Module.phi.name not in ALL_CALC_PHI_FEATURES:
             raise NotImplementedError("Module.phi.name=%r" % opt.Module.phi.name)
-        ideal = ideal_module_size / (2.0 if opt.Compress.half else 4.0)
+        quant = quantize_of(opt)
+        if quant is not None:
+            # bits / 8 bytes per parameter behind the file's header and tensor table
+            overhead = quantize.overhead_bytes(opt.Module.phi.layers)
+            ideal = (ideal_module_size - overhead) * 8.0 / quant[0]
+        else:
+            ideal = ideal_module_size / (2.0 if opt.Compress.half else 4.0)
         if opt.Module.phi.name == "SIREN_Pyramid" and NFGR._under_floor(opt, "SIREN_Pyramid", ideal):
             opt.Module.phi.name = "SIRENFT"
             opt.Module.phi.features_plus = opt.Module.phi.features_dis
@@ -153,6 +161,8 @@ class NFGR:
         feats = ALL_CALC_PHI_FEATURES[name](param_count=ideal, **{k: v for k, v in opt.Module.phi.items() if k != "name"})
         kw = {k: v for k, v in opt.Module.phi.items() if k not in ("name", "features")}
         actual = ALL_CALC_PHI_PARAM_COUNT[name](features=feats, **kw)
+        if quant is not None:
+            return feats, actual, float(quantize.code_bytes(actual, quant[0]) + overhead)
         return feats, actual, actual * (2.0 if opt.Compress.half else 4.0)
 
     def prepare_module(self, ideal_module_size):
@@ -341,6 +351,8 @@ class NFGR:
             sideinfos["phi_precision"] = getattr(self, "module_precision", self.precision)      # extra key only off the reference's fp32 path: what THIS net was fitted in
         if bound is not None:
             sideinfos["error_bound"] = bound      # extra key only in the error-bounded mode: a decoder that sees it insists on the corrections file
+        if self.quantize is not None:
+            sideinfos["quantize"] = {"bits": self.quantize[0], "tensors": 2 * len(phi.net)}      # extra key only with Compress.quantize
         dims = list(pre.shape[:-1])
         cout = pre.shape[-1]
         tgt = tgt_dev.reshape(-1, cout)
@@ -379,7 +391,9 @@ class NFGR:
         n_step = C_.sampler.sample_size if index_stream is None else index_stream.n
         fit = Fitter(phi, tgt, dims, _coords_range(C_.coords_mode), weights=wts, sampler=sampler, sample_size=n_step,
                      optimizer=C_.optimizer_name_phi, lr=C_.lr_phi, scheduler=config.to_plain(C_.lr_scheduler_phi),
-                     loss=C_.loss.name, thr=thr, beta=C_.loss.beta, seed=getattr(opt, "_seed", 42), index_stream=index_stream)
+                     loss=C_.loss.name, thr=thr, beta=C_.loss.beta, seed=getattr(opt, "_seed", 42), index_stream=index_stream,
+                     # the last finetune_steps of max_steps run on the quantised weights (Fitter.run_quantised)
+                     quantize=(self.quantize[0], int(C_.max_steps) - self.quantize[1]) if (self.quantize and self.quantize[1] > 0) else None)
         self.sideinfos = sideinfos
         return {"fit": fit, "phi": phi, "data": data, "data_path": data_path, "logdir": logdir, "name": name, "ext": ext,
                 "sideinfos": sideinfos, "theory_size": theory_size, "results": {},
@@ -394,7 +408,7 @@ class NFGR:
         os.makedirs(cdir, exist_ok=True)
         module_path, side_path = opj(cdir, "module"), opj(cdir, "sideinfos.yaml")
         save_yaml(sideinfos, side_path)
-        save_model(ctx["phi"], module_path, self.device)
+        save_model(ctx["phi"], module_path, self.device, quantize_bits=self.quantize[0] if self.quantize else None)      # (the master weights as they are now)
         bound, corr_bytes, dec_t = error_bound_of(opt), 0, None
         if bound is not None:
             # error-bounded mode, whether or not this checkpoint is evaluated: decode what was just written, store a correction for
@@ -835,6 +849,33 @@ class NFGR:
 
 
 # ------------------------------------------------------------------------------------------ helpers
+def quantize_of(cf):
+    """Compress.quantize of a CompressFramework option tree: None (absent, null or 'none': off) or (bits, finetune_steps), checked.
+    Refused by name: a net whose artefact is not SIREN's weight-file directory, a low-precision fit, bits outside 2..16, finetune_steps
+    negative or above max_steps."""
+    q = cf.Compress.get("quantize", None)
+    if q is None or (isinstance(q, str) and q.lower() == "none"):
+        return None
+    if not isinstance(q, dict) or "bits" not in q:
+        raise ValueError("Compress.quantize must be {bits: 2..16, finetune_steps: n >= 0} or none (got %r)" % (q,))
+    name = cf.Module.phi.name
+    if name not in quantize.NETS:
+        raise NotImplementedError("Compress.quantize supports %s (the weight-file artefact with SIREN's layers); Module.phi.name=%s has another "
+                                  "artefact layout" % (", ".join(quantize.NETS), name))
+    precision = str(cf.Compress.get("precision", "fp32"))
+    if cf.Compress.half or precision not in ("fp32", "f32"):
+        raise ValueError("Compress.quantize needs an fp32 fit: Compress.half must be false and Compress.precision fp32 (got half=%s precision=%s)"
+                         % (bool(cf.Compress.half), precision))
+    bits = quantize.check_bits(q["bits"])
+    ft = q.get("finetune_steps", 0)
+    ft = 0 if ft is None else ft
+    if isinstance(ft, bool) or not isinstance(ft, int) or ft < 0:
+        raise ValueError("Compress.quantize.finetune_steps must be an integer >= 0 (got %r)" % (ft,))
+    if ft > int(cf.Compress.max_steps):
+        raise ValueError("Compress.quantize.finetune_steps=%d exceeds Compress.max_steps=%d" % (ft, int(cf.Compress.max_steps)))
+    return bits, ft
+
+
 def error_bound_of(cf):
     """Compress.error_bound of a CompressFramework option tree: None (off) or the bound in grey levels of the source dtype"""
     return corrections.parse_bound(cf.Compress.get("error_bound", None))

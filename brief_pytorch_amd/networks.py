@@ -15,7 +15,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import _lib, region
+from . import _lib, quantize, region
 
 __all__ = ["SIREN", "FFN", "NeRF", "MFNFourier", "MFNGabor", "SIREN_Pyramid", "SIRENFT", "SIRENPS", "init_phi", "ALLPHI", "ALL_CALC_PHI_FEATURES", "ALL_CALC_PHI_PARAM_COUNT",
            "ALL_CHECK_PARAM_COUNT", "get_nnmodule_param_count"]
@@ -134,6 +134,7 @@ class SIREN:
         self.params = self._reference_init()          # CPU until .to(device)
         self.grads = None
         self.packed = None
+        self.qparams = None
         self._stale = True
         self._seen_version = -1
         self._autograd = False
@@ -195,6 +196,7 @@ class SIREN:
             self.params = self.params.to(device)
             self.grads = None
             self.packed = None
+            self.qparams = None
             self._ws = self._fws = None
             self._stale = True
         return self
@@ -376,9 +378,10 @@ class SIREN:
         return out
 
     def train_step(self, n, targets, idx=None, coords=None, weights=None, grid=None, offset=0,
-                   loss="datal2", thr=0.0, beta=0.01, want_yhat=False):
+                   loss="datal2", thr=0.0, beta=0.01, want_yhat=False, rng=None):
         """zero_grad + forward + loss + backward of main.py:385-396 for one batch of n samples.
-        Fills self.grads (canonical layout) and returns (loss [1] device tensor, yhat or None)."""
+        Fills self.grads (canonical layout) and returns (loss [1] device tensor, yhat or None).
+        rng = (pop, seed, step) with neither idx nor coords: the samples are drawn inside the kernel, as fit_step draws them."""
         self._require_gpu()
         self.sync_packed()
         dev = self.params.device
@@ -397,7 +400,7 @@ class SIREN:
             g = self._grid(dims, lo, hi)
         b = _lib.BatchDesc(_dev_ptr(coords, torch.float32, "coords", dev), _dev_ptr(targets, torch.float32, "targets", dev),
                            _dev_ptr(weights, torch.float32, "weights", dev), _dev_ptr(idx, torch.int64, "idx", dev),
-                           int(offset), int(n), 0, 0, 0)
+                           int(offset), int(n), *((int(v) for v in rng) if (rng is not None and idx is None and coords is None) else (0, 0, 0)))
         _lib.check(self._abi_train_step(g, b, _lib.LOSS_KIND[loss], thr, beta, yhat))
         return self._loss, yhat
 
@@ -434,12 +437,59 @@ class SIREN:
         if self._ws is None or self._ws.numel() * 4 < need:
             self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
 
+    # ---- quantised weights (quantize.py; kernels: csrc/brief_quant.inc)
+    def quant_spans(self):
+        """the net's tensors (every weight matrix and every bias, in canonical order) as brief_quant_span's"""
+        spans, off = [], 0
+        for (o, i) in self._shapes:
+            spans += [(off, o * i), (off + o * i, o)]
+            off += o * i + o
+        return (_lib.QuantSpan * len(spans))(*spans)
+
+    def fake_quantise(self, bits):
+        """self.qparams = deq(code(self.params)), every tensor with its own range, on the device (brief_quant_ranges +
+        brief_quant_apply: three launches, nothing crosses to the host): what an artefact written now with `bits` bits decodes to.
+        Returns self.qparams (canonical layout; allocated once)."""
+        self._require_gpu()
+        if getattr(type(self), "kind", "SIREN") not in quantize.NETS:
+            raise _lib.BriefError("quantised weights exist for %s only (this net is %s)" % (", ".join(quantize.NETS), type(self).kind))
+        if self.precision not in ("fp32", "f32"):
+            raise _lib.BriefError("quantised weights need an fp32 net (this one runs in %s)" % self.precision)
+        L = _lib.lib()
+        if getattr(self, "_qspans", None) is None or self.qparams is None or self.qparams.device != self.params.device:
+            self._qspans = self.quant_spans()
+            n = len(self._qspans)
+            if n > _lib.QUANT_MAX_TENSORS:
+                raise _lib.BriefError("quantised weights: at most %d tensors (this net has %d)" % (_lib.QUANT_MAX_TENSORS, n))
+            self.qparams = torch.empty_like(self.params)
+            self._qlo_step = torch.empty((n, 2), dtype=torch.float32, device=self.params.device)
+            self._qws = torch.empty(L.brief_quant_workspace_bytes(self.params.numel(), n) // 4, dtype=torch.float32, device=self.params.device)
+        n = len(self._qspans)
+        _lib.check(L.brief_quant_ranges(_lib.ptr(self.params), self._qspans, n, int(bits), _lib.ptr(self._qlo_step), _lib.ptr(self._qws),
+                                        self._qws.numel() * 4, _lib.stream_ptr()))
+        _lib.check(L.brief_quant_apply(_lib.ptr(self.params), self._qspans, n, int(bits), _lib.ptr(self._qlo_step), _lib.ptr(self.qparams), None,
+                                       _lib.stream_ptr()))
+        return self.qparams
+
+    def pack_from(self, src):
+        """the fragment-ordered copy rebuilt from `src` (canonical layout, e.g. self.qparams) instead of the master parameters; it stays
+        that way until the parameters change through torch or .data, or mark_packed_stale() is called"""
+        self._require_gpu()
+        if self.packed is None:
+            self.sync_packed()
+        _lib.check(self._abi_repack(src))
+        self._stale = False
+        self._seen_version = self.params._version
+
+    def mark_packed_stale(self):
+        self._stale = True
+
     # ---- the C-ABI entries of this net kind (_FusedFamily overrides them)
     def _abi_packed_count(self):
         return _lib.lib().brief_packed_count(C.byref(self.desc))
 
-    def _abi_repack(self):
-        return _lib.lib().brief_siren_repack(C.byref(self.desc), _lib.ptr(self.params), _lib.ptr(self.packed), _lib.stream_ptr())
+    def _abi_repack(self, src=None):
+        return _lib.lib().brief_siren_repack(C.byref(self.desc), _lib.ptr(self.params if src is None else src), _lib.ptr(self.packed), _lib.stream_ptr())
 
     def _abi_forward(self, grid, batch, out, kind, scale, vrange, n):
         ws, ws_bytes = self._forward_scratch(n)
@@ -519,8 +569,8 @@ class _FusedFamily(SIREN):
     def _abi_packed_count(self):
         return self._entry("packed_count")(C.byref(self.desc))
 
-    def _abi_repack(self):
-        return self._entry("repack")(C.byref(self.desc), _lib.ptr(self.params), _lib.ptr(self.packed), _lib.stream_ptr())
+    def _abi_repack(self, src=None):
+        return self._entry("repack")(C.byref(self.desc), _lib.ptr(self.params if src is None else src), _lib.ptr(self.packed), _lib.stream_ptr())
 
     def _abi_forward(self, grid, batch, out, kind, scale, vrange, n):
         return self._entry("forward")(C.byref(self.desc), _lib.ptr(self.packed), C.byref(grid) if grid is not None else None,
@@ -604,6 +654,7 @@ class FFN(_FusedFamily):
         self.params = self._reference_init()
         self.grads = None
         self.packed = None
+        self.qparams = None
         self._stale = True
         self._seen_version = -1
         self._autograd = False
@@ -704,6 +755,7 @@ class NeRF(_FusedFamily):
         self.params = self._reference_init()
         self.grads = None
         self.packed = None
+        self.qparams = None
         self._stale = True
         self._seen_version = -1
         self._autograd = False
@@ -817,6 +869,7 @@ class _MFNBase(_FusedFamily):
         self.params = self._reference_init()
         self.grads = None
         self.packed = None
+        self.qparams = None
         self._stale = True
         self._seen_version = -1
         self._autograd = False
@@ -980,6 +1033,7 @@ class _TaperBase(_FusedFamily):
         self.params = SIREN._reference_init(self)
         self.grads = None
         self.packed = None
+        self.qparams = None
         self._stale = True
         self._seen_version = -1
         self._autograd = False

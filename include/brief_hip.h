@@ -245,6 +245,36 @@ int brief_correct_apply(void *out, int elem_bytes, int64_t n, const int64_t *idx
 int brief_mip_accumulate(const void *src, int elem_kind /* BRIEF_OUT_U8 | BRIEF_OUT_U16 */, const int64_t extent[3], int32_t channels,
                          void *mip_d, void *mip_h, void *mip_w, const int64_t origin[3], const int64_t frame[3], void *stream);
 
+/* ---- weight quantisation (csrc/brief_quant.inc, csrc/brief_quant.h) ----------------------------------------------------------
+ * The quantiser of the quantised artefact (module/quantized.bin) and of the quantised fine-tune: uniform, affine, per tensor, every
+ * fp32 operation rounded on its own (nothing fused), so that plain numpy float32 arithmetic gives the same bits:
+ *     lo = min(w); hi = max(w); top = 2^bits - 1;  step = (hi - lo) / top
+ *     code = clamp(rint((w - lo) / step), 0, top)   (rint: ties to even; step == 0: code = 0);   deq = code * step + lo
+ * A tensor is a span {offset, count} (elements) of the canonical parameter buffer; `tensors` is a HOST array of ntensors spans, in
+ * any order, which travels by value in the kernel arguments.  lo_step: device float [ntensors][2] = (lo, step) per tensor, in the
+ * order of `tensors`.  Every call only enqueues on `stream`; there are no atomics and nothing crosses to the host.
+ *   brief_quant_workspace_bytes  scratch of brief_quant_ranges for spans of total_count elements altogether in ntensors tensors;
+ *   brief_quant_ranges           two launches: a partial (min, max) per 16 Ki-element chunk of a tensor, then lo and step per tensor;
+ *   brief_quant_apply            one launch: qparams[i] = deq(code(params[i])) (float, canonical layout; may be NULL) and codes[i] =
+ *                                code(params[i]) (uint16 per element, canonical layout; may be NULL) for every element of a span.
+ *                                Elements of a GAP between two spans are copied through to qparams unchanged (their codes are left
+ *                                alone); nothing in front of the first span or behind the last one is read or written;
+ *   brief_quant_decode           one launch: params_out[i] = deq(codes[i]) for every element of a span (gaps are left alone).
+ * Limits (BRIEF_ERR_INVALID with a message naming the limit): no null buffer (apply: at least one of qparams / codes), bits 2 .. 16,
+ * ntensors 1 .. BRIEF_QUANT_MAX_TENSORS, every span count >= 1 and offset >= 0 with offset + count <= 2^40, no two spans overlapping;
+ * a workspace smaller than brief_quant_workspace_bytes: BRIEF_ERR_WORKSPACE. */
+#define BRIEF_QUANT_MAX_TENSORS 64
+typedef struct {
+    int64_t offset, count;
+} brief_quant_span;
+int64_t brief_quant_workspace_bytes(int64_t total_count, int32_t ntensors);
+int brief_quant_ranges(const float *params, const brief_quant_span *tensors, int32_t ntensors, int32_t bits, float *lo_step,
+                       void *workspace, int64_t workspace_bytes, void *stream);
+int brief_quant_apply(const float *params, const brief_quant_span *tensors, int32_t ntensors, int32_t bits, const float *lo_step,
+                      float *qparams, uint16_t *codes, void *stream);
+int brief_quant_decode(const uint16_t *codes, const brief_quant_span *tensors, int32_t ntensors, const float *lo_step,
+                       float *params_out, void *stream);
+
 /* cal_ssim of utils/misc.py:458-475 for single-channel uint16 volumes [D,H,W]: per z-slice 2-D SSIM (utils/ssim.py:
  * 11-tap Gaussian `window11`, valid padding, K=(0.01,0.03)).  Writes one double per 16x64 output tile, slice-major
  * (brief_ssim_partial_count of them; tiles of slice z are contiguous); slice mean = sum of its tiles / ((H-10)(W-10)),

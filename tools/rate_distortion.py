@@ -6,11 +6,19 @@
 For every compression ratio the network width is solved from the byte budget exactly as NFGR does
 (utils/Networks.py:299-314 -> SIREN.calc_features), the fit runs through the fused path (Fitter ==
 main.py:385-400 with the randompoint sampler of main.py:126-163) and the decoded uint16 volume is scored on
-the device (brief_sse_u16 / brief_ssim_u16).  bits/voxel = 32 P / voxels (fp32 weights, side info excluded).
+the device (brief_sse_u16 / brief_ssim_u16).  Every scored decode is the decode of the WRITTEN artefact, loaded into a fresh net;
+bits/voxel = 8 x the written directory's bytes / voxels (side info excluded).
+
+    python tools/rate_distortion.py --size 256 --steps 20000 --ratios 256 64 --quantize-bits 12 --finetune-steps 2000
+
+--quantize-bits B writes module/quantized.bin (B-bit codes; the width is solved from the same byte budget by NFGR's rule for quantised
+artefacts, so a B-bit net has about 32 / B times the parameters); --finetune-steps N runs the last N of max(--steps) on the quantised
+weights (Fitter.run_quantised).
 """
 import argparse
 import os
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -18,7 +26,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from brief_pytorch_amd import _lib                           # noqa: E402
-from brief_pytorch_amd import metrics                        # noqa: E402
+from brief_pytorch_amd import metrics, quantize              # noqa: E402
+from brief_pytorch_amd.io import get_folder_size             # noqa: E402
+from brief_pytorch_amd.modelsave import load_model, save_model   # noqa: E402
 from brief_pytorch_amd.fit import Fitter                     # noqa: E402
 from brief_pytorch_amd.networks import SIREN                 # noqa: E402
 from brief_pytorch_amd.synthetic import make_volume_torch    # noqa: E402
@@ -36,8 +46,15 @@ def main():
     ap.add_argument("--ssim", action="store_true")
     ap.add_argument("--precision", choices=["fp32", "bf16"], default="fp32")
     ap.add_argument("--detail", type=int, default=64, help="1/f texture components added to the synthetic field (0 = the bench volume)")
+    ap.add_argument("--quantize-bits", type=int, default=0, help="2..16: the artefact is quantized.bin with this many bits per weight (0: fp32 weight files)")
+    ap.add_argument("--finetune-steps", type=int, default=0, help="with --quantize-bits: the last N of max(--steps) run on the quantised weights")
     ap.add_argument("--out", type=str, default="")
     a = ap.parse_args()
+    bits = quantize.check_bits(a.quantize_bits) if a.quantize_bits else None
+    if a.finetune_steps and (bits is None or not 0 <= a.finetune_steps <= max(a.steps)):
+        ap.error("--finetune-steps needs --quantize-bits and 0 <= N <= max(--steps)")
+    if bits is not None and a.precision != "fp32":
+        ap.error("--quantize-bits needs --precision fp32")
     n = a.size
     dims = (n, n, n)
     vox = n ** 3
@@ -48,17 +65,21 @@ def main():
     del vf
     # the same field without its N(0, 200) noise: PSNR against it separates a good fit from a bad one (against the noisy source every codec is capped at 50.3 dB)
     clean = make_volume_torch(dims, seed=42, detail=a.detail, noise_sigma=0.0)
-    lines = ["| ratio | features | params | bits/voxel | steps | fit s | Mvoxel-samples/s | PSNR dB | PSNR vs noise-free field dB |%s" % (" SSIM |" if a.ssim else ""),
-             "|---|---|---|---|---|---|---|---|---|%s" % ("---|" if a.ssim else "")]
-    jobs = [(vox * 2.0 / (4.0 * SIREN.calc_param_count(3, 1, F, a.layers)), F) for F in a.features] if a.features else \
-           [(ratio, SIREN.calc_features(vox * 2 / ratio / 4, 3, 1, a.layers)) for ratio in a.ratios]
+    lines = ["| ratio | artefact | features | params | artefact bytes | bits/voxel | steps | fit s | Mvoxel-samples/s | PSNR dB | PSNR vs noise-free field dB |%s" % (" SSIM |" if a.ssim else ""),
+             "|---|---|---|---|---|---|---|---|---|---|---|%s" % ("---|" if a.ssim else "")]
+    tag = "fp32" if bits is None else "%d bit%s" % (bits, " + %d ft" % a.finetune_steps if a.finetune_steps else "")
+    over = quantize.overhead_bytes(a.layers) if bits is not None else 0
+    per = 4.0 if bits is None else bits / 8.0                                # bytes per parameter of the artefact
+    jobs = [(vox * 2.0 / (per * SIREN.calc_param_count(3, 1, F, a.layers) + over), F) for F in a.features] if a.features else \
+           [(ratio, SIREN.calc_features((vox * 2 / ratio - over) / per, 3, 1, a.layers)) for ratio in a.ratios]
     for ratio, F in jobs:
         if F > 4096:
             print("ratio %g needs %d features (> 4096): skipped" % (ratio, F), flush=True)
             continue
         torch.manual_seed(42)
         m = SIREN(coords_channel=3, data_channel=1, features=F, layers=a.layers, w0=a.w0, precision=a.precision).to("cuda")
-        fit = Fitter(m, tv, dims, sampler="randompoint", sample_size=a.sample_size, seed=42)
+        fit = Fitter(m, tv, dims, sampler="randompoint", sample_size=a.sample_size, seed=42,
+                     quantize=(bits, max(a.steps) - a.finetune_steps) if a.finetune_steps else None)
         done, t_fit = 0, 0.0
         for target in sorted(a.steps):
             torch.cuda.synchronize()
@@ -67,7 +88,13 @@ def main():
             torch.cuda.synchronize()
             t_fit += time.time() - t0
             done = target
-            dec = m.decode_grid(dims, out_kind="u16", scale=(0.0, 100.0), vrange=(vmin, vmax))     # fused invnormalize
+            with tempfile.TemporaryDirectory() as tmp:                       # what is scored is the artefact as written
+                save_model(m, os.path.join(tmp, "module"), quantize_bits=bits)
+                nbytes = get_folder_size(os.path.join(tmp, "module"))
+                stored = load_model(SIREN(coords_channel=3, data_channel=1, features=F, layers=a.layers, w0=a.w0, precision=a.precision),
+                                    os.path.join(tmp, "module")).to("cuda")
+            dec = stored.decode_grid(dims, out_kind="u16", scale=(0.0, 100.0), vrange=(vmin, vmax))     # fused invnormalize
+            del stored
             sse = torch.zeros(1, dtype=torch.float64, device="cuda")
             _lib.check(_lib.lib().brief_sse_u16(_lib.ptr(vol), _lib.ptr(dec), vox, _lib.ptr(sse), _lib.stream_ptr()))
             psnr = -10.0 * np.log10(sse.item() / vox / 65535.0 ** 2)
@@ -75,8 +102,8 @@ def main():
             psnr_c = -10.0 * np.log10(sse.item() / vox / 65535.0 ** 2)
             if a.ssim:
                 ss, ns = metrics.gpu_ssim_u16(vol.reshape(dims), dec.reshape(dims))
-            row = "| %.4g | %d | %d | %.4f | %d | %.1f | %.1f | %.2f | %.2f |" % (ratio, F, m.param_count, 32.0 * m.param_count / vox, done, t_fit,
-                                                                              done * fit.n / t_fit / 1e6, psnr, psnr_c)
+            row = "| %.4g | %s | %d | %d | %d | %.4f | %d | %.1f | %.1f | %.2f | %.2f |" % (ratio, tag, F, m.param_count, nbytes, 8.0 * nbytes / vox, done, t_fit,
+                                                                                        done * fit.n / t_fit / 1e6, psnr, psnr_c)
             if a.ssim:
                 row += " %.4f |" % (ss / ns)
             print(row, flush=True)
