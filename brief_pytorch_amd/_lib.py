@@ -114,7 +114,8 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_sincos_probe", "brief_cu_count",
            "brief_correct_chunk_elems", "brief_correct_count", "brief_correct_emit", "brief_correct_apply",
            "brief_mip_accumulate",
-           "brief_quant_workspace_bytes", "brief_quant_ranges", "brief_quant_apply", "brief_quant_decode"] \
+           "brief_quant_workspace_bytes", "brief_quant_ranges", "brief_quant_apply", "brief_quant_decode",
+           "brief_siren_jac_packed_count", "brief_siren_jac_repack", "brief_siren_jac_forward", "brief_siren_jac_forward_box"] \
     + ["brief_%s_%s" % (prefix, entry) for prefix, _, _ in FAMILIES for entry in FAMILY_ENTRIES]
 
 
@@ -223,6 +224,11 @@ def lib():
     L.brief_quant_ranges.argtypes = [vp, sp, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp]
     L.brief_quant_apply.argtypes = [vp, sp, C.c_int32, C.c_int32, vp, vp, vp, vp]
     L.brief_quant_decode.argtypes = [vp, sp, C.c_int32, vp, vp, vp]
+    L.brief_siren_jac_packed_count.restype = C.c_int64
+    L.brief_siren_jac_packed_count.argtypes = [dp]
+    L.brief_siren_jac_repack.argtypes = [dp, vp, vp, vp]
+    L.brief_siren_jac_forward.argtypes = [dp, vp, gp, bp, vp, vp, vp]
+    L.brief_siren_jac_forward_box.argtypes = [dp, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, vp, vp]
     _LIB = L
     return L
 

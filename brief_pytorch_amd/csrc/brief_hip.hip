@@ -38,6 +38,7 @@
 //   brief_correct.inc  k_correct_count / k_correct_emit / k_correct_apply: the stored corrections of the error-bounded mode.
 //   brief_mip.inc      k_mip_rows / k_mip_cols: max-intensity projections of a decoded box, folded into three images.
 //   brief_quant.inc    k_quant_minmax / k_quant_fold / k_quant_apply / k_quant_decode: the 2..16-bit weight quantiser of the quantised artefact.
+//   brief_jac.inc      k_jac_fwd / k_jac_repack: value and analytic Jacobian of an fp32 SIREN with respect to the coordinates (host: brief_jac_host.inc).
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
@@ -65,6 +66,7 @@
 #include "brief_correct.inc"    // error-bounded mode: k_correct_count, k_correct_emit, k_correct_apply
 #include "brief_mip.inc"        // max-intensity projections: k_mip_rows, k_mip_cols
 #include "brief_quant.inc"      // weight quantisation: k_quant_minmax, k_quant_fold, k_quant_apply, k_quant_decode
+#include "brief_jac.inc"        // spatial-gradient decode: k_jac_fwd, k_jac_repack
 
 // =============================================================================================
 // C-ABI
@@ -1769,3 +1771,4 @@ int brief_quant_decode(const uint16_t *codes, const brief_quant_span *tensors, i
 }   // extern "C"
 
 #include "brief_family_host.inc"      // FFN, NeRF, MFN, tapered SIRENs: one host driver, four traits structs and their C-ABI entries
+#include "brief_jac_host.inc"         // spatial-gradient decode: brief_siren_jac_* (named last: its kernels are the last ones instantiated)

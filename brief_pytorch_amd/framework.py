@@ -317,6 +317,21 @@ class NFGR:
         return mip.decompress_divide_mip(opt if opt is not None else _wrap(self.opt), orig_sideinfos_path, module_save_dir, sideinfos_save_dir,
                                          region, step, self.device)
 
+    # ---- spatial-gradient decode: the analytic Jacobian of the stored net in grey levels per voxel (brief_pytorch_amd/gradient.py)
+    @staticmethod
+    def decompress_gradient(opt, module_path, sideinfos, region=None, step=1, shape=None, device="cuda"):
+        """numpy float32 [*extent, cout, cin]: d(channel) / d(axis) of the stored fp32 SIREN over the region, in grey levels per voxel
+        step (gradient.decompress_gradient has the definition, the units and the scope)"""
+        from . import gradient
+        return gradient.decompress_gradient(opt, module_path, sideinfos, region, step, shape, device)
+
+    def decompress_divide_gradient(self, orig_sideinfos_path, module_save_dir, sideinfos_save_dir, region=None, step=1, opt=None):
+        """the same for a stored DivideTask artefact: every block on its own grid and scale, discontinuous at the block faces
+        (gradient.decompress_divide_gradient)"""
+        from . import gradient
+        return gradient.decompress_divide_gradient(opt if opt is not None else _wrap(self.opt), orig_sideinfos_path, module_save_dir,
+                                                   sideinfos_save_dir, region, step, self.device)
+
     # ---- SingleTask encode (main.py:322-454)
     def prepare_fit(self, data_path, data=None, logdir=None):
         """everything main.py:322-384 sets up before the loop: preprocess, loss weights, normalise, size the
@@ -1091,3 +1106,9 @@ def decompress_divide_mip(opt, orig_sideinfos, module_dir, sideinfos_dir, region
     """the three max-intensity projections of a region of a stored DivideTask artefact (mip.decompress_divide_mip); opt: the whole option tree"""
     from . import mip
     return mip.decompress_divide_mip(opt, orig_sideinfos, module_dir, sideinfos_dir, region, step, device)
+
+
+def decompress_divide_gradient(opt, orig_sideinfos, module_dir, sideinfos_dir, region=None, step=1, device="cuda"):
+    """the spatial gradient of a region of a stored DivideTask artefact (gradient.decompress_divide_gradient); opt: the whole option tree"""
+    from . import gradient
+    return gradient.decompress_divide_gradient(opt, orig_sideinfos, module_dir, sideinfos_dir, region, step, device)

@@ -1,0 +1,170 @@
+"""Spatial gradients straight from a stored artefact: the analytic Jacobian of the fitted SIREN with respect to the voxel position,
+in grey levels per voxel step, evaluated on the HIP path (csrc/brief_jac.inc through SIREN.decode_gradient_box) with decode_box's
+region semantics: a region equals the slice of the whole, results do not depend on how a region is cut into calls, and the same
+call gives the same bits.  (DESIGN.md "Spatial-gradient decode".)
+
+voxel_scale, refusal and supported are host arithmetic; everything else needs a ROCm GPU (there is no CPU fallback)."""
+import copy
+import os
+
+import numpy as np
+
+from . import config
+from . import region as region_mod
+
+MAX_FEATURES = 1024
+NETS = ("SIREN",)                  # the net classes brief_siren_jac_* evaluate
+PRECISIONS = ("fp32", "f32")
+
+
+def voxel_scale(dims, lo, hi, norm_range, vmin, vmax):
+    """per axis (hi - lo) / (dims[a] - 1) * (vmax - vmin) / (b - a), in float64; 0 for an axis of length 1.
+
+    The factor between d(net output) / d(coordinate) and grey levels per voxel step: the derivative of the unclipped, untruncated
+    invnormalize_data('minmaxany_a_b') of the net's output ((y - a) / (b - a) * (vmax - vmin) + vmin, norm_range = (a, b)), per step
+    of one voxel of the linspace grid `dims` over [lo, hi] that is being evaluated.  With a stride it is still per voxel of that grid;
+    with a resampled view (shape) `dims` is the resampled grid, so it is per voxel of that one."""
+    a, b = (np.float64(v) for v in norm_range)
+    grey = (np.float64(vmax) - np.float64(vmin)) / (b - a)
+    out = np.zeros(len(dims), dtype=np.float64)
+    for ax, n in enumerate(dims):
+        if int(n) > 1:
+            out[ax] = (np.float64(hi) - np.float64(lo)) / np.float64(int(n) - 1) * grey
+    return out
+
+
+def refusal(phi_name, precision, features):
+    """None where spatial gradients exist, else the refusal text (pure: no GPU, no library)"""
+    if str(phi_name) not in NETS or str(precision) not in PRECISIONS or not 1 <= int(features) <= MAX_FEATURES:
+        return "spatial gradients exist for fp32 SIREN up to %d features (this net is %s, %s, %d features)" % (
+            MAX_FEATURES, phi_name, precision, int(features))
+    return None
+
+
+def supported(phi_name, precision, features):
+    """whether spatial gradients exist for a net of this class, precision and width (refusal() has the text)"""
+    return refusal(phi_name, precision, features) is None
+
+
+def check_artefact(cf, sideinfos):
+    """what decompress_gradient supports, checked on option and side-info dicts before any decode; returns (a, b) of the normalisation"""
+    from .io import minmaxany_range
+    precision = str(sideinfos.get("phi_precision", cf.Compress.get("precision", "fp32")))
+    why = refusal(sideinfos["phi_name"], precision, sideinfos["phi_features"])
+    if why is not None:
+        raise ValueError(why)
+    rng = minmaxany_range(cf.Normalize.name)
+    if rng is None:
+        raise ValueError("the spatial-gradient decode supports the 'minmaxany_a_b' normalisations only (their inverse is affine in the "
+                         "net's output), not Normalize.name=%s" % cf.Normalize.name)
+    return rng
+
+
+def _block_gradient(cf, module_path, sideinfos, dims, start, stop, step, device, chunk=None):
+    """the scaled Jacobian [*extent, cout, cin] (device, float32) of one stored net over the box start:stop:step of the grid `dims`"""
+    import torch
+    from .framework import _coords_range
+    from .mip import _load_phi
+    rng = check_artefact(cf, sideinfos)
+    phi = _load_phi(cf, module_path, sideinfos, device)
+    lo, hi = _coords_range(cf.Compress.coords_mode)
+    jac, _ = phi.decode_gradient_box(dims, start, stop, step, lo, hi, chunk=chunk, want_value=False)
+    scale = voxel_scale(dims, lo, hi, rng, sideinfos["min"], sideinfos["max"])
+    return jac * torch.tensor(scale, dtype=torch.float32, device=jac.device)
+
+
+def _as_dicts(opt, sideinfos):
+    from .io import load_yaml
+    if isinstance(opt, str):
+        opt = config.load(opt)
+    if isinstance(sideinfos, str):
+        sideinfos = load_yaml(sideinfos)
+    return opt, sideinfos
+
+
+def decompress_gradient_device(opt, module_path, sideinfos, region=None, step=1, shape=None, device="cuda", chunk=None):
+    """decompress_gradient's result as a device tensor (what the magnitude of decompress.py is taken of)"""
+    opt, sideinfos = _as_dicts(opt, sideinfos)
+    cf = copy.deepcopy(opt.CompressFramework)
+    check_artefact(cf, sideinfos)
+    dims = [int(v) for v in list(sideinfos["data_shape"])[:-1]]
+    if shape is not None:
+        shape = [int(v) for v in shape]
+        if len(shape) != len(dims) or any(v < 1 for v in shape):
+            raise ValueError("shape %s does not fit the %d spatial axes of the artefact" % (shape, len(dims)))
+        dims = shape
+    start, stop, stp = region_mod.normalize_region(dims, region if region is not None else (slice(None),) * len(dims), step)
+    return _block_gradient(cf, module_path, sideinfos, dims, start, stop, stp, device, chunk)
+
+
+def decompress_gradient(opt, module_path, sideinfos, region=None, step=1, shape=None, device="cuda", chunk=None):
+    """The spatial gradient of a stored SingleTask artefact over `region` (None: the whole grid; NFGR.decompress_region's region,
+    step and shape semantics): numpy float32 [*extent, cout, cin], entry [..., c, a] = d(channel c) / d(axis a) in GREY LEVELS PER
+    VOXEL STEP of the grid being evaluated (the fitted one; with `shape`, the resampled one; a stride does not change the unit).
+
+    It is voxel_scale x the analytic Jacobian of the stored net at the voxel centres: the derivative of the unclipped, untruncated
+    de-normalised output.  Defined for 'minmaxany_a_b' artefacts of any dtype; other normalisations are refused by name.  Quantised
+    artefacts work unchanged (load_model dequantises: the gradient is that of the dequantised weights).  For an error-bounded
+    artefact the result is the gradient of the net ALONE: the stored corrections are integer repairs of single voxels and have no
+    derivative.  Decompress.postprocess (threshold, clip) is NOT applied: it acts on grey values, not on their derivative.
+    Nets other than an fp32 SIREN of at most 1024 features are refused before any decode."""
+    return decompress_gradient_device(opt, module_path, sideinfos, region, step, shape, device, chunk).cpu().numpy()
+
+
+def _ranges_overlap(a, b, axes):
+    return all(a[k][0] <= b[k][1] and b[k][0] <= a[k][1] for k in axes)
+
+
+def decompress_divide_gradient_device(opt, orig_sideinfos, module_dir, sideinfos_dir, region=None, step=1, device="cuda", chunk=None):
+    """decompress_divide_gradient's result as a device tensor"""
+    import torch
+    from .io import load_yaml
+    from .misc import parse_chunk_name
+    opj = os.path.join
+    if isinstance(opt, str):
+        opt = config.load(opt)
+    orig = load_yaml(orig_sideinfos) if isinstance(orig_sideinfos, str) else orig_sideinfos
+    data_shape = [int(v) for v in orig["data_shape"]]
+    dims, cout = data_shape[:-1], data_shape[-1]
+    axes = "dhw" if len(dims) == 3 else "hw"
+    start, stop, stp = region_mod.normalize_region(dims, region if region is not None else (slice(None),) * len(dims), step)
+    ext = region_mod.extents(start, stop, stp)
+    names = sorted(os.listdir(module_dir))
+    if not names:
+        raise ValueError("no blocks under %s" % module_dir)
+    # every refusal before any decode
+    blocks = []
+    for name in names:
+        side = load_yaml(opj(sideinfos_dir, name, "sideinfos.yaml"))
+        check_artefact(opt.CompressFramework, side)
+        blocks.append((name, side, parse_chunk_name(name)))
+    for i, (na, _, ra) in enumerate(blocks):
+        for nb, _, rb in blocks[i + 1:]:
+            if _ranges_overlap(ra, rb, axes):
+                raise ValueError("the blocks %s and %s overlap: merge_divided_data adds overlapping blocks and clips the sum, which has "
+                                 "no single net's gradient; the spatial-gradient decode needs a partition without overlap" % (na, nb))
+    out = torch.zeros((*ext, cout, len(dims)), dtype=torch.float32, device=device)
+    for name, side, r in blocks:
+        hit = region_mod.block_intersection(start, stp, ext, [r[a][0] for a in axes], [r[a][1] for a in axes])
+        if hit is None:
+            continue
+        o_lo, o_hi, l_start, l_stop = hit
+        b_dims = [int(v) for v in list(side["data_shape"])[:-1]]
+        g = _block_gradient(copy.deepcopy(opt.CompressFramework), opj(module_dir, name, "module"), side, b_dims, l_start, l_stop, stp, device, chunk)
+        out[tuple(slice(b, e) for b, e in zip(o_lo, o_hi))] = g
+    return out
+
+
+def decompress_divide_gradient(opt, orig_sideinfos, module_dir, sideinfos_dir, region=None, step=1, device="cuda", chunk=None):
+    """The spatial gradient of a stored DivideTask artefact over `region` (decompress_divide_region's region semantics): numpy float32
+    [*extent, cout, cin] in grey levels per voxel step.  Only the blocks that meet the region are evaluated; each on its OWN grid and
+    with its OWN voxel_scale (its dims, its min and max), placed at its output offset; voxels no block covers are 0.  The field is
+    each block's own net up to the block's faces and is DISCONTINUOUS there: no derivative is taken across a face.  Blocks whose
+    ranges overlap are refused (merge_divided_data adds and clips there).  decompress_gradient's notes on corrections, quantised
+    weights and Decompress.postprocess hold per block."""
+    return decompress_divide_gradient_device(opt, orig_sideinfos, module_dir, sideinfos_dir, region, step, device, chunk).cpu().numpy()
+
+
+def magnitude(grad):
+    """sqrt(sum over the axes of g^2): [*extent, cout, cin] -> [*extent, cout] (a torch tensor in, the same device out)"""
+    return (grad * grad).sum(dim=-1).sqrt()

@@ -15,7 +15,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import _lib, quantize, region
+from . import _lib, gradient, quantize, region
 
 __all__ = ["SIREN", "FFN", "NeRF", "MFNFourier", "MFNGabor", "SIREN_Pyramid", "SIRENFT", "SIRENPS", "init_phi", "ALLPHI", "ALL_CALC_PHI_FEATURES", "ALL_CALC_PHI_PARAM_COUNT",
            "ALL_CHECK_PARAM_COUNT", "get_nnmodule_param_count"]
@@ -376,6 +376,76 @@ class SIREN:
             cnt = min(chunk, total - off)
             _lib.check(self._abi_forward_box(box, off, cnt, flat[off:off + cnt], kind, scale, vrange))
         return out
+
+    # ---- spatial gradients: value and analytic Jacobian with respect to the coordinates (csrc/brief_jac.inc)
+    def _sync_jac(self):
+        """the Jacobian kernel's own fragment buffer, a second derived copy of self.params: allocated on first use, and written anew
+        at the head of EVERY gradient call (one launch over the net's size).  A stale copy is the bug this is built against: the
+        parameters change under load_state_dict / load_model (.data), torch optimizers, to() and the in-kernel updates of a fit,
+        and a flag would have to follow every one of those writers; a copy that is never reused cannot be stale."""
+        self._require_gpu()
+        why = gradient.refusal(getattr(type(self), "kind", "SIREN"), self.precision, self.features)
+        if why is not None:
+            raise _lib.BriefError(why)
+        L = _lib.lib()
+        pk = getattr(self, "_jac_packed", None)
+        if pk is None or pk.device != self.params.device:
+            n = L.brief_siren_jac_packed_count(C.byref(self.desc))
+            if n < 0:
+                raise _lib.BriefError(L.brief_last_error().decode())
+            pk = self._jac_packed = torch.empty(n, dtype=torch.float32, device=self.params.device)
+        _lib.check(L.brief_siren_jac_repack(C.byref(self.desc), _lib.ptr(self.params), _lib.ptr(pk), _lib.stream_ptr()))
+        return pk
+
+    def spatial_gradient(self, coords, want_value=True):
+        """(value [n, cout], jac [n, cout, cin]) at arbitrary device coordinates [n, cin]: the net's output and its analytic Jacobian
+        d phi_c / d x_a in coordinate units (with output_act, of the activated output); float32, from brief_siren_jac_forward.
+        value is None with want_value=False.  fp32 SIREN up to 1024 features only (BriefError otherwise)."""
+        pk = self._sync_jac()
+        cin, cout = self.coords_channel, self.data_channel
+        c = coords.to(self.params.device, torch.float32).reshape(-1, cin).contiguous()
+        n = c.shape[0]
+        value = torch.empty((n, cout), dtype=torch.float32, device=c.device) if want_value else None
+        jac = torch.empty((n, cout, cin), dtype=torch.float32, device=c.device)
+        if n:
+            b = _lib.BatchDesc(c.data_ptr(), None, None, None, 0, n, 0, 0, 0)
+            _lib.check(_lib.lib().brief_siren_jac_forward(C.byref(self.desc), _lib.ptr(pk), None, C.byref(b), _lib.ptr(value), _lib.ptr(jac),
+                                                          _lib.stream_ptr()))
+        return value, jac
+
+    def decode_gradient_box(self, dims, start=None, stop=None, step=1, lo=-1.0, hi=1.0, chunk=None, want_value=True):
+        """(jac [*extent, cout, cin], value [*extent, cout] | None) over the box start:stop:step of the linspace grid `dims`, with
+        decode_box's region semantics, coordinates (bit for bit) and chunk loop: a box equals the slice of the whole grid's result,
+        and neither `chunk` nor a repeat of the call changes a bit.  Coordinate units: per unit of [lo, hi] (gradient.voxel_scale
+        converts to grey levels per voxel step)."""
+        pk = self._sync_jac()
+        nd = len(dims)
+        per = (lambda v: [v] * nd if v is None or np.isscalar(v) else list(v))
+        b, e = per(start), per(stop)
+        if len(b) != nd or len(e) != nd:
+            raise ValueError("start / stop need one entry per axis of dims")
+        b0, e0, st = region.normalize_region(dims, tuple(slice(x, y) for x, y in zip(b, e)), step)
+        ext = region.extents(b0, e0, st)
+        total = int(np.prod(ext))
+        cin, cout = self.coords_channel, self.data_channel
+        dev = self.params.device
+        jac = torch.empty((*ext, cout, cin), dtype=torch.float32, device=dev)
+        value = torch.empty((*ext, cout), dtype=torch.float32, device=dev) if want_value else None
+        box = _lib.GridBox()
+        box.grid = self._grid(dims, lo, hi)
+        for a in range(nd):
+            box.start[a], box.step[a], box.extent[a] = b0[a], st[a], ext[a]
+        chunk = int(chunk or self.BOX_CHUNK)
+        if chunk < 1:
+            raise ValueError("chunk must be >= 1")
+        fj = jac.view(total, cout, cin)
+        fv = value.view(total, cout) if want_value else None
+        for off in range(0, total, chunk):
+            cnt = min(chunk, total - off)
+            _lib.check(_lib.lib().brief_siren_jac_forward_box(C.byref(self.desc), _lib.ptr(pk), C.byref(box), off, cnt,
+                                                              _lib.ptr(fv[off:off + cnt]) if want_value else None, _lib.ptr(fj[off:off + cnt]),
+                                                              _lib.stream_ptr()))
+        return jac, value
 
     def train_step(self, n, targets, idx=None, coords=None, weights=None, grid=None, offset=0,
                    loss="datal2", thr=0.0, beta=0.01, want_yhat=False, rng=None):

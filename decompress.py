@@ -13,6 +13,12 @@ The artefact kind is read from the directory: a `sideinfos/` directory of blocks
 `--mip` writes the three max-intensity projections of the region (out_mip_d.tif, out_mip_h.tif, out_mip_w.tif) instead of the
 region itself: it is decoded chunk by chunk on the GPU and folded into the three images, the volume is never held (3-D uint8 /
 uint16 artefacts; not with `--shape`).
+
+    python decompress.py -p <run yaml> -c <.../compressed> --region :,:,: --gradient components -o grad.npy
+
+`--gradient components` writes the analytic spatial gradient of the stored net over the region, float32 [*extent, channels, axes] in
+grey levels per voxel step; `--gradient magnitude` writes its Euclidean norm over the axes, float32 [*extent, channels] (fp32 SIREN
+artefacts up to 1024 features under a `minmaxany_a_b` normalisation; `.npy` output only; not with `--mip`; `--shape` on SingleTask only).
 """
 import argparse
 import os
@@ -31,8 +37,21 @@ def main(argv=None):
     ap.add_argument("--step", type=int, default=1, help="stride of every axis whose part has none (default 1)")
     ap.add_argument("--shape", default=None, help="D,H,W: decode a resampled view on a grid of this shape (SingleTask)")
     ap.add_argument("--mip", action="store_true", help="write the region's three max-intensity projections <out>_mip_{d,h,w}<ext> instead of the region")
+    ap.add_argument("--gradient", default=None, metavar="{components,magnitude}",
+                    help="write the region's analytic spatial gradient (grey levels per voxel step) or its magnitude instead of the region (.npy)")
     ap.add_argument("-o", required=True, help="output file (.tif / .tiff / .npy / .png / .jpg)")
     args = ap.parse_args(argv)
+    if args.gradient is not None:
+        # every refusal by name, before the GPU path is imported
+        if args.gradient not in ("components", "magnitude"):
+            raise SystemExit("--gradient %s: unknown mode (components or magnitude)" % args.gradient)
+        if args.mip:
+            raise SystemExit("--gradient with --mip: a projection of a gradient is not defined here; ask for one of them")
+        if os.path.splitext(args.o)[1].lower() != ".npy":
+            raise SystemExit("--gradient writes float32 arrays as .npy only (got %s): gradient output in image formats is not supported"
+                             % (os.path.splitext(args.o)[1] or "no extension"))
+        if args.shape and os.path.isdir(os.path.join(args.c, "sideinfos")):
+            raise SystemExit("--gradient --shape: resampling is not defined for a DivideTask artefact (every block has its own linspace grid)")
     if args.mip and args.shape:
         from brief_pytorch_amd.mip import SHAPE_REFUSAL
         raise SystemExit("--mip --shape: " + SHAPE_REFUSAL)
@@ -49,6 +68,8 @@ def main(argv=None):
     divide = os.path.isdir(os.path.join(args.c, "sideinfos"))
     if args.mip:
         return _mip(args, opt, region, divide)
+    if args.gradient is not None:
+        return _gradient(args, opt, region, shape, divide)
     t0 = time.perf_counter()
     if divide:
         if shape is not None:
@@ -86,6 +107,31 @@ def _mip(args, opt, region, divide):
     print("%s region %s: max-intensity projections d %s, h %s, w %s, dtype %s, decoded in %.3f s -> %s_mip_{d,h,w}%s" % (
         "DivideTask" if divide else "SingleTask", args.region, tuple(mips[0].shape), tuple(mips[1].shape), tuple(mips[2].shape), mips[0].dtype,
         dt, os.path.splitext(args.o)[0], ext))
+    return 0
+
+
+def _gradient(args, opt, region, shape, divide):
+    import numpy as np
+    import torch
+    from brief_pytorch_amd import gradient
+    t0 = time.perf_counter()
+    try:
+        if divide:
+            g = gradient.decompress_divide_gradient_device(opt, os.path.join(args.c, "sideinfos.yaml"), os.path.join(args.c, "module"),
+                                                           os.path.join(args.c, "sideinfos"), region, args.step)
+        else:
+            g = gradient.decompress_gradient_device(opt, os.path.join(args.c, "module"), os.path.join(args.c, "sideinfos.yaml"), region, args.step,
+                                                    shape=shape)
+    except ValueError as e:                                       # a refusal (net class, precision, width, normalisation, overlap, region)
+        raise SystemExit("--gradient: %s" % e)
+    if args.gradient == "magnitude":
+        g = gradient.magnitude(g)                                 # on the device
+    data = g.cpu().numpy()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    np.save(args.o, data)
+    print("%s region %s: spatial gradient (%s, grey levels per voxel), shape %s, dtype %s, decoded in %.3f s -> %s" % (
+        "DivideTask" if divide else "SingleTask", args.region, args.gradient, tuple(data.shape), data.dtype, dt, args.o))
     return 0
 
 

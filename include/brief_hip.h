@@ -544,6 +544,24 @@ typedef struct brief_taper_fit_job {
 /* `steps` optimizer steps (train step + reduction + update + repack: four launches each, no host synchronisation) */
 int brief_taper_fit(const brief_taper_fit_job *job, int64_t steps, void *stream);
 
+/* ---- spatial-gradient decode of an fp32 SIREN (csrc/brief_jac.inc) ---------------------------------------------------------------
+ * value[n][cout] = phi(x_n) and jac[n][cout][cin] = d phi_c / d x_a (x_n), the analytic Jacobian with respect to the coordinates, in
+ * coordinate units (per unit of the grid's [lo, hi] range); with output_act, of the activated output.  Forward mode on the matrix pipe:
+ * the value and its cin tangents travel through the layers together, 8 samples x 4 quantities per 32-column MFMA tile.  Both outputs
+ * are float32; value may be NULL.  The kernels read a forward-only fragment buffer of their own (brief_siren_jac_packed_count floats,
+ * written by brief_siren_jac_repack from the canonical parameters: call it after every change of them).  Sample sources are those of
+ * brief_siren_forward (batch.coords, batch.idx, batch.offset, grid coordinates) and of brief_siren_forward_box (the same box rules and
+ * refusals; coordinates bit-identical to it), so a box equals the slice of the whole and results do not depend on how a box is cut
+ * into calls.  Enqueue-only on `stream`: no allocation, no synchronisation.
+ * Limits (BRIEF_ERR_INVALID with a message naming the limit, before any launch): precision BRIEF_PREC_F32, features 1 .. 1024,
+ * layers >= 2, cin 2 | 3, cout 1 .. 4, packed and jac not NULL, n >= 1, and everything the forward entries refuse of a batch / box. */
+int64_t brief_siren_jac_packed_count(const brief_siren_desc *d);
+int brief_siren_jac_repack(const brief_siren_desc *d, const float *params, float *packed, void *stream);
+int brief_siren_jac_forward(const brief_siren_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                            float *value /* [n][cout] or NULL */, float *jac /* [n][cout][cin] */, void *stream);
+int brief_siren_jac_forward_box(const brief_siren_desc *d, const float *packed, const brief_grid_box *box, int64_t offset, int64_t n,
+                                float *value, float *jac, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
