@@ -86,6 +86,15 @@ class QuantSpan(C.Structure):       # brief_quant_span
     _fields_ = [("offset", C.c_int64), ("count", C.c_int64)]
 
 
+class ViewDesc(C.Structure):        # brief_view_desc
+    _fields_ = [("dims", C.c_int64 * 3), ("lo", C.c_float), ("hi", C.c_float), ("origin", C.c_float * 3),
+                ("drow", C.c_float * 3), ("dcol", C.c_float * 3), ("ddepth", C.c_float * 3),
+                ("rows", C.c_int32), ("cols", C.c_int32), ("depth", C.c_int32), ("reserved", C.c_int32),
+                ("box_lo", C.c_float * 3), ("box_hi", C.c_float * 3)]
+
+
+VIEW_MODE = {"max": 0, "min": 1, "mean": 2, "slice": 3}      # BRIEF_VIEW_MAX .. BRIEF_VIEW_SLICE
+
 TAPER_MAX_LAYERS = 16              # BRIEF_TAPER_MAX_LAYERS
 
 
@@ -115,7 +124,8 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_correct_chunk_elems", "brief_correct_count", "brief_correct_emit", "brief_correct_apply",
            "brief_mip_accumulate",
            "brief_quant_workspace_bytes", "brief_quant_ranges", "brief_quant_apply", "brief_quant_decode",
-           "brief_siren_jac_packed_count", "brief_siren_jac_repack", "brief_siren_jac_forward", "brief_siren_jac_forward_box"] \
+           "brief_siren_jac_packed_count", "brief_siren_jac_repack", "brief_siren_jac_forward", "brief_siren_jac_forward_box",
+           "brief_view_clip", "brief_view_coords", "brief_view_fold", "brief_view_finish", "brief_view_sample_host", "brief_view_clip_host"] \
     + ["brief_%s_%s" % (prefix, entry) for prefix, _, _ in FAMILIES for entry in FAMILY_ENTRIES]
 
 
@@ -229,6 +239,13 @@ def lib():
     L.brief_siren_jac_repack.argtypes = [dp, vp, vp, vp]
     L.brief_siren_jac_forward.argtypes = [dp, vp, gp, bp, vp, vp, vp]
     L.brief_siren_jac_forward_box.argtypes = [dp, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, vp, vp]
+    wp, i64, i32 = C.POINTER(ViewDesc), C.c_int64, C.c_int32
+    L.brief_view_clip.argtypes = [wp, vp, vp, vp]
+    L.brief_view_coords.argtypes = [wp, vp, vp, i64, i64, i64, i64, i32, vp, vp]
+    L.brief_view_fold.argtypes = [wp, vp, vp, i64, i64, i64, i64, i32, vp, C.c_int, i32, i32, vp, vp, vp]
+    L.brief_view_finish.argtypes = [wp, C.c_int, i32, i32, vp, vp, vp, vp]
+    L.brief_view_sample_host.argtypes = [wp, vp, vp, vp, i64, vp, vp, vp]
+    L.brief_view_clip_host.argtypes = [wp, vp, vp]
     _LIB = L
     return L
 

@@ -39,6 +39,7 @@
 //   brief_mip.inc      k_mip_rows / k_mip_cols: max-intensity projections of a decoded box, folded into three images.
 //   brief_quant.inc    k_quant_minmax / k_quant_fold / k_quant_apply / k_quant_decode: the 2..16-bit weight quantiser of the quantised artefact.
 //   brief_jac.inc      k_jac_fwd / k_jac_repack: value and analytic Jacobian of an fp32 SIREN with respect to the coordinates (host: brief_jac_host.inc).
+//   brief_view.inc     k_view_clip / k_view_coords / k_view_fold / k_view_finish: oblique slices and projections along any direction (geometry: brief_view.h).
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
@@ -1772,3 +1773,4 @@ int brief_quant_decode(const uint16_t *codes, const brief_quant_span *tensors, i
 
 #include "brief_family_host.inc"      // FFN, NeRF, MFN, tapered SIRENs: one host driver, four traits structs and their C-ABI entries
 #include "brief_jac_host.inc"         // spatial-gradient decode: brief_siren_jac_* (named last: its kernels are the last ones instantiated)
+#include "brief_view.inc"             // orthographic view decode: kernels and entries of their own, behind everything else (the kernels above keep their order)

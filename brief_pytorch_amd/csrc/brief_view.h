@@ -1,0 +1,108 @@
+// brief_view.h — the geometry of the orthographic view decode (brief_pytorch_amd/view.py, csrc/brief_view.inc), defined once: the scalar
+// functions the gfx950 kernels call, compiled on the host too (brief_view_sample_host / brief_view_clip_host, tests/test_view_host.py).
+//
+// A view is a lattice of samples (row, col, k), row < rows, col < cols, k < depth, in VOXEL-INDEX space of the fitted grid `dims`.
+// Every fp32 operation rounds on its own; nothing is contracted into an fma except where an fma is written:
+//     position    p_a = fl(fl(fl(origin_a + fl(row * drow_a)) + fl(col * dcol_a)) + fl(k * ddepth_a))       (row, col, k < 2^24: exact floats)
+//     inside      box_lo_a <= p_a <= box_hi_a on every axis
+//     coordinate  step_a = fl(fl(hi - lo) / (float)(n_a - 1))                                               (fill_grid of brief_hip.hip)
+//                 x_a = p_a < (float)(n_a / 2) ? fma(step_a, p_a, lo) : fma(-step_a, (float)(n_a - 1) - p_a, hi)
+// The coordinate is lin_coord's two-sided form (brief_device.inc) taken at a real position: at an integer position it is the grid's
+// own coordinate of that voxel, bit for bit, so an axis-aligned view of unit spacing reproduces the grid decode.
+//
+// Ray range.  With row and col fixed, every p_a is a monotone function of k (k -> fl(k * d) is monotone, and so is x -> fl(b + x)),
+// so the inside samples of a ray are ONE interval of k.  brief_view_ray_range finds it by bisection on the position function itself:
+// the range it returns holds every inside sample of the ray and nothing else, whatever the roundings do at a face the ray skims.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#ifndef BRIEF_HD
+#define BRIEF_HD __host__ __device__ __forceinline__
+#endif
+#else
+#include <cmath>
+#ifndef BRIEF_HD
+#define BRIEF_HD static inline
+#endif
+#endif
+
+#if defined(__clang__)
+#define BRIEF_VIEW_NO_CONTRACT _Pragma("clang fp contract(off)")
+#else
+#define BRIEF_VIEW_NO_CONTRACT      /* g++: built with -ffp-contract=off */
+#endif
+
+// the ray's foot: the position of sample (row, col, 0) on axis a
+BRIEF_HD float brief_view_base(const brief_view_desc &v, int a, int32_t row, int32_t col)
+{
+    BRIEF_VIEW_NO_CONTRACT
+    const float r = (float)row * v.drow[a];
+    const float c = (float)col * v.dcol[a];
+    const float t = v.origin[a] + r;
+    return t + c;
+}
+
+BRIEF_HD float brief_view_at(const brief_view_desc &v, int a, float base, int32_t k)
+{
+    BRIEF_VIEW_NO_CONTRACT
+    const float d = (float)k * v.ddepth[a];
+    return base + d;
+}
+
+BRIEF_HD float brief_view_pos(const brief_view_desc &v, int a, int32_t row, int32_t col, int32_t k)
+{
+    return brief_view_at(v, a, brief_view_base(v, a, row, col), k);
+}
+
+BRIEF_HD bool brief_view_inside(const brief_view_desc &v, float p0, float p1, float p2)
+{
+    return v.box_lo[0] <= p0 && p0 <= v.box_hi[0] && v.box_lo[1] <= p1 && p1 <= v.box_hi[1] && v.box_lo[2] <= p2 && p2 <= v.box_hi[2];
+}
+
+BRIEF_HD float brief_view_step(const brief_view_desc &v, int a)
+{
+    BRIEF_VIEW_NO_CONTRACT
+    const float spread = v.hi - v.lo;
+    return v.dims[a] > 1 ? spread / (float)(v.dims[a] - 1) : 0.f;
+}
+
+BRIEF_HD float brief_view_coord(const brief_view_desc &v, int a, float step, float p)
+{
+    BRIEF_VIEW_NO_CONTRACT
+    const int64_t nn = v.dims[a];
+    if (p < (float)(nn / 2)) return fmaf(step, p, v.lo);
+    const float back = (float)(nn - 1) - p;
+    return fmaf(-step, back, v.hi);
+}
+
+// the first k in [0, depth] at which `p_a(k) >= bound` (ge) or `p_a(k) > bound` (!ge) holds, for a position that does not decrease with k
+// (rising) or does not increase (then the first k at which `<=` / `<` holds); depth if it never does
+BRIEF_HD int32_t brief_view_first(const brief_view_desc &v, int a, float base, float bound, bool rising, bool strict)
+{
+    int32_t lo = 0, hi = v.depth;                    // the predicate is false below lo and true from hi on
+    while (lo < hi) {
+        const int32_t mid = lo + (hi - lo) / 2;
+        const float p = brief_view_at(v, a, base, mid);
+        const bool t = rising ? (strict ? p > bound : p >= bound) : (strict ? p < bound : p <= bound);
+        if (t) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// the inside samples of ray (row, col) are exactly k0 <= k < k0 + cnt (cnt == 0: the ray misses the box; k0 is 0 then)
+BRIEF_HD void brief_view_ray_range(const brief_view_desc &v, int32_t row, int32_t col, int32_t &k0, int32_t &cnt)
+{
+    int32_t b = 0, e = v.depth;
+    for (int a = 0; a < 3; ++a) {
+        const float base = brief_view_base(v, a, row, col);
+        const bool rising = !(v.ddepth[a] < 0.f);
+        // rising: inside from the first p >= box_lo up to the first p > box_hi; falling: from the first p <= box_hi up to the first p < box_lo
+        const int32_t first = brief_view_first(v, a, base, rising ? v.box_lo[a] : v.box_hi[a], rising, false);
+        const int32_t end = brief_view_first(v, a, base, rising ? v.box_hi[a] : v.box_lo[a], rising, true);
+        b = first > b ? first : b;
+        e = end < e ? end : e;
+    }
+    cnt = e > b ? e - b : 0;
+    k0 = cnt ? b : 0;
+}

@@ -1,0 +1,285 @@
+// brief_view.inc — orthographic view decode: k_view_clip, k_view_coords, k_view_fold, k_view_finish and their C-ABI entries brief_view_*
+// (part of the single translation unit brief_hip.hip, included at its very end: kernels and host code of a feature that touches no
+// other kernel).  The geometry is csrc/brief_view.h, compiled here for the device and for the host entries alike.
+//
+// A view is rows x cols rays of `depth` samples each.  The net is evaluated by its own forward entry on explicit coordinates; these
+// kernels only say WHERE (clip, coords) and reduce WHAT came back (fold, finish):
+//   k_view_clip    one thread per ray: the interval [k0, k0 + cnt) of its samples inside the clip box (brief_view_ray_range).
+//   (caller)       off = exclusive scan of cnt (int64, rays + 1 entries): the COMPACTED SAMPLE LIST.
+//   k_view_coords  the [n][3] fp32 coordinates of the samples [s0, s1) of that list.
+//   (caller)       the net's forward entry on those coordinates, integer output kind: vals [n][C] uint8 / uint16.
+//   k_view_fold    reduces vals into the per-pixel accumulators; k_view_finish writes the image.
+//
+// Layout of the compacted list: RAY-MAJOR, a ray's samples contiguous and ascending in k — sample off[r] + j is (row, col, k0[r] + j)
+// with r = row * cols + col.  Rays that are neighbours in the image are neighbours in the list.  Both kernels that walk it give a ray
+// to a GROUP of G = 2^lg adjacent lanes (G = 1 .. 64, chosen by the caller near the mean samples per ray; 64 / G rays per wave): lane
+// `sub` of the group takes the samples lo + sub, lo + sub + G, ...  So in every pass the G lanes of a group touch G consecutive
+// samples, and the groups of a wave touch consecutive rays, whose samples follow each other in the list: a wave's 12-byte coordinate
+// stores and its 1..8-byte value loads fall into one contiguous span of the chunk (whole cache lines, apart from the span's ends),
+// whether a ray holds one sample (a slice: G = 1, lane = ray = sample) or hundreds (a projection: G = 64, a wave per ray).
+//
+// There are NO atomics: within a launch a pixel has ONE owner, its group.  The group applies the exact inside test to every sample,
+// reduces over its lanes in registers (a butterfly of lg steps within the group) and lane 0 does one plain read-modify-write of the
+// pixel's accumulators: hits (int32) and the running max / min (int32) or sum (int64) per channel.  Launches of one view follow each
+// other on one stream.  Everything folded is an integer: the result is exact and does not depend on G, on the chunking or on the run.
+#include <type_traits>
+#include "brief_view.h"
+
+struct ViewChunk {
+    int64_t s0, s1;      // the samples of the compacted list this launch covers
+    int64_t r0, r1;      // the rays that may hold one of them: off[r + 1] > s0 and off[r] < s1 for r0 <= r < r1
+    int lg;              // log2 of the lanes per ray
+    float step[3];       // brief_view_step per axis, from the host (fill_grid's own float)
+};
+
+__global__ __launch_bounds__(256) void k_view_clip(brief_view_desc v, int32_t *__restrict__ k0, int32_t *__restrict__ cnt)
+{
+    const int64_t rays = (int64_t)v.rows * v.cols;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rays; r += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t row = (int32_t)(r / v.cols), col = (int32_t)(r - (int64_t)row * v.cols);
+        int32_t b, n;
+        brief_view_ray_range(v, row, col, b, n);
+        k0[r] = b;
+        cnt[r] = n;
+    }
+}
+
+// the part of the walk both list kernels share: the group's ray of iteration `it` and its samples within the chunk, [lo, hi) (empty
+// for a group beyond the last ray), the ray's first list index `a` and its foot `base`
+struct ViewRay { int64_t r, a, lo, hi; float base[3]; };
+__device__ __forceinline__ ViewRay view_ray(const brief_view_desc &v, const ViewChunk &ch, const int64_t *__restrict__ off, int64_t g)
+{
+    ViewRay q;
+    const bool live = g < ch.r1 - ch.r0;
+    q.r = ch.r0 + (live ? g : 0);
+    q.a = off[q.r];
+    const int64_t b = off[q.r + 1];
+    q.lo = q.a > ch.s0 ? q.a : ch.s0;
+    q.hi = live ? (b < ch.s1 ? b : ch.s1) : q.lo;
+    const int32_t row = (int32_t)(q.r / v.cols), col = (int32_t)(q.r - (int64_t)row * v.cols);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) q.base[a] = brief_view_base(v, a, row, col);
+    return q;
+}
+
+__global__ __launch_bounds__(256) void k_view_coords(brief_view_desc v, ViewChunk ch, const int32_t *__restrict__ k0, const int64_t *__restrict__ off,
+                                                     float *__restrict__ coords)
+{
+    const int G = 1 << ch.lg, sub = threadIdx.x & (G - 1);
+    const int64_t groups = ((int64_t)gridDim.x * blockDim.x) >> ch.lg;
+    for (int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> ch.lg; g < ch.r1 - ch.r0; g += groups) {
+        const ViewRay q = view_ray(v, ch, off, g);
+        const int32_t kb = k0[q.r];
+        for (int64_t s = q.lo + sub; s < q.hi; s += G) {
+            const int32_t k = kb + (int32_t)(s - q.a);
+            float *x = coords + (s - ch.s0) * 3;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) x[a] = brief_view_coord(v, a, ch.step[a], brief_view_at(v, a, q.base[a], k));
+        }
+    }
+}
+
+// MODE 0: max, 1: min, 2: sum (mean).  acc: int32 [rays][C] (max, min) or int64 [rays][C] (sum), caller-initialised to the fold's
+// identity (0, INT32_MAX, 0); hits: int32 [rays], caller-initialised to 0.
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void k_view_fold(brief_view_desc v, ViewChunk ch, const int32_t *__restrict__ k0, const int64_t *__restrict__ off,
+                                                   const T *__restrict__ vals, int C, int32_t *__restrict__ hits, void *__restrict__ acc)
+{
+    typedef typename std::conditional<MODE == 2, long long, int>::type A;
+    const int G = 1 << ch.lg, sub = threadIdx.x & (G - 1);
+    const int64_t groups = ((int64_t)gridDim.x * blockDim.x) >> ch.lg, nr = ch.r1 - ch.r0;
+    const int64_t iters = (nr + groups - 1) / groups;               // the same for every lane: the butterfly below needs the whole group
+    int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> ch.lg;
+    for (int64_t it = 0; it < iters; ++it, g += groups) {
+        const ViewRay q = view_ray(v, ch, off, g);
+        const int32_t kb = k0[q.r];
+        int n = 0;
+        A m[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) m[c] = MODE == 1 ? (A)INT32_MAX : (A)0;
+        for (int64_t s = q.lo + sub; s < q.hi; s += G) {
+            const int32_t k = kb + (int32_t)(s - q.a);
+            if (!brief_view_inside(v, brief_view_at(v, 0, q.base[0], k), brief_view_at(v, 1, q.base[1], k), brief_view_at(v, 2, q.base[2], k)))
+                continue;
+            ++n;
+            const T *x = vals + (s - ch.s0) * C;
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (c < C) {
+                    const A y = (A)x[c];
+                    m[c] = MODE == 0 ? (y > m[c] ? y : m[c]) : (MODE == 1 ? (y < m[c] ? y : m[c]) : m[c] + y);
+                }
+        }
+        for (int o = G >> 1; o >= 1; o >>= 1) {                      // (G is the launch's: every group of the wave takes the same steps)
+            n += __shfl_xor(n, o);
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (c < C) {
+                    const A y = __shfl_xor(m[c], o);
+                    m[c] = MODE == 0 ? (y > m[c] ? y : m[c]) : (MODE == 1 ? (y < m[c] ? y : m[c]) : m[c] + y);
+                }
+        }
+        if (sub == 0 && n > 0) {                                     // the pixel's owner
+            hits[q.r] += n;
+            A *d = (A *)acc + q.r * C;
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (c < C) d[c] = MODE == 0 ? (m[c] > d[c] ? m[c] : d[c]) : (MODE == 1 ? (m[c] < d[c] ? m[c] : d[c]) : d[c] + m[c]);
+        }
+    }
+}
+
+// out[r][c]: the running value in the source dtype (T, max / min / slice) or the mean as float ((float)((double)sum / hits)); a pixel
+// without an inside sample is 0
+template <typename T, bool MEAN>
+__global__ __launch_bounds__(256) void k_view_finish(int64_t rays, int C, const int32_t *__restrict__ hits, const void *__restrict__ acc, void *__restrict__ out)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rays * C; i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t h = hits[i / C];
+        if (MEAN) ((float *)out)[i] = h > 0 ? (float)((double)((const long long *)acc)[i] / (double)h) : 0.f;
+        else ((T *)out)[i] = h > 0 ? (T)((const int *)acc)[i] : (T)0;
+    }
+}
+
+// ---- host side
+static const int32_t kViewMaxCount = 1 << 24;      // rows, cols and depth travel as floats
+static const int64_t kViewMaxRays = (int64_t)1 << 40;
+
+static int check_view(const brief_view_desc *v)
+{
+    if (!v) return fail(BRIEF_ERR_INVALID, "view: null descriptor");
+    if (v->rows < 1 || v->cols < 1 || v->depth < 1 || v->rows >= kViewMaxCount || v->cols >= kViewMaxCount || v->depth >= kViewMaxCount)
+        return fail(BRIEF_ERR_INVALID, "view: rows, cols and depth must be 1 .. 2^24 - 1 (a float holds them exactly)");
+    if (!(v->lo == v->lo && v->hi == v->hi) || v->lo - v->lo != 0.f || v->hi - v->hi != 0.f) return fail(BRIEF_ERR_INVALID, "view: lo and hi must be finite");
+    for (int a = 0; a < 3; ++a) {
+        if (v->dims[a] < 2 || v->dims[a] >= ((int64_t)1 << 31)) return fail(BRIEF_ERR_INVALID, "view: every grid dim must be 2 .. 2^31 - 1");
+        const float f[6] = {v->origin[a], v->drow[a], v->dcol[a], v->ddepth[a], v->box_lo[a], v->box_hi[a]};
+        for (int i = 0; i < 6; ++i)
+            if (f[i] - f[i] != 0.f) return fail(BRIEF_ERR_INVALID, "view: origin, steps and clip box must be finite");
+        if (!(v->box_lo[a] >= 0.f && v->box_lo[a] <= v->box_hi[a] && v->box_hi[a] <= (float)(v->dims[a] - 1)))
+            return fail(BRIEF_ERR_INVALID, "view: the clip box must satisfy 0 <= box_lo <= box_hi <= dims - 1 on every axis");
+    }
+    return 0;
+}
+
+static int view_blocks(int64_t threads)
+{
+    const int64_t want = (threads + 255) / 256, cap = (int64_t)kCUs * 64;
+    return (int)(want < 1 ? 1 : (want < cap ? want : cap));
+}
+
+static int check_view_chunk(const brief_view_desc *v, const void *k0, const void *off, int64_t s0, int64_t s1, int64_t r0, int64_t r1, int32_t lanes,
+                            ViewChunk *ch)
+{
+    if (int rc = check_view(v)) return rc;
+    if (!k0 || !off) return fail(BRIEF_ERR_INVALID, "view: null buffer");
+    const int64_t rays = (int64_t)v->rows * v->cols;
+    if (s0 < 0 || s1 <= s0) return fail(BRIEF_ERR_INVALID, "view: an empty or negative sample range");
+    if (r0 < 0 || r1 <= r0 || r1 > rays) return fail(BRIEF_ERR_INVALID, "view: the ray range must lie inside 0 .. rows * cols");
+    int lg = 0;
+    while (lg < 6 && (1 << lg) < lanes) ++lg;
+    if (lanes < 1 || lanes > 64 || (1 << lg) != lanes) return fail(BRIEF_ERR_INVALID, "view: lanes per ray must be a power of two, 1 .. 64");
+    ch->s0 = s0; ch->s1 = s1; ch->r0 = r0; ch->r1 = r1; ch->lg = lg;
+    for (int a = 0; a < 3; ++a) ch->step[a] = brief_view_step(*v, a);
+    return 0;
+}
+
+extern "C" {
+
+int brief_view_clip(const brief_view_desc *view, int32_t *k0, int32_t *cnt, void *stream)
+{
+    if (int rc = check_view(view)) return rc;
+    if (!k0 || !cnt) return fail(BRIEF_ERR_INVALID, "view: null buffer");
+    const int64_t rays = (int64_t)view->rows * view->cols;
+    if (rays > kViewMaxRays) return fail(BRIEF_ERR_INVALID, "view: more than 2^40 rays");
+    hipLaunchKernelGGL(k_view_clip, dim3(view_blocks(rays)), dim3(256), 0, (hipStream_t)stream, *view, k0, cnt);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_view_coords(const brief_view_desc *view, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1, int64_t r0, int64_t r1,
+                      int32_t lanes, float *coords, void *stream)
+{
+    ViewChunk ch;
+    if (int rc = check_view_chunk(view, k0, off, s0, s1, r0, r1, lanes, &ch)) return rc;
+    if (!coords) return fail(BRIEF_ERR_INVALID, "view: null buffer");
+    hipLaunchKernelGGL(k_view_coords, dim3(view_blocks((r1 - r0) << ch.lg)), dim3(256), 0, (hipStream_t)stream, *view, ch, k0, off, coords);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_view_fold(const brief_view_desc *view, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1, int64_t r0, int64_t r1,
+                    int32_t lanes, const void *vals, int elem_kind, int32_t channels, int32_t mode, int32_t *hits, void *acc, void *stream)
+{
+    ViewChunk ch;
+    if (int rc = check_view_chunk(view, k0, off, s0, s1, r0, r1, lanes, &ch)) return rc;
+    if (!vals || !hits || !acc) return fail(BRIEF_ERR_INVALID, "view: null buffer");
+    if (elem_kind != BRIEF_OUT_U8 && elem_kind != BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "view: elem_kind must be BRIEF_OUT_U8 (1) or BRIEF_OUT_U16 (2)");
+    if (channels < 1 || channels > 4) return fail(BRIEF_ERR_INVALID, "view: channels must be 1..4");
+    if (mode < BRIEF_VIEW_MAX || mode > BRIEF_VIEW_SLICE) return fail(BRIEF_ERR_INVALID, "view: mode must be BRIEF_VIEW_MAX, _MIN, _MEAN or _SLICE");
+    const dim3 grid(view_blocks((r1 - r0) << ch.lg)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    const int m = mode == BRIEF_VIEW_SLICE ? 0 : mode;      // a slice has at most one inside sample per ray: its max is that sample
+#define VIEW_FOLD(T, M) hipLaunchKernelGGL((k_view_fold<T, M>), grid, block, 0, st, *view, ch, k0, off, (const T *)vals, (int)channels, hits, acc)
+    if (elem_kind == BRIEF_OUT_U8) {
+        if (m == 0) VIEW_FOLD(uint8_t, 0); else if (m == 1) VIEW_FOLD(uint8_t, 1); else VIEW_FOLD(uint8_t, 2);
+    } else {
+        if (m == 0) VIEW_FOLD(uint16_t, 0); else if (m == 1) VIEW_FOLD(uint16_t, 1); else VIEW_FOLD(uint16_t, 2);
+    }
+#undef VIEW_FOLD
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_view_finish(const brief_view_desc *view, int elem_kind, int32_t channels, int32_t mode, const int32_t *hits, const void *acc, void *out,
+                      void *stream)
+{
+    if (int rc = check_view(view)) return rc;
+    if (!hits || !acc || !out) return fail(BRIEF_ERR_INVALID, "view: null buffer");
+    if (elem_kind != BRIEF_OUT_U8 && elem_kind != BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "view: elem_kind must be BRIEF_OUT_U8 (1) or BRIEF_OUT_U16 (2)");
+    if (channels < 1 || channels > 4) return fail(BRIEF_ERR_INVALID, "view: channels must be 1..4");
+    if (mode < BRIEF_VIEW_MAX || mode > BRIEF_VIEW_SLICE) return fail(BRIEF_ERR_INVALID, "view: mode must be BRIEF_VIEW_MAX, _MIN, _MEAN or _SLICE");
+    const int64_t rays = (int64_t)view->rows * view->cols;
+    const dim3 grid(view_blocks(rays * channels)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == BRIEF_VIEW_MEAN) hipLaunchKernelGGL((k_view_finish<uint16_t, true>), grid, block, 0, st, rays, (int)channels, hits, acc, out);
+    else if (elem_kind == BRIEF_OUT_U8) hipLaunchKernelGGL((k_view_finish<uint8_t, false>), grid, block, 0, st, rays, (int)channels, hits, acc, out);
+    else hipLaunchKernelGGL((k_view_finish<uint16_t, false>), grid, block, 0, st, rays, (int)channels, hits, acc, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the same header on the host CPU: no GPU call
+int brief_view_sample_host(const brief_view_desc *view, const int32_t *row, const int32_t *col, const int32_t *k, int64_t n, float *pos, float *coord,
+                           uint8_t *inside)
+{
+    if (int rc = check_view(view)) return rc;
+    if (!row || !col || !k || n < 0) return fail(BRIEF_ERR_INVALID, "view: null index buffer or negative count");
+    float step[3];
+    for (int a = 0; a < 3; ++a) step[a] = brief_view_step(*view, a);
+    for (int64_t i = 0; i < n; ++i) {
+        if (row[i] < 0 || row[i] >= view->rows || col[i] < 0 || col[i] >= view->cols || k[i] < 0 || k[i] >= view->depth)
+            return fail(BRIEF_ERR_INVALID, "view: a sample index outside rows x cols x depth");
+        float p[3];
+        for (int a = 0; a < 3; ++a) p[a] = brief_view_pos(*view, a, row[i], col[i], k[i]);
+        if (pos) { pos[3 * i] = p[0]; pos[3 * i + 1] = p[1]; pos[3 * i + 2] = p[2]; }
+        if (coord)
+            for (int a = 0; a < 3; ++a) coord[3 * i + a] = brief_view_coord(*view, a, step[a], p[a]);
+        if (inside) inside[i] = brief_view_inside(*view, p[0], p[1], p[2]) ? 1 : 0;
+    }
+    return 0;
+}
+
+int brief_view_clip_host(const brief_view_desc *view, int32_t *k0, int32_t *cnt)
+{
+    if (int rc = check_view(view)) return rc;
+    if (!k0 || !cnt) return fail(BRIEF_ERR_INVALID, "view: null buffer");
+    for (int32_t row = 0; row < view->rows; ++row)
+        for (int32_t col = 0; col < view->cols; ++col) {
+            const int64_t r = (int64_t)row * view->cols + col;
+            brief_view_ray_range(*view, row, col, k0[r], cnt[r]);
+        }
+    return 0;
+}
+
+}   // extern "C"

@@ -317,6 +317,15 @@ class NFGR:
         return mip.decompress_divide_mip(opt if opt is not None else _wrap(self.opt), orig_sideinfos_path, module_save_dir, sideinfos_save_dir,
                                          region, step, self.device)
 
+    # ---- view decode: oblique slices and projections along any direction without the volume (brief_pytorch_amd/view.py)
+    @staticmethod
+    def decompress_view(opt, module_path, sideinfos, direction, **kwargs):
+        """an orthographic view of a stored SingleTask artefact as a numpy image [rows, cols, channels]: mode 'max' | 'min' | 'mean'
+        folds every ray of direction `direction` over the clip box `region`, 'slice' is one plane at any orientation.  Only the samples
+        inside the clip box are evaluated; the volume is never decoded.  view.decompress_view has the arguments and the envelope."""
+        from . import view
+        return view.decompress_view(opt, module_path, sideinfos, direction, **kwargs)
+
     # ---- spatial-gradient decode: the analytic Jacobian of the stored net in grey levels per voxel (brief_pytorch_amd/gradient.py)
     @staticmethod
     def decompress_gradient(opt, module_path, sideinfos, region=None, step=1, shape=None, device="cuda"):

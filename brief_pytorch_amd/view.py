@@ -1,0 +1,303 @@
+"""Oblique slices and projections of a stored artefact along any direction: an orthographic view decode.  A view is a lattice of
+rows x cols parallel rays with `depth` samples each, anywhere in the volume and at any orientation.  Only the samples inside the clip
+box are evaluated, by the net's own forward entry on explicit coordinates, chunk by chunk; each chunk is folded into per-pixel
+accumulators on the device (max | min | mean along the ray, or a single plane: slice) and dropped.  The volume is never decoded.
+(csrc/brief_view.h has the geometry, csrc/brief_view.inc the kernels, DESIGN.md "View decode" the reasoning.)
+
+make_view is host arithmetic; brief_view_sample_host / brief_view_clip_host restate the device's geometry on the CPU; everything else
+needs a ROCm GPU (there is no CPU fallback)."""
+import copy
+import ctypes as C
+import math
+import os
+
+import numpy as np
+
+from . import _lib, config
+from . import region as region_mod
+
+MODES = ("max", "min", "mean", "slice")
+MAX_COUNT = 1 << 24          # rows, cols and depth travel as floats
+DIVIDE_REFUSAL = ("view decode of a DivideTask artefact is refused: every block has its own net and coordinate grid, and a sample between "
+                  "two blocks has no owner yet (a follow-up will add partitioned artefacts); decode the region and resample it")
+
+
+def _vec3(v, what):
+    try:
+        out = np.array([float(x) for x in v], np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be three numbers in (z, y, x) order (got %r)" % (what, v)) from None
+    if out.shape != (3,) or not np.isfinite(out).all():
+        raise ValueError("%s must be three finite numbers in (z, y, x) order (got %r)" % (what, v))
+    return out
+
+
+def _positive(v, what):
+    v = float(v)
+    if not (math.isfinite(v) and v > 0):
+        raise ValueError("%s must be a positive finite number (got %r)" % (what, v))
+    return v
+
+
+def _count(span, spacing, what):
+    n = int(math.floor(span / spacing + 1e-9)) + 1
+    if n >= MAX_COUNT:
+        raise ValueError("%s = %d is refused: sizes of 2^24 and above are not exact in a float" % (what, n))
+    return max(n, 1)
+
+
+def frame(direction, up=None):
+    """the orthonormal PHYSICAL frame (row_dir, col_dir, direction) of a view, float64, each in (z, y, x) order.  `direction` is
+    normalised; the rows of the image run along `up` made orthogonal to it (default: the grid axis the direction has least of, the
+    first of them on a tie); col_dir = direction x row_dir with (z, y, x) as the three components, so (direction, row_dir, col_dir)
+    is a proper rotation of (z, y, x) and a turning direction never mirrors the image.  Looking along +z gives rows = y, cols = x,
+    along +x rows = z, cols = y, along -y rows = z, cols = x: the orientations of mip_ops' three images."""
+    d = _vec3(direction, "direction")
+    if not np.linalg.norm(d) > 0:
+        raise ValueError("direction must not be the zero vector")
+    d = d / np.linalg.norm(d)
+    if up is None:
+        u = np.zeros(3)
+        u[int(np.argmin(np.abs(d)))] = 1.0
+    else:
+        u = _vec3(up, "up")
+        if not np.linalg.norm(u) > 0:
+            raise ValueError("up must not be the zero vector")
+    r = u - np.dot(u, d) * d
+    if not np.linalg.norm(r) > 1e-9 * np.linalg.norm(u):
+        raise ValueError("up %r is parallel to direction %r: the image's rows have no direction" % (tuple(u), tuple(d)))
+    r = r / np.linalg.norm(r)
+    c = np.cross(d, r)
+    return r, c / np.linalg.norm(c), d
+
+
+def make_view(dims, direction, up=None, centre=None, spacing=1.0, depth_spacing=1.0, size=None, depth=None, voxel_size=(1, 1, 1), region=None):
+    """the descriptor (_lib.ViewDesc = brief_view_desc) of an orthographic view of the grid `dims` (3 spatial axes, (z, y, x)).
+    direction, up: see frame(); they are PHYSICAL directions, voxel_size (sz, sy, sx) being a voxel's physical extent per axis
+                   (every step is divided by it per axis to give voxel-index units).
+    centre:        the voxel-index position the view is centred on (default: the volume's centre, (n - 1) / 2 per axis).
+    spacing, depth_spacing: distance between neighbouring pixels / between samples of a ray, in physical units (voxels for the
+                   default voxel_size).
+    region:        the clip box (numpy slice semantics per axis, step 1 only; default the whole grid): samples outside it are
+                   never evaluated and never folded.
+    size:          (rows, cols), centred on `centre`; default: the smallest image that covers the clip box's projection.
+    depth:         (t0, t1), the range along `direction` relative to `centre` in physical units, sampled at t0, t0 + depth_spacing,
+                   ... <= t1; a single number t is the one plane (t, t); default: the range that covers the clip box.
+    Everything is computed in float64 and rounded to fp32 once.  lo / hi of the descriptor are set by render()."""
+    dims = [int(v) for v in dims]
+    if len(dims) != 3:
+        raise ValueError("a view is defined for 3-D data only (got a %d-D grid)" % len(dims))
+    if any(n < 2 for n in dims):
+        raise ValueError("a view needs every axis of the grid to be at least 2 voxels long (got %s): an axis of length 1 has no coordinate "
+                         "range to sample" % (dims,))
+    vs = _vec3(voxel_size, "voxel_size")
+    if (vs <= 0).any():
+        raise ValueError("voxel_size must be positive on every axis (got %r)" % (tuple(voxel_size),))
+    spacing, depth_spacing = _positive(spacing, "spacing"), _positive(depth_spacing, "depth_spacing")
+    row_dir, col_dir, d = frame(direction, up)
+    start, stop, step = region_mod.normalize_region(dims, region if region is not None else (slice(None),) * 3, 1)
+    if any(s != 1 for s in step):
+        raise ValueError("the clip box of a view is a box, not a lattice: region steps other than 1 are refused (got %s)" % (step,))
+    box_lo, box_hi = np.array(start, np.float64), np.array(stop, np.float64) - 1.0
+    c = (np.array(dims, np.float64) - 1.0) / 2.0 if centre is None else _vec3(centre, "centre")
+    corners = np.array([[(box_lo, box_hi)[(i >> a) & 1][a] for a in range(3)] for i in range(8)])
+    rel = (corners - c) * vs                                     # physical offsets of the clip box's corners from the centre
+    pu, pv, pw = rel @ row_dir, rel @ col_dir, rel @ d
+    if size is None:
+        u0, v0 = float(pu.min()), float(pv.min())
+        rows, cols = _count(float(pu.max()) - u0, spacing, "rows"), _count(float(pv.max()) - v0, spacing, "cols")
+    else:
+        try:
+            rows, cols = (int(x) for x in size)
+        except (TypeError, ValueError):
+            raise ValueError("size must be (rows, cols) (got %r)" % (size,)) from None
+        if rows < 1 or cols < 1:
+            raise ValueError("size must be at least 1 x 1 (got %r)" % (size,))
+        if rows >= MAX_COUNT or cols >= MAX_COUNT:
+            raise ValueError("size %r is refused: sizes of 2^24 and above are not exact in a float" % (size,))
+        u0, v0 = -(rows - 1) / 2.0 * spacing, -(cols - 1) / 2.0 * spacing
+    if depth is None:
+        w0 = float(pw.min())
+        nk = _count(float(pw.max()) - w0, depth_spacing, "depth")
+    else:
+        t0, t1 = (float(depth), float(depth)) if np.isscalar(depth) else (float(x) for x in depth)
+        if not (math.isfinite(t0) and math.isfinite(t1) and t1 >= t0):
+            raise ValueError("depth must be a finite range (t0, t1) with t1 >= t0 (got %r)" % (depth,))
+        w0, nk = t0, _count(t1 - t0, depth_spacing, "depth")
+    v = _lib.ViewDesc()
+    origin = c + (u0 * row_dir + v0 * col_dir + w0 * d) / vs
+    for a in range(3):
+        v.dims[a] = dims[a]
+        v.origin[a] = origin[a]
+        v.drow[a], v.dcol[a], v.ddepth[a] = spacing * row_dir[a] / vs[a], spacing * col_dir[a] / vs[a], depth_spacing * d[a] / vs[a]
+        v.box_lo[a], v.box_hi[a] = box_lo[a], box_hi[a]
+    v.lo, v.hi = -1.0, 1.0
+    v.rows, v.cols, v.depth = rows, cols, nk
+    return v
+
+
+def _with_range(view, lo, hi):
+    v = _lib.ViewDesc.from_buffer_copy(view)
+    v.lo, v.hi = float(lo), float(hi)
+    return v
+
+
+def sample_host(view, row, col, k):
+    """(pos [n, 3] float32, coord [n, 3] float32, inside [n] bool) of the samples (row, col, k) as the device computes them: the same
+    header on the host CPU (brief_view_sample_host), no GPU call"""
+    row, col, k = (np.ascontiguousarray(x, np.int32).ravel() for x in (row, col, k))
+    n = len(row)
+    if len(col) != n or len(k) != n:
+        raise ValueError("row, col and k must have one entry per sample")
+    pos, coord, inside = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32), np.empty(n, np.uint8)
+    p = (lambda a: a.ctypes.data_as(C.c_void_p))
+    _lib.check(_lib.lib().brief_view_sample_host(C.byref(view), p(row), p(col), p(k), n, p(pos), p(coord), p(inside)))
+    return pos, coord, inside.astype(bool)
+
+
+def clip_host(view):
+    """(k0 [rows, cols], cnt [rows, cols]) int32: the inside samples of every ray, k0 <= k < k0 + cnt, on the host CPU"""
+    k0, cnt = np.empty((view.rows, view.cols), np.int32), np.empty((view.rows, view.cols), np.int32)
+    _lib.check(_lib.lib().brief_view_clip_host(C.byref(view), k0.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p)))
+    return k0, cnt
+
+
+def _lanes(mean_count):
+    """adjacent lanes that share a ray: the power of two at or above the mean samples per hit ray, 1 .. 64"""
+    g = 1
+    while g < 64 and g < mean_count:
+        g *= 2
+    return g
+
+
+def render(phi, view, mode, lo, hi, out_kind, scale, vrange, chunk=None):
+    """the view of the net `phi` (any net kind and precision its forward entry serves) on the linspace grid view.dims over [lo, hi]:
+    (image [rows, cols, channels], hits [rows, cols] int32, stats) as device tensors.  mode 'max' | 'min' | 'mean' folds the inside
+    samples of every ray; 'slice' needs a view of depth 1 and gives that plane.  out_kind 'u8' | 'u16' with scale / vrange: the
+    fused integer epilogue of decode_box; max / min / slice images are of that dtype, a mean is float32 (float)((double)sum / hits).
+    Pixels whose ray has no inside sample (hits == 0) are 0.  Samples are evaluated in chunks of at most `chunk` (default
+    mip.DEFAULT_CHUNK): the memory is one chunk of coordinates and values plus the accumulators, whatever the volume's size.
+    stats = {rays, rays_hit, samples_inside, samples_evaluated}."""
+    import torch
+    from . import mip
+    if mode not in MODES:
+        raise ValueError("view mode %r is not one of %s" % (mode, " | ".join(MODES)))
+    if out_kind not in ("u8", "u16"):
+        raise ValueError("render folds the integer decode only: out_kind must be 'u8' or 'u16' (got %r)" % (out_kind,))
+    if mode == "slice" and view.depth != 1:
+        raise ValueError("mode 'slice' needs a view of one plane (depth 1); this one has %d samples per ray" % view.depth)
+    if int(phi.coords_channel) != 3:
+        raise ValueError("a view is defined for 3-D data only (the net takes %d coordinates)" % phi.coords_channel)
+    phi._require_gpu()
+    chunk = int(chunk or mip.DEFAULT_CHUNK)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    L, st = _lib.lib(), _lib.stream_ptr
+    v = _with_range(view, lo, hi)
+    dev, ch = phi.params.device, int(phi.data_channel)
+    rays = v.rows * v.cols
+    kind, dt = (_lib.OUT_U8, torch.uint8) if out_kind == "u8" else (_lib.OUT_U16, torch.uint16)
+    m = _lib.VIEW_MODE[mode]
+    k0, cnt = torch.empty(rays, dtype=torch.int32, device=dev), torch.empty(rays, dtype=torch.int32, device=dev)
+    _lib.check(L.brief_view_clip(C.byref(v), _lib.ptr(k0), _lib.ptr(cnt), st()))
+    off = torch.zeros(rays + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(cnt, 0, dtype=torch.int64, out=off[1:])
+    total, rays_hit = int(off[-1].item()), int((cnt > 0).sum().item())
+    hits = torch.zeros(rays, dtype=torch.int32, device=dev)
+    if mode == "mean":
+        acc = torch.zeros((rays, ch), dtype=torch.int64, device=dev)
+    else:
+        acc = torch.full((rays, ch), 0x7FFFFFFF if mode == "min" else 0, dtype=torch.int32, device=dev)
+    if total > 0:
+        phi.sync_packed()
+        lanes = _lanes(total / rays_hit)
+        cuts = torch.tensor(list(range(0, total, chunk)) + [total], dtype=torch.int64, device=dev)
+        r0s = torch.searchsorted(off[1:], cuts[:-1], right=True).cpu().tolist()       # the first ray that ends behind s0
+        r1s = torch.searchsorted(off[:-1], cuts[1:], right=False).cpu().tolist()      # the first ray that starts at or behind s1
+        cuts = cuts.cpu().tolist()
+        coords = torch.empty((min(chunk, total), 3), dtype=torch.float32, device=dev)
+        vals = torch.empty((min(chunk, total), ch), dtype=dt, device=dev)
+        for s0, s1, r0, r1 in zip(cuts[:-1], cuts[1:], r0s, r1s):
+            n = s1 - s0
+            _lib.check(L.brief_view_coords(C.byref(v), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(coords), st()))
+            b = _lib.BatchDesc(coords.data_ptr(), None, None, None, 0, n, 0, 0, 0)
+            _lib.check(phi._abi_forward(None, b, vals, kind, scale, vrange, n))
+            _lib.check(L.brief_view_fold(C.byref(v), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(vals), kind, ch, m,
+                                         _lib.ptr(hits), _lib.ptr(acc), st()))
+    image = torch.empty((v.rows, v.cols, ch), dtype=torch.float32 if mode == "mean" else dt, device=dev)
+    _lib.check(L.brief_view_finish(C.byref(v), kind, ch, m, _lib.ptr(hits), _lib.ptr(acc), _lib.ptr(image), st()))
+    stats = {"rays": rays, "rays_hit": rays_hit, "samples_inside": int(hits.sum(dtype=torch.int64).item()), "samples_evaluated": total}
+    return image, hits.view(v.rows, v.cols), stats
+
+
+# ---- artefacts ------------------------------------------------------------------------------------------------------------------
+def check_envelope(cf, sideinfos, mode, module_path=None):
+    """what the view decode supports, checked on option and side-info dicts before any decode: a SingleTask artefact without stored
+    corrections, 3-D uint8 / uint16 data with no axis of length 1 under a 'minmaxany_a_b' normalisation (the fused integer epilogue),
+    and a Decompress.postprocess that is local to a voxel (for a mean: the identity)"""
+    from .framework import _region_postprocess_check
+    from .io import minmaxany_range
+    from .misc import preprocess_is_identity
+    if mode not in MODES:
+        raise ValueError("view mode %r is not one of %s" % (mode, " | ".join(MODES)))
+    if "phi_features" not in sideinfos or (module_path is not None and os.path.isdir(os.path.join(os.path.dirname(str(module_path)), "sideinfos"))):
+        raise ValueError(DIVIDE_REFUSAL)
+    data_shape = list(sideinfos["data_shape"])
+    if "error_bound" in sideinfos:
+        raise ValueError("a view of an error-bounded artefact is refused: its corrections (error_bound %s) exist on the points of the "
+                         "fitted grid %s only, and a view samples between them" % (sideinfos["error_bound"], data_shape[:-1]))
+    if len(data_shape) != 4:
+        raise ValueError("a view is defined for 3-D data only: this artefact holds %d-D data of shape %s" % (len(data_shape) - 1, data_shape))
+    if sideinfos["dtype"] not in ("uint8", "uint16"):
+        raise ValueError("the view decode supports uint8 / uint16 data only (the fused integer decode); this artefact holds %s"
+                         % sideinfos["dtype"])
+    if minmaxany_range(cf.Normalize.name) is None:
+        raise ValueError("the view decode supports the 'minmaxany_a_b' normalisations only (the fused integer decode), not "
+                         "Normalize.name=%s" % cf.Normalize.name)
+    pp = cf.Decompress.postprocess
+    _region_postprocess_check(np.dtype(sideinfos["dtype"]), pp)
+    if any(int(n) < 2 for n in data_shape[:-1]):
+        raise ValueError("a view needs every axis of the grid to be at least 2 voxels long (got %s): an axis of length 1 has no coordinate "
+                         "range to sample" % (data_shape[:-1],))
+    if mode == "mean" and not preprocess_is_identity(np.zeros(1, np.dtype(sideinfos["dtype"])), pp.denoise.level, pp.denoise.close, pp.clip):
+        raise ValueError("a mean view with a Decompress.postprocess that changes values is refused: a threshold or a clip does not "
+                         "commute with a mean (denoise.level %s, clip %s); use an identity postprocess" % (pp.denoise.level, list(pp.clip)))
+
+
+def decompress_view(opt, module_path, sideinfos, direction, up=None, mode="max", region=None, centre=None, spacing=1.0, depth_spacing=1.0,
+                    size=None, depth=None, offset=None, voxel_size=(1, 1, 1), device="cuda", chunk=None, return_hits=False):
+    """an orthographic view of a stored SingleTask artefact as a numpy image [rows, cols, channels], without decoding the volume.
+    mode 'max' | 'min' (source dtype) or 'mean' (float32) folds every ray over the clip box `region` (None: the whole grid);
+    'slice' (source dtype) is the one plane at `offset` along `direction` from `centre` (default 0: through the centre).  The
+    geometry arguments are make_view's.  Decompress.postprocess is applied to the IMAGE for max, min and slice: on unsigned data the
+    threshold (x <= level -> 0) and the clip are monotone non-decreasing maps, which commute with max and min (the argument of
+    mip.decompress_mip), and on a slice they act per pixel as they would per voxel.  They do not commute with a mean: a mean with a
+    postprocess other than the identity is refused.  Refused by name before any decode: DivideTask and error-bounded artefacts, 2-D
+    data, dtypes other than uint8 / uint16, normalisations other than 'minmaxany_a_b', a denoise through a binary opening, an axis
+    of length 1.  return_hits: (image, hits [rows, cols] int32, stats) instead of the image."""
+    from .io import load_yaml, minmaxany_range
+    from .framework import _coords_range
+    from .mip import _load_phi, _postprocess
+    if isinstance(opt, str):
+        opt = config.load(opt)
+    if isinstance(sideinfos, str):
+        sideinfos = load_yaml(sideinfos)
+    cf = copy.deepcopy(opt.CompressFramework)
+    check_envelope(cf, sideinfos, mode, module_path)
+    if mode == "slice":
+        if depth is not None:
+            raise ValueError("mode 'slice' takes the plane's `offset`, not a `depth` range")
+        depth = 0.0 if offset is None else float(offset)
+    elif offset is not None:
+        raise ValueError("`offset` names the plane of mode 'slice'; mode %r takes a `depth` range" % mode)
+    dims = list(sideinfos["data_shape"])[:-1]
+    view = make_view(dims, direction, up, centre, spacing, depth_spacing, size, depth, voxel_size, region)
+    phi = _load_phi(cf, module_path, sideinfos, device)
+    lo, hi = _coords_range(cf.Compress.coords_mode)
+    image, hits, stats = render(phi, view, mode, lo, hi, "u8" if sideinfos["dtype"] == "uint8" else "u16", minmaxany_range(cf.Normalize.name),
+                                (sideinfos["min"], sideinfos["max"]), chunk=chunk)
+    img = image.cpu().numpy()
+    if mode != "mean":
+        img = np.array(_postprocess(img, cf.Decompress.postprocess), copy=True)
+        img[hits.cpu().numpy() == 0] = 0                            # (a ray without a sample stays 0 whatever the clip's floor is)
+    return (img, hits.cpu().numpy(), stats) if return_hits else img

@@ -19,6 +19,16 @@ uint16 artefacts; not with `--shape`).
 `--gradient components` writes the analytic spatial gradient of the stored net over the region, float32 [*extent, channels, axes] in
 grey levels per voxel step; `--gradient magnitude` writes its Euclidean norm over the axes, float32 [*extent, channels] (fp32 SIREN
 artefacts up to 1024 features under a `minmaxany_a_b` normalisation; `.npy` output only; not with `--mip`; `--shape` on SingleTask only).
+
+    python decompress.py -p <run yaml> -c <.../compressed> --region :,:,: --view dz,dy,dx [--view-up uz,uy,ux]
+        [--view-mode max|min|mean|slice] [--view-spacing s] [--view-depth-spacing t] [--view-size R,C] [--view-offset t]
+        [--voxel-size sz,sy,sx] -o out.tif|out.npy|out.png
+
+`--view` writes ONE image: the orthographic view of the artefact along the direction (dz, dy, dx), with `--region` as the clip box.
+`max` (default), `min` and `mean` fold every ray over the clip box (a rotating-MIP frame, a thick-slab mean); `slice` is the plane
+through the volume's centre, `--view-offset` voxels along the direction, at any orientation (an oblique reslice).  Only samples inside
+the clip box are evaluated; the volume is never decoded (SingleTask 3-D uint8 / uint16 artefacts; `mean` writes float32 `.npy` only;
+not with `--mip`, `--gradient`, `--shape` or a `--step` other than 1).
 """
 import argparse
 import os
@@ -39,8 +49,22 @@ def main(argv=None):
     ap.add_argument("--mip", action="store_true", help="write the region's three max-intensity projections <out>_mip_{d,h,w}<ext> instead of the region")
     ap.add_argument("--gradient", default=None, metavar="{components,magnitude}",
                     help="write the region's analytic spatial gradient (grey levels per voxel step) or its magnitude instead of the region (.npy)")
+    ap.add_argument("--view", default=None, metavar="dz,dy,dx", help="write the orthographic view along this direction instead of the region (--region is the clip box)")
+    ap.add_argument("--view-up", default=None, metavar="uz,uy,ux", help="the direction the image's rows run along (default: the grid axis the view direction has least of)")
+    ap.add_argument("--view-mode", default="max", help="max | min | mean | slice (default max)")
+    ap.add_argument("--view-spacing", type=float, default=1.0, help="distance between pixels, in voxels (default 1)")
+    ap.add_argument("--view-depth-spacing", type=float, default=1.0, help="distance between the samples of a ray, in voxels (default 1)")
+    ap.add_argument("--view-size", default=None, metavar="R,C", help="image size (default: the smallest image that covers the clip box)")
+    ap.add_argument("--view-offset", type=float, default=None, help="slice: the plane's offset from the volume's centre along the direction (default 0)")
+    ap.add_argument("--voxel-size", default=None, metavar="sz,sy,sx", help="physical extent of a voxel per axis (default 1,1,1)")
     ap.add_argument("-o", required=True, help="output file (.tif / .tiff / .npy / .png / .jpg)")
     args = ap.parse_args(argv)
+    if args.view is not None:
+        _view_refusals(args)          # every refusal by name, before the GPU path is imported
+    elif any(v is not None for v in (args.view_up, args.view_size, args.view_offset, args.voxel_size)) or args.view_mode != "max" \
+            or args.view_spacing != 1.0 or args.view_depth_spacing != 1.0:
+        raise SystemExit("--view-up / --view-mode / --view-spacing / --view-depth-spacing / --view-size / --view-offset / --voxel-size "
+                         "describe a --view: give its direction with --view dz,dy,dx")
     if args.gradient is not None:
         # every refusal by name, before the GPU path is imported
         if args.gradient not in ("components", "magnitude"):
@@ -66,6 +90,8 @@ def main(argv=None):
     region = parse_region(args.region)
     shape = parse_shape(args.shape) if args.shape else None
     divide = os.path.isdir(os.path.join(args.c, "sideinfos"))
+    if args.view is not None:
+        return _view(args, opt, region, divide)
     if args.mip:
         return _mip(args, opt, region, divide)
     if args.gradient is not None:
@@ -107,6 +133,69 @@ def _mip(args, opt, region, divide):
     print("%s region %s: max-intensity projections d %s, h %s, w %s, dtype %s, decoded in %.3f s -> %s_mip_{d,h,w}%s" % (
         "DivideTask" if divide else "SingleTask", args.region, tuple(mips[0].shape), tuple(mips[1].shape), tuple(mips[2].shape), mips[0].dtype,
         dt, os.path.splitext(args.o)[0], ext))
+    return 0
+
+
+def _floats(text, n, what):
+    try:
+        out = [float(x) for x in text.split(",")]
+    except ValueError:
+        out = []
+    if len(out) != n:
+        raise SystemExit("%s %s: expected %d comma-separated numbers" % (what, text, n))
+    return out
+
+
+def _view_refusals(args):
+    for flag, on in (("--mip", args.mip), ("--gradient", args.gradient is not None), ("--shape", args.shape is not None),
+                     ("--step %d" % args.step, args.step != 1)):
+        if on:
+            raise SystemExit("--view with %s: a view is one image of the fitted grid along its own direction (its sampling is set by "
+                             "--view-spacing and --view-depth-spacing); ask for one of them" % flag)
+    from brief_pytorch_amd.view import DIVIDE_REFUSAL, MODES
+    if args.view_mode not in MODES:
+        raise SystemExit("--view-mode %s: unknown mode (%s)" % (args.view_mode, ", ".join(MODES)))
+    ext = os.path.splitext(args.o)[1].lower()
+    if args.view_mode == "mean" and ext != ".npy":
+        raise SystemExit("--view-mode mean writes a float32 image as .npy only (got %s): float output in image formats is not supported"
+                         % (ext or "no extension"))
+    if args.view_mode != "slice" and args.view_offset is not None:
+        raise SystemExit("--view-offset names the plane of --view-mode slice (got --view-mode %s)" % args.view_mode)
+    _floats(args.view, 3, "--view")
+    if args.view_up is not None:
+        _floats(args.view_up, 3, "--view-up")
+    if args.voxel_size is not None:
+        _floats(args.voxel_size, 3, "--voxel-size")
+    if args.view_size is not None:
+        _floats(args.view_size, 2, "--view-size")
+    if os.path.isdir(os.path.join(args.c, "sideinfos")):
+        raise SystemExit("--view: " + DIVIDE_REFUSAL)
+
+
+def _view(args, opt, region, divide):
+    import numpy as np
+    import torch
+    from brief_pytorch_amd.framework import NFGR
+    from brief_pytorch_amd.tool import save_img
+    t0 = time.perf_counter()
+    try:
+        img, hits, stats = NFGR.decompress_view(
+            opt, os.path.join(args.c, "module"), os.path.join(args.c, "sideinfos.yaml"), _floats(args.view, 3, "--view"),
+            up=_floats(args.view_up, 3, "--view-up") if args.view_up is not None else None, mode=args.view_mode, region=region,
+            spacing=args.view_spacing, depth_spacing=args.view_depth_spacing,
+            size=[int(x) for x in _floats(args.view_size, 2, "--view-size")] if args.view_size is not None else None,
+            offset=args.view_offset, voxel_size=_floats(args.voxel_size, 3, "--voxel-size") if args.voxel_size is not None else (1, 1, 1),
+            return_hits=True)
+    except ValueError as e:                                       # a refusal (artefact kind, dtype, normalisation, postprocess, geometry, region)
+        raise SystemExit("--view: %s" % e)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    if os.path.splitext(args.o)[1].lower() == ".npy":
+        np.save(args.o, img)
+    else:
+        save_img(args.o, img)
+    print("SingleTask view %s (%s) of region %s: image %s, dtype %s, %d of %d rays hit, %d samples evaluated, decoded in %.3f s -> %s" % (
+        args.view, args.view_mode, args.region, tuple(img.shape), img.dtype, stats["rays_hit"], stats["rays"], stats["samples_evaluated"], dt, args.o))
     return 0
 
 

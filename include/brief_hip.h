@@ -562,6 +562,51 @@ int brief_siren_jac_forward(const brief_siren_desc *d, const float *packed, cons
 int brief_siren_jac_forward_box(const brief_siren_desc *d, const float *packed, const brief_grid_box *box, int64_t offset, int64_t n,
                                 float *value, float *jac, void *stream);
 
+/* ---- orthographic view decode: oblique slices and projections along any direction (csrc/brief_view.inc, csrc/brief_view.h) --------
+ * A view is a lattice of rows x cols rays with `depth` samples each, in voxel-index units of the fitted grid `dims` ((d,h,w) order):
+ *     position    p_a = fl(fl(fl(origin_a + fl(row * drow_a)) + fl(col * dcol_a)) + fl(k * ddepth_a))       (fp32, nothing contracted)
+ *     inside      box_lo_a <= p_a <= box_hi_a on every axis (an inclusive clip box within [0, dims_a - 1])
+ *     coordinate  p_a < (float)(dims_a / 2) ? fma(step_a, p_a, lo) : fma(-step_a, (float)(dims_a - 1) - p_a, hi),
+ *                 step_a = (hi - lo) / (float)(dims_a - 1): at an integer position the grid's own coordinate, bit for bit.
+ * Only samples inside the clip box are evaluated, by the net's own forward entry on explicit coordinates (integer output kind):
+ *   brief_view_clip    k0[r], cnt[r] (int32, r = row * cols + col): the inside samples of ray r are exactly k0 <= k < k0 + cnt (along a
+ *                      ray every p_a is monotone in k, so they are one interval, found by bisection on the position itself);
+ *   (caller)           off = exclusive scan of cnt (int64, rows * cols + 1 entries): the compacted, ray-major sample list, sample
+ *                      off[r] + j being (row, col, k0[r] + j);
+ *   brief_view_coords  coords[s - s0][3] for the samples s0 <= s < s1 of the list;
+ *   (caller)           vals[s - s0][channels] = the forward entry on coords, out_kind BRIEF_OUT_U8 | BRIEF_OUT_U16;
+ *   brief_view_fold    folds vals into the accumulators: hits[r] (int32, inside samples so far) and acc, int32 [rays][channels] for
+ *                      BRIEF_VIEW_MAX / _MIN / _SLICE (running max / min; a slice is the max over its single plane) or int64
+ *                      [rays][channels] for BRIEF_VIEW_MEAN (running sum).  The caller initialises hits = 0 and acc = 0 (min: INT32_MAX);
+ *   brief_view_finish  out[r][c] = acc as uint8 / uint16 (elem_kind), or for _MEAN the float (float)((double)sum / hits); 0 where hits == 0.
+ * [r0, r1) names the rays that may hold a sample of [s0, s1) (off[r + 1] > s0 and off[r] < s1); `lanes` (a power of two, 1 .. 64) is
+ * the number of adjacent lanes that share a ray, best near the mean cnt.  No atomics: within a launch a pixel has one owner; all
+ * accumulators are read-modify-write, so the chunks of a view follow each other on one stream.  Integers throughout: the result is
+ * exact and independent of chunking, `lanes` and the run.  Every device entry only enqueues on `stream`.
+ * brief_view_sample_host / brief_view_clip_host evaluate the same header on the host CPU, without any GPU call (pos, coord: [n][3];
+ * any of pos / coord / inside may be NULL).
+ * Limits (BRIEF_ERR_INVALID with a message naming the limit): rows, cols, depth 1 .. 2^24 - 1; dims 2 .. 2^31 - 1; everything finite;
+ * 0 <= box_lo <= box_hi <= dims - 1; at most 2^40 rays; no null buffer; channels 1 .. 4; sample indices inside the lattice. */
+typedef struct {
+    int64_t dims[3];
+    float lo, hi;                            /* coordinate range of the fitted grid */
+    float origin[3];                         /* position of sample (0, 0, 0) */
+    float drow[3], dcol[3], ddepth[3];       /* position steps per row, column and depth sample */
+    int32_t rows, cols, depth, reserved;
+    float box_lo[3], box_hi[3];              /* inclusive clip box */
+} brief_view_desc;
+enum { BRIEF_VIEW_MAX = 0, BRIEF_VIEW_MIN = 1, BRIEF_VIEW_MEAN = 2, BRIEF_VIEW_SLICE = 3 };
+int brief_view_clip(const brief_view_desc *view, int32_t *k0, int32_t *cnt, void *stream);
+int brief_view_coords(const brief_view_desc *view, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1, int64_t r0, int64_t r1,
+                      int32_t lanes, float *coords, void *stream);
+int brief_view_fold(const brief_view_desc *view, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1, int64_t r0, int64_t r1,
+                    int32_t lanes, const void *vals, int elem_kind, int32_t channels, int32_t mode, int32_t *hits, void *acc, void *stream);
+int brief_view_finish(const brief_view_desc *view, int elem_kind, int32_t channels, int32_t mode, const int32_t *hits, const void *acc, void *out,
+                      void *stream);
+int brief_view_sample_host(const brief_view_desc *view, const int32_t *row, const int32_t *col, const int32_t *k, int64_t n, float *pos, float *coord,
+                           uint8_t *inside);
+int brief_view_clip_host(const brief_view_desc *view, int32_t *k0, int32_t *cnt);
+
 #ifdef __cplusplus
 }
 #endif
