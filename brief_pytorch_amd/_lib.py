@@ -94,6 +94,7 @@ class ViewDesc(C.Structure):        # brief_view_desc
 
 
 VIEW_MODE = {"max": 0, "min": 1, "mean": 2, "slice": 3}      # BRIEF_VIEW_MAX .. BRIEF_VIEW_SLICE
+SURFACE_SIDE = {"above": 0, "below": 1}                      # BRIEF_SURFACE_ABOVE, BRIEF_SURFACE_BELOW
 
 TAPER_MAX_LAYERS = 16              # BRIEF_TAPER_MAX_LAYERS
 
@@ -125,7 +126,9 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_mip_accumulate",
            "brief_quant_workspace_bytes", "brief_quant_ranges", "brief_quant_apply", "brief_quant_decode",
            "brief_siren_jac_packed_count", "brief_siren_jac_repack", "brief_siren_jac_forward", "brief_siren_jac_forward_box",
-           "brief_view_clip", "brief_view_coords", "brief_view_fold", "brief_view_finish", "brief_view_sample_host", "brief_view_clip_host"] \
+           "brief_view_clip", "brief_view_coords", "brief_view_fold", "brief_view_finish", "brief_view_sample_host", "brief_view_clip_host",
+           "brief_surface_fold", "brief_surface_bracket", "brief_surface_coords", "brief_surface_step", "brief_surface_shade",
+           "brief_view_sample_t_host"] \
     + ["brief_%s_%s" % (prefix, entry) for prefix, _, _ in FAMILIES for entry in FAMILY_ENTRIES]
 
 
@@ -246,6 +249,12 @@ def lib():
     L.brief_view_finish.argtypes = [wp, C.c_int, i32, i32, vp, vp, vp, vp]
     L.brief_view_sample_host.argtypes = [wp, vp, vp, vp, i64, vp, vp, vp]
     L.brief_view_clip_host.argtypes = [wp, vp, vp]
+    L.brief_surface_fold.argtypes = [wp, vp, vp, i64, i64, i64, i64, i32, vp, C.c_int, i32, i32, i32, i32, vp, vp, vp]
+    L.brief_surface_bracket.argtypes = [wp, vp, vp, vp, vp, vp]
+    L.brief_surface_coords.argtypes = [wp, vp, vp, i32, vp, vp, vp]
+    L.brief_surface_step.argtypes = [wp, vp, C.c_int, i32, i32, i32, i32, vp, vp, vp]
+    L.brief_surface_shade.argtypes = [wp, vp, vp, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp, vp]
+    L.brief_view_sample_t_host.argtypes = [wp, vp, vp, vp, i64, vp, vp, vp]
     _LIB = L
     return L
 

@@ -50,6 +50,24 @@ BRIEF_HD float brief_view_at(const brief_view_desc &v, int a, float base, int32_
     return base + d;
 }
 
+// the same at a real depth t (the surface view's refinement): p_a = fl(base_a + fl(t * ddepth_a)).  (float)k is exact for k < 2^24, so
+// at an integer t this is brief_view_at, bit for bit; and t -> p_a is monotone, as k -> p_a is.
+BRIEF_HD float brief_view_at_t(const brief_view_desc &v, int a, float base, float t)
+{
+    BRIEF_VIEW_NO_CONTRACT
+    const float d = t * v.ddepth[a];
+    return base + d;
+}
+
+// the midpoint of a bracket, t_mid = fl(t_lo + fl(0.5f * fl(t_hi - t_lo))): never outside [t_lo, t_hi]
+BRIEF_HD float brief_view_mid(float t_lo, float t_hi)
+{
+    BRIEF_VIEW_NO_CONTRACT
+    const float w = t_hi - t_lo;
+    const float h = 0.5f * w;
+    return t_lo + h;
+}
+
 BRIEF_HD float brief_view_pos(const brief_view_desc &v, int a, int32_t row, int32_t col, int32_t k)
 {
     return brief_view_at(v, a, brief_view_base(v, a, row, col), k);

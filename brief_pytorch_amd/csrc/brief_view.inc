@@ -283,3 +283,240 @@ int brief_view_clip_host(const brief_view_desc *view, int32_t *k0, int32_t *cnt)
 }
 
 }   // extern "C"
+
+// ---- surface view: the first sample of every ray at which one channel of the integer decode crosses a level, a sub-sample bisection
+// of that crossing, and a Lambert shading from the net's analytic Jacobian at the hit (view.render_surface; DESIGN.md "Surface view").
+//   k_surface_fold     k_view_fold's walk, folding first[r] = the smallest inside k whose value passes the side test (int32, caller-
+//                      initialised to INT32_MAX) and hits[r]; one owner per pixel, a butterfly min within the group, no atomics.
+//   k_surface_bracket  t_lo / t_hi per ray: (first - 1, first) where first > k0 (the sample before the hit is inside and fails the test),
+//                      (first, first) for a CUT ray (first == k0: the clip box slices the object open), (NaN, NaN) without a hit.
+//   k_surface_coords   DENSE [rays][3] coordinates (and positions) at the bracket's midpoint, or at t_hi (the hit itself).
+//   (caller)           the net's forward entry on them, integer output kind.
+//   k_surface_step     t_hi = t_mid where the value at t_mid passes the test, t_lo = t_mid otherwise.
+//   k_surface_shade    the unit normal and the Lambert term of every pixel from the Jacobian at the hits.
+// The side test compares decoded integers, and the bracket moves by it alone: first, t_lo and t_hi are exact and do not depend on the
+// lanes per ray, on the chunking or on the run.
+struct SurfaceTest { int32_t channel, level, below; };      // passes: value[channel] >= level (above) or <= level (below)
+struct SurfaceVec { float v[3]; };
+
+__device__ __forceinline__ bool surface_pass(const SurfaceTest &t, int32_t y) { return t.below ? y <= t.level : y >= t.level; }
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_surface_fold(brief_view_desc v, ViewChunk ch, const int32_t *__restrict__ k0, const int64_t *__restrict__ off,
+                                                      const T *__restrict__ vals, int C, SurfaceTest test, int32_t *__restrict__ hits,
+                                                      int32_t *__restrict__ first)
+{
+    const int G = 1 << ch.lg, sub = threadIdx.x & (G - 1);
+    const int64_t groups = ((int64_t)gridDim.x * blockDim.x) >> ch.lg, nr = ch.r1 - ch.r0;
+    const int64_t iters = (nr + groups - 1) / groups;               // the same for every lane: the butterfly below needs the whole group
+    int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> ch.lg;
+    for (int64_t it = 0; it < iters; ++it, g += groups) {
+        const ViewRay q = view_ray(v, ch, off, g);
+        const int32_t kb = k0[q.r];
+        int n = 0;
+        int32_t f = INT32_MAX;
+        for (int64_t s = q.lo + sub; s < q.hi; s += G) {
+            const int32_t k = kb + (int32_t)(s - q.a);
+            if (!brief_view_inside(v, brief_view_at(v, 0, q.base[0], k), brief_view_at(v, 1, q.base[1], k), brief_view_at(v, 2, q.base[2], k)))
+                continue;
+            ++n;
+            if (k < f && surface_pass(test, (int32_t)vals[(s - ch.s0) * C + test.channel])) f = k;      // (a lane's k ascend: its first pass)
+        }
+        for (int o = G >> 1; o >= 1; o >>= 1) {
+            n += __shfl_xor(n, o);
+            const int32_t y = __shfl_xor(f, o);
+            f = y < f ? y : f;
+        }
+        if (sub == 0 && n > 0) {                                     // the pixel's owner
+            hits[q.r] += n;
+            if (f < first[q.r]) first[q.r] = f;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_surface_bracket(int64_t rays, const int32_t *__restrict__ k0, const int32_t *__restrict__ first,
+                                                         float *__restrict__ t_lo, float *__restrict__ t_hi)
+{
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rays; r += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t f = first[r];
+        const bool hit = f >= 0 && f != INT32_MAX;
+        const float hi = hit ? (float)f : __builtin_nanf("");
+        t_hi[r] = hi;
+        t_lo[r] = hit && f > k0[r] ? (float)(f - 1) : hi;
+    }
+}
+
+// the depth a round evaluates: the midpoint of a bracket, else t_hi (a cut ray's hit; NaN without a hit)
+__device__ __forceinline__ float surface_t(float lo, float hi, bool mid) { return mid && lo < hi ? brief_view_mid(lo, hi) : hi; }
+
+__global__ __launch_bounds__(256) void k_surface_coords(brief_view_desc v, SurfaceVec step, int mid, const float *__restrict__ t_lo,
+                                                        const float *__restrict__ t_hi, float *__restrict__ coords, float *__restrict__ pos)
+{
+    const int64_t rays = (int64_t)v.rows * v.cols;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rays; r += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t row = (int32_t)(r / v.cols), col = (int32_t)(r - (int64_t)row * v.cols);
+        const float t = surface_t(t_lo[r], t_hi[r], mid != 0);
+        const bool hit = t == t;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            // a ray without a hit gets the clip box's corner: a valid coordinate whose value nobody reads
+            const float p = hit ? brief_view_at_t(v, a, brief_view_base(v, a, row, col), t) : v.box_lo[a];
+            coords[r * 3 + a] = brief_view_coord(v, a, step.v[a], p);
+            if (pos) pos[r * 3 + a] = hit ? p : t;
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_surface_step(int64_t rays, const T *__restrict__ vals, int C, SurfaceTest test, float *__restrict__ t_lo,
+                                                      float *__restrict__ t_hi)
+{
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rays; r += (int64_t)gridDim.x * blockDim.x) {
+        const float lo = t_lo[r], hi = t_hi[r];
+        if (!(lo < hi)) continue;                                    // cut, or no hit: never refined
+        const float t = brief_view_mid(lo, hi);
+        if (surface_pass(test, (int32_t)vals[r * C + test.channel])) t_hi[r] = t; else t_lo[r] = t;
+    }
+}
+
+// g_a = jac[r][channel][a] * gscale_a (grey levels per physical unit); n = -g / |g| above (out of a bright object), +g / |g| below;
+// shade = max(0, -(n . light)), light the unit direction the light travels.  |g| == 0 or no hit: normal 0, shade 0.
+__global__ __launch_bounds__(256) void k_surface_shade(int64_t rays, const float *__restrict__ t, const float *__restrict__ jac, int C, SurfaceTest test,
+                                                       SurfaceVec gscale, SurfaceVec light, float *__restrict__ normal, float *__restrict__ shade)
+{
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rays; r += (int64_t)gridDim.x * blockDim.x) {
+        float n[3] = {0.f, 0.f, 0.f}, s = 0.f;
+        if (t[r] == t[r]) {
+            const float *j = jac + (r * C + test.channel) * 3;
+            const float g0 = j[0] * gscale.v[0], g1 = j[1] * gscale.v[1], g2 = j[2] * gscale.v[2];
+            const float len = sqrtf(g0 * g0 + g1 * g1 + g2 * g2);
+            if (len > 0.f && len - len == 0.f) {
+                const float sign = test.below ? 1.f : -1.f;
+                n[0] = sign * g0 / len; n[1] = sign * g1 / len; n[2] = sign * g2 / len;
+                const float d = -(n[0] * light.v[0] + n[1] * light.v[1] + n[2] * light.v[2]);
+                s = d > 0.f ? d : 0.f;
+            }
+        }
+        normal[r * 3] = n[0]; normal[r * 3 + 1] = n[1]; normal[r * 3 + 2] = n[2];
+        shade[r] = s;
+    }
+}
+
+static int check_surface_test(int elem_kind, int32_t channels, int32_t channel, int32_t level, int32_t side, SurfaceTest *t)
+{
+    if (elem_kind != BRIEF_OUT_U8 && elem_kind != BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "surface: elem_kind must be BRIEF_OUT_U8 (1) or BRIEF_OUT_U16 (2)");
+    if (channels < 1 || channels > 4) return fail(BRIEF_ERR_INVALID, "surface: channels must be 1..4");
+    if (channel < 0 || channel >= channels) return fail(BRIEF_ERR_INVALID, "surface: channel must be 0 .. channels - 1");
+    if (level < 0 || level > (elem_kind == BRIEF_OUT_U8 ? 255 : 65535))
+        return fail(BRIEF_ERR_INVALID, "surface: level must lie in the range of the integer decode (0 .. 255 for uint8, 0 .. 65535 for uint16)");
+    if (side != BRIEF_SURFACE_ABOVE && side != BRIEF_SURFACE_BELOW) return fail(BRIEF_ERR_INVALID, "surface: side must be BRIEF_SURFACE_ABOVE (0) or BRIEF_SURFACE_BELOW (1)");
+    t->channel = channel; t->level = level; t->below = side == BRIEF_SURFACE_BELOW;
+    return 0;
+}
+
+static int check_surface_rays(const brief_view_desc *v, int64_t *rays)
+{
+    if (int rc = check_view(v)) return rc;
+    *rays = (int64_t)v->rows * v->cols;
+    if (*rays > kViewMaxRays) return fail(BRIEF_ERR_INVALID, "view: more than 2^40 rays");
+    return 0;
+}
+
+extern "C" {
+
+int brief_surface_fold(const brief_view_desc *view, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1, int64_t r0, int64_t r1,
+                       int32_t lanes, const void *vals, int elem_kind, int32_t channels, int32_t channel, int32_t level, int32_t side, int32_t *hits,
+                       int32_t *first, void *stream)
+{
+    ViewChunk ch;
+    SurfaceTest t;
+    if (int rc = check_view_chunk(view, k0, off, s0, s1, r0, r1, lanes, &ch)) return rc;
+    if (!vals || !hits || !first) return fail(BRIEF_ERR_INVALID, "surface: null buffer");
+    if (int rc = check_surface_test(elem_kind, channels, channel, level, side, &t)) return rc;
+    const dim3 grid(view_blocks((r1 - r0) << ch.lg)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (elem_kind == BRIEF_OUT_U8) hipLaunchKernelGGL((k_surface_fold<uint8_t>), grid, block, 0, st, *view, ch, k0, off, (const uint8_t *)vals, (int)channels, t, hits, first);
+    else hipLaunchKernelGGL((k_surface_fold<uint16_t>), grid, block, 0, st, *view, ch, k0, off, (const uint16_t *)vals, (int)channels, t, hits, first);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_surface_bracket(const brief_view_desc *view, const int32_t *k0, const int32_t *first, float *t_lo, float *t_hi, void *stream)
+{
+    int64_t rays;
+    if (int rc = check_surface_rays(view, &rays)) return rc;
+    if (!k0 || !first || !t_lo || !t_hi) return fail(BRIEF_ERR_INVALID, "surface: null buffer");
+    hipLaunchKernelGGL(k_surface_bracket, dim3(view_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rays, k0, first, t_lo, t_hi);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_surface_coords(const brief_view_desc *view, const float *t_lo, const float *t_hi, int32_t midpoint, float *coords, float *pos, void *stream)
+{
+    int64_t rays;
+    if (int rc = check_surface_rays(view, &rays)) return rc;
+    if (!t_lo || !t_hi || !coords) return fail(BRIEF_ERR_INVALID, "surface: null buffer (pos alone may be NULL)");
+    if (midpoint != 0 && midpoint != 1) return fail(BRIEF_ERR_INVALID, "surface: midpoint must be 0 (the hit, t_hi) or 1 (the bracket's midpoint)");
+    SurfaceVec step;
+    for (int a = 0; a < 3; ++a) step.v[a] = brief_view_step(*view, a);
+    hipLaunchKernelGGL(k_surface_coords, dim3(view_blocks(rays)), dim3(256), 0, (hipStream_t)stream, *view, step, (int)midpoint, t_lo, t_hi, coords, pos);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_surface_step(const brief_view_desc *view, const void *vals, int elem_kind, int32_t channels, int32_t channel, int32_t level, int32_t side,
+                       float *t_lo, float *t_hi, void *stream)
+{
+    int64_t rays;
+    SurfaceTest t;
+    if (int rc = check_surface_rays(view, &rays)) return rc;
+    if (!vals || !t_lo || !t_hi) return fail(BRIEF_ERR_INVALID, "surface: null buffer");
+    if (int rc = check_surface_test(elem_kind, channels, channel, level, side, &t)) return rc;
+    const dim3 grid(view_blocks(rays)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (elem_kind == BRIEF_OUT_U8) hipLaunchKernelGGL((k_surface_step<uint8_t>), grid, block, 0, st, rays, (const uint8_t *)vals, (int)channels, t, t_lo, t_hi);
+    else hipLaunchKernelGGL((k_surface_step<uint16_t>), grid, block, 0, st, rays, (const uint16_t *)vals, (int)channels, t, t_lo, t_hi);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_surface_shade(const brief_view_desc *view, const float *t, const float *jac, int32_t channels, int32_t channel, int32_t side,
+                        const float *gscale, const float *light, float *normal, float *shade, void *stream)
+{
+    int64_t rays;
+    SurfaceTest test;
+    if (int rc = check_surface_rays(view, &rays)) return rc;
+    if (!t || !jac || !gscale || !light || !normal || !shade) return fail(BRIEF_ERR_INVALID, "surface: null buffer");
+    if (int rc = check_surface_test(BRIEF_OUT_U16, channels, channel, 0, side, &test)) return rc;
+    SurfaceVec g, l;
+    for (int a = 0; a < 3; ++a) {
+        g.v[a] = gscale[a]; l.v[a] = light[a];
+        if (g.v[a] - g.v[a] != 0.f || l.v[a] - l.v[a] != 0.f) return fail(BRIEF_ERR_INVALID, "surface: gscale and light must be finite");
+    }
+    hipLaunchKernelGGL(k_surface_shade, dim3(view_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rays, t, jac, (int)channels, test, g, l, normal, shade);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// brief_view_sample_host at a real depth t, 0 <= t <= depth - 1: the positions the refinement evaluates, on the host CPU
+int brief_view_sample_t_host(const brief_view_desc *view, const int32_t *row, const int32_t *col, const float *t, int64_t n, float *pos, float *coord,
+                             uint8_t *inside)
+{
+    if (int rc = check_view(view)) return rc;
+    if (!row || !col || !t || n < 0) return fail(BRIEF_ERR_INVALID, "view: null index buffer or negative count");
+    float step[3];
+    for (int a = 0; a < 3; ++a) step[a] = brief_view_step(*view, a);
+    for (int64_t i = 0; i < n; ++i) {
+        if (row[i] < 0 || row[i] >= view->rows || col[i] < 0 || col[i] >= view->cols || !(t[i] >= 0.f && t[i] <= (float)(view->depth - 1)))
+            return fail(BRIEF_ERR_INVALID, "view: a sample outside rows x cols x [0, depth - 1]");
+        float p[3];
+        for (int a = 0; a < 3; ++a) p[a] = brief_view_at_t(*view, a, brief_view_base(*view, a, row[i], col[i]), t[i]);
+        if (pos) { pos[3 * i] = p[0]; pos[3 * i + 1] = p[1]; pos[3 * i + 2] = p[2]; }
+        if (coord)
+            for (int a = 0; a < 3; ++a) coord[3 * i + a] = brief_view_coord(*view, a, step[a], p[a]);
+        if (inside) inside[i] = brief_view_inside(*view, p[0], p[1], p[2]) ? 1 : 0;
+    }
+    return 0;
+}
+
+}   // extern "C"

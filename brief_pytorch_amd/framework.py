@@ -326,6 +326,15 @@ class NFGR:
         from . import view
         return view.decompress_view(opt, module_path, sideinfos, direction, **kwargs)
 
+    @staticmethod
+    def decompress_surface(opt, module_path, sideinfos, direction, level, **kwargs):
+        """the isosurface view of a stored SingleTask artefact as a dict of numpy arrays: per ray of direction `direction` the first
+        sample at which a channel of the integer decode crosses `level` (a grey level BEFORE Decompress.postprocess), refined by
+        bisection (first, t, depth, position), and for an fp32 SIREN the unit normal and a Lambert-shaded image from the analytic
+        Jacobian (normal, shade).  The volume is never decoded.  view.decompress_surface has the arguments and the envelope."""
+        from . import view
+        return view.decompress_surface(opt, module_path, sideinfos, direction, level, **kwargs)
+
     # ---- spatial-gradient decode: the analytic Jacobian of the stored net in grey levels per voxel (brief_pytorch_amd/gradient.py)
     @staticmethod
     def decompress_gradient(opt, module_path, sideinfos, region=None, step=1, shape=None, device="cuda"):

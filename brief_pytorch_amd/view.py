@@ -4,7 +4,10 @@ box are evaluated, by the net's own forward entry on explicit coordinates, chunk
 accumulators on the device (max | min | mean along the ray, or a single plane: slice) and dropped.  The volume is never decoded.
 (csrc/brief_view.h has the geometry, csrc/brief_view.inc the kernels, DESIGN.md "View decode" the reasoning.)
 
-make_view is host arithmetic; brief_view_sample_host / brief_view_clip_host restate the device's geometry on the CPU; everything else
+The surface view (render_surface, decompress_surface) folds the same march to the FIRST sample of every ray at which a channel
+crosses a level, refines that hit by bisection and shades it with the net's analytic normal (DESIGN.md "Surface view").
+
+make_view is host arithmetic; brief_view_sample_host / brief_view_sample_t_host / brief_view_clip_host restate the device's geometry on the CPU; everything else
 needs a ROCm GPU (there is no CPU fallback)."""
 import copy
 import ctypes as C
@@ -162,12 +165,56 @@ def clip_host(view):
     return k0, cnt
 
 
+def sample_t_host(view, row, col, t):
+    """sample_host at real depths t (float32, 0 <= t <= depth - 1): position p_a = fl(base_a + fl(t * ddepth_a)), the positions the
+    surface view's refinement evaluates (brief_view_sample_t_host); at an integer t it is sample_host's sample k = t, bit for bit"""
+    row, col = (np.ascontiguousarray(x, np.int32).ravel() for x in (row, col))
+    t = np.ascontiguousarray(t, np.float32).ravel()
+    n = len(row)
+    if len(col) != n or len(t) != n:
+        raise ValueError("row, col and t must have one entry per sample")
+    pos, coord, inside = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32), np.empty(n, np.uint8)
+    p = (lambda a: a.ctypes.data_as(C.c_void_p))
+    _lib.check(_lib.lib().brief_view_sample_t_host(C.byref(view), p(row), p(col), p(t), n, p(pos), p(coord), p(inside)))
+    return pos, coord, inside.astype(bool)
+
+
 def _lanes(mean_count):
     """adjacent lanes that share a ray: the power of two at or above the mean samples per hit ray, 1 .. 64"""
     g = 1
     while g < 64 and g < mean_count:
         g *= 2
     return g
+
+
+def _march(phi, v, kind, dt, scale, vrange, chunk, fold):
+    """the part every view shares: clip the rays of `v` (lo / hi set), scan, and evaluate the compacted sample list chunk by chunk with
+    the net's own forward entry, handing each chunk to fold(k0, off, s0, s1, r0, r1, lanes, vals).  Returns (k0, total, rays_hit)."""
+    import torch
+    L, st = _lib.lib(), _lib.stream_ptr
+    dev, ch = phi.params.device, int(phi.data_channel)
+    rays = v.rows * v.cols
+    k0, cnt = torch.empty(rays, dtype=torch.int32, device=dev), torch.empty(rays, dtype=torch.int32, device=dev)
+    _lib.check(L.brief_view_clip(C.byref(v), _lib.ptr(k0), _lib.ptr(cnt), st()))
+    off = torch.zeros(rays + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(cnt, 0, dtype=torch.int64, out=off[1:])
+    total, rays_hit = int(off[-1].item()), int((cnt > 0).sum().item())
+    if total > 0:
+        phi.sync_packed()
+        lanes = _lanes(total / rays_hit)
+        cuts = torch.tensor(list(range(0, total, chunk)) + [total], dtype=torch.int64, device=dev)
+        r0s = torch.searchsorted(off[1:], cuts[:-1], right=True).cpu().tolist()       # the first ray that ends behind s0
+        r1s = torch.searchsorted(off[:-1], cuts[1:], right=False).cpu().tolist()      # the first ray that starts at or behind s1
+        cuts = cuts.cpu().tolist()
+        coords = torch.empty((min(chunk, total), 3), dtype=torch.float32, device=dev)
+        vals = torch.empty((min(chunk, total), ch), dtype=dt, device=dev)
+        for s0, s1, r0, r1 in zip(cuts[:-1], cuts[1:], r0s, r1s):
+            n = s1 - s0
+            _lib.check(L.brief_view_coords(C.byref(v), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(coords), st()))
+            b = _lib.BatchDesc(coords.data_ptr(), None, None, None, 0, n, 0, 0, 0)
+            _lib.check(phi._abi_forward(None, b, vals, kind, scale, vrange, n))
+            fold(k0, off, s0, s1, r0, r1, lanes, vals)
+    return k0, total, rays_hit
 
 
 def render(phi, view, mode, lo, hi, out_kind, scale, vrange, chunk=None):
@@ -198,36 +245,139 @@ def render(phi, view, mode, lo, hi, out_kind, scale, vrange, chunk=None):
     rays = v.rows * v.cols
     kind, dt = (_lib.OUT_U8, torch.uint8) if out_kind == "u8" else (_lib.OUT_U16, torch.uint16)
     m = _lib.VIEW_MODE[mode]
-    k0, cnt = torch.empty(rays, dtype=torch.int32, device=dev), torch.empty(rays, dtype=torch.int32, device=dev)
-    _lib.check(L.brief_view_clip(C.byref(v), _lib.ptr(k0), _lib.ptr(cnt), st()))
-    off = torch.zeros(rays + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(cnt, 0, dtype=torch.int64, out=off[1:])
-    total, rays_hit = int(off[-1].item()), int((cnt > 0).sum().item())
     hits = torch.zeros(rays, dtype=torch.int32, device=dev)
     if mode == "mean":
         acc = torch.zeros((rays, ch), dtype=torch.int64, device=dev)
     else:
         acc = torch.full((rays, ch), 0x7FFFFFFF if mode == "min" else 0, dtype=torch.int32, device=dev)
-    if total > 0:
-        phi.sync_packed()
-        lanes = _lanes(total / rays_hit)
-        cuts = torch.tensor(list(range(0, total, chunk)) + [total], dtype=torch.int64, device=dev)
-        r0s = torch.searchsorted(off[1:], cuts[:-1], right=True).cpu().tolist()       # the first ray that ends behind s0
-        r1s = torch.searchsorted(off[:-1], cuts[1:], right=False).cpu().tolist()      # the first ray that starts at or behind s1
-        cuts = cuts.cpu().tolist()
-        coords = torch.empty((min(chunk, total), 3), dtype=torch.float32, device=dev)
-        vals = torch.empty((min(chunk, total), ch), dtype=dt, device=dev)
-        for s0, s1, r0, r1 in zip(cuts[:-1], cuts[1:], r0s, r1s):
-            n = s1 - s0
-            _lib.check(L.brief_view_coords(C.byref(v), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(coords), st()))
-            b = _lib.BatchDesc(coords.data_ptr(), None, None, None, 0, n, 0, 0, 0)
-            _lib.check(phi._abi_forward(None, b, vals, kind, scale, vrange, n))
-            _lib.check(L.brief_view_fold(C.byref(v), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(vals), kind, ch, m,
-                                         _lib.ptr(hits), _lib.ptr(acc), st()))
+
+    def fold(k0, off, s0, s1, r0, r1, lanes, vals):
+        _lib.check(L.brief_view_fold(C.byref(v), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(vals), kind, ch, m,
+                                     _lib.ptr(hits), _lib.ptr(acc), st()))
+    _, total, rays_hit = _march(phi, v, kind, dt, scale, vrange, chunk, fold)
     image = torch.empty((v.rows, v.cols, ch), dtype=torch.float32 if mode == "mean" else dt, device=dev)
     _lib.check(L.brief_view_finish(C.byref(v), kind, ch, m, _lib.ptr(hits), _lib.ptr(acc), _lib.ptr(image), st()))
     stats = {"rays": rays, "rays_hit": rays_hit, "samples_inside": int(hits.sum(dtype=torch.int64).item()), "samples_evaluated": total}
     return image, hits.view(v.rows, v.cols), stats
+
+
+# ---- surface view: first-hit depth, refined, and shaded normals ---------------------------------------------------------------------
+SIDES = ("above", "below")
+MAX_REFINE = 16
+NO_HIT = 0x7FFFFFFF          # the fold's identity of `first`
+
+
+def check_surface(level, channel, side, refine, channels, out_kind):
+    """the surface view's own arguments, refused by name: (level, channel, refine) as ints"""
+    top = 255 if out_kind in ("u8", "uint8") else 65535
+    try:
+        lv = int(level)
+        whole = float(level) == lv
+    except (TypeError, ValueError):
+        whole = False
+    if not whole:
+        raise ValueError("level must be an integer grey level of the integer decode (got %r)" % (level,))
+    if not 0 <= lv <= top:
+        raise ValueError("level %d lies outside the range of the integer decode, 0 .. %d" % (lv, top))
+    if int(channel) != channel or not 0 <= int(channel) < int(channels):
+        raise ValueError("channel %r does not exist: the net has the channels 0 .. %d" % (channel, int(channels) - 1))
+    if side not in SIDES:
+        raise ValueError("side %r is not one of %s" % (side, " | ".join(SIDES)))
+    if int(refine) != refine or not 0 <= int(refine) <= MAX_REFINE:
+        raise ValueError("refine must be 0 .. %d rounds of bisection (got %r)" % (MAX_REFINE, refine))
+    return lv, int(channel), int(refine)
+
+
+def _unit3(v, what):
+    v = _vec3(v, what)
+    if not np.linalg.norm(v) > 0:
+        raise ValueError("%s must not be the zero vector" % what)
+    return v / np.linalg.norm(v)
+
+
+def render_surface(phi, view, level, lo, hi, out_kind, scale, vrange, channel=0, side="above", refine=8, shading=True, light=None,
+                   gscale=None, chunk=None):
+    """the isosurface view of the net `phi`: for every ray of `view` the first inside sample at which channel `channel` of the integer
+    decode (out_kind, scale, vrange: render's) passes the side test, value >= level ('above') or value <= level ('below'), refined
+    by `refine` rounds of bisection between that sample and the one before it, and shaded.  A dict of device tensors:
+        first     int32 [rows, cols]: the sample index k of the first hit, -1 without one
+        t_lo, t_hi, t  float32 [rows, cols]: the final bracket in sample units (the test fails at t_lo and passes at t_hi) and the
+                  hit t = t_hi; NaN without a hit.  A CUT ray (first is the ray's first inside sample: the clip box slices the object
+                  open) has no bracket: t_lo == t_hi == first, never refined.  refine=0: t == first.
+        position  float32 [rows, cols, 3]: the hit in voxel-index units, NaN without a hit
+        normal    float32 [rows, cols, 3], shade float32 [rows, cols] (None with shading=False): the unit normal -g / |g| ('above': out
+                  of a bright object) or +g / |g| ('below') of g_a = d(channel) / d(coordinate a) * gscale_a at the hit, from the
+                  analytic Jacobian (fp32 SIREN up to 1024 features; anything else is refused BEFORE any decode), and the Lambert term
+                  max(0, -(normal . light)).  gscale: grey levels per physical unit and coordinate unit, default gradient.voxel_scale
+                  (voxels of extent 1); light: the direction the light travels, in the normal's frame, default the view's own
+                  direction ddepth (a headlight; decompress_surface passes the physical one).  0 without a hit.
+        hits      int32 [rows, cols]: inside samples per ray
+        stats     render's keys, rays_surface (rays with a hit), rays_cut, refine_points (points the refinement evaluated)
+    The march evaluates exactly what render evaluates, in chunks of `chunk`; a refinement round is one dense pass over rows * cols
+    points (1 / depth of the march).  Every decision compares decoded integers: first, t_lo, t_hi do not depend on chunking or run."""
+    import torch
+    from . import gradient, mip
+    if out_kind not in ("u8", "u16"):
+        raise ValueError("render_surface tests the integer decode only: out_kind must be 'u8' or 'u16' (got %r)" % (out_kind,))
+    if int(phi.coords_channel) != 3:
+        raise ValueError("a view is defined for 3-D data only (the net takes %d coordinates)" % phi.coords_channel)
+    ch = int(phi.data_channel)
+    level, channel, refine = check_surface(level, channel, side, refine, ch, out_kind)
+    if shading:
+        why = gradient.refusal(getattr(type(phi), "kind", "SIREN"), phi.precision, phi.features)
+        if why is not None:
+            raise ValueError("normals and shading need the analytic Jacobian: %s; ask for shading=False" % why)
+    phi._require_gpu()
+    chunk = int(chunk or mip.DEFAULT_CHUNK)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    L, st = _lib.lib(), _lib.stream_ptr
+    v = _with_range(view, lo, hi)
+    dev, rays = phi.params.device, view.rows * view.cols
+    kind, dt = (_lib.OUT_U8, torch.uint8) if out_kind == "u8" else (_lib.OUT_U16, torch.uint16)
+    sd = _lib.SURFACE_SIDE[side]
+    hits = torch.zeros(rays, dtype=torch.int32, device=dev)
+    first = torch.full((rays,), NO_HIT, dtype=torch.int32, device=dev)
+
+    def fold(k0, off, s0, s1, r0, r1, lanes, vals):
+        _lib.check(L.brief_surface_fold(C.byref(v), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(vals), kind, ch, channel, level,
+                                        sd, _lib.ptr(hits), _lib.ptr(first), st()))
+    k0, total, rays_hit = _march(phi, v, kind, dt, scale, vrange, chunk, fold)
+    t_lo, t_hi = torch.empty(rays, dtype=torch.float32, device=dev), torch.empty(rays, dtype=torch.float32, device=dev)
+    _lib.check(L.brief_surface_bracket(C.byref(v), _lib.ptr(k0), _lib.ptr(first), _lib.ptr(t_lo), _lib.ptr(t_hi), st()))
+    hit = first != NO_HIT
+    rays_surface, rays_cut = int(hit.sum().item()), int((hit & (first == k0)).sum().item())
+    coords = torch.empty((rays, 3), dtype=torch.float32, device=dev)
+    pos = torch.empty((rays, 3), dtype=torch.float32, device=dev)
+    refine_points = 0
+    if refine and rays_surface > rays_cut:
+        vals = torch.empty((rays, ch), dtype=dt, device=dev)
+        for _ in range(refine):
+            _lib.check(L.brief_surface_coords(C.byref(v), _lib.ptr(t_lo), _lib.ptr(t_hi), 1, _lib.ptr(coords), None, st()))
+            for o in range(0, rays, mip.DEFAULT_CHUNK):            # (dense: rows * cols points, whatever `chunk` bounds the march to)
+                n = min(mip.DEFAULT_CHUNK, rays - o)
+                b = _lib.BatchDesc(coords[o:o + n].data_ptr(), None, None, None, 0, n, 0, 0, 0)
+                _lib.check(phi._abi_forward(None, b, vals[o:o + n], kind, scale, vrange, n))
+            _lib.check(L.brief_surface_step(C.byref(v), _lib.ptr(vals), kind, ch, channel, level, sd, _lib.ptr(t_lo), _lib.ptr(t_hi), st()))
+        refine_points = refine * rays
+    _lib.check(L.brief_surface_coords(C.byref(v), _lib.ptr(t_lo), _lib.ptr(t_hi), 0, _lib.ptr(coords), _lib.ptr(pos), st()))
+    normal = shade = None
+    if shading:
+        g = np.asarray(gscale if gscale is not None else gradient.voxel_scale(list(view.dims), lo, hi, scale, vrange[0], vrange[1]), np.float64)
+        if g.shape != (3,) or not np.isfinite(g).all():
+            raise ValueError("gscale must be three finite numbers in (z, y, x) order (got %r)" % (gscale,))
+        l = _unit3(light if light is not None else list(view.ddepth), "light")
+        _, jac = phi.spatial_gradient(coords, want_value=False)
+        normal = torch.empty((view.rows, view.cols, 3), dtype=torch.float32, device=dev)
+        shade = torch.empty((view.rows, view.cols), dtype=torch.float32, device=dev)
+        f3 = C.c_float * 3
+        _lib.check(L.brief_surface_shade(C.byref(v), _lib.ptr(t_hi), _lib.ptr(jac), ch, channel, sd, f3(*g), f3(*l), _lib.ptr(normal),
+                                         _lib.ptr(shade), st()))
+    shape = (view.rows, view.cols)
+    stats = {"rays": rays, "rays_hit": rays_hit, "samples_inside": int(hits.sum(dtype=torch.int64).item()), "samples_evaluated": total,
+             "rays_surface": rays_surface, "rays_cut": rays_cut, "refine_points": refine_points}
+    return {"first": torch.where(hit, first, torch.full_like(first, -1)).view(shape), "t_lo": t_lo.view(shape), "t_hi": t_hi.view(shape),
+            "t": t_hi.view(shape), "position": pos.view(*shape, 3), "normal": normal, "shade": shade, "hits": hits.view(shape), "stats": stats}
 
 
 # ---- artefacts ------------------------------------------------------------------------------------------------------------------
@@ -301,3 +451,49 @@ def decompress_view(opt, module_path, sideinfos, direction, up=None, mode="max",
         img = np.array(_postprocess(img, cf.Decompress.postprocess), copy=True)
         img[hits.cpu().numpy() == 0] = 0                            # (a ray without a sample stays 0 whatever the clip's floor is)
     return (img, hits.cpu().numpy(), stats) if return_hits else img
+
+
+def decompress_surface(opt, module_path, sideinfos, direction, level, up=None, region=None, centre=None, spacing=1.0, depth_spacing=1.0,
+                       size=None, depth=None, voxel_size=(1, 1, 1), channel=0, side="above", refine=8, shading=True, light=None, device="cuda",
+                       chunk=None):
+    """the isosurface view of a stored SingleTask artefact, without decoding the volume: a dict of numpy arrays, render_surface's
+    first, t_lo, t_hi, t, position, normal, shade, hits and stats, plus depth = t * depth_spacing (float32, physical units along the
+    ray from the view's first sample plane; NaN without a hit).  The geometry arguments are make_view's; `region` is the clip box.
+
+    `level` is a grey level of the artefact's INTEGER DECODE (uint8 / uint16 after the fused de-normalisation), compared BEFORE
+    Decompress.postprocess: a threshold or a clip of the postprocess does not move the surface.  side 'above': the first sample with
+    value >= level (the surface of a bright object); 'below': value <= level.  Normals are physical: the stored net's analytic
+    gradient in grey levels per physical unit (gradient.voxel_scale / voxel_size per axis), and `light` is the physical direction
+    the light travels, default `direction` (a headlight).  Refused by name before any decode: everything view.check_envelope
+    refuses, a level outside the dtype's range, a channel that does not exist, a side other than 'above' | 'below', refine outside
+    0 .. 16, and shading behind a net without the Jacobian kernel (anything but an fp32 SIREN of at most 1024 features; ask for
+    shading=False to get first, depth and position)."""
+    from . import gradient
+    from .io import load_yaml, minmaxany_range
+    from .framework import _coords_range
+    from .mip import _load_phi
+    if isinstance(opt, str):
+        opt = config.load(opt)
+    if isinstance(sideinfos, str):
+        sideinfos = load_yaml(sideinfos)
+    cf = copy.deepcopy(opt.CompressFramework)
+    check_envelope(cf, sideinfos, "max", module_path)
+    data_shape = list(sideinfos["data_shape"])
+    check_surface(level, channel, side, refine, data_shape[-1], sideinfos["dtype"])
+    if shading:
+        why = gradient.refusal(sideinfos["phi_name"], str(sideinfos.get("phi_precision", cf.Compress.get("precision", "fp32"))),
+                               sideinfos["phi_features"])
+        if why is not None:
+            raise ValueError("normals and shading need the analytic Jacobian: %s; ask for shading=False" % why)
+    dims = data_shape[:-1]
+    view = make_view(dims, direction, up, centre, spacing, depth_spacing, size, depth, voxel_size, region)
+    physical = frame(direction, up)[2] if light is None else _unit3(light, "light")
+    rng = minmaxany_range(cf.Normalize.name)
+    lo, hi = _coords_range(cf.Compress.coords_mode)
+    gscale = gradient.voxel_scale(dims, lo, hi, rng, sideinfos["min"], sideinfos["max"]) / _vec3(voxel_size, "voxel_size")
+    phi = _load_phi(cf, module_path, sideinfos, device)
+    out = render_surface(phi, view, level, lo, hi, "u8" if sideinfos["dtype"] == "uint8" else "u16", rng, (sideinfos["min"], sideinfos["max"]),
+                         channel=channel, side=side, refine=refine, shading=shading, light=physical, gscale=gscale, chunk=chunk)
+    res = {k: (x.cpu().numpy() if hasattr(x, "cpu") else x) for k, x in out.items()}
+    res["depth"] = res["t"] * np.float32(depth_spacing)
+    return res

@@ -29,6 +29,17 @@ artefacts up to 1024 features under a `minmaxany_a_b` normalisation; `.npy` outp
 through the volume's centre, `--view-offset` voxels along the direction, at any orientation (an oblique reslice).  Only samples inside
 the clip box are evaluated; the volume is never decoded (SingleTask 3-D uint8 / uint16 artefacts; `mean` writes float32 `.npy` only;
 not with `--mip`, `--gradient`, `--shape` or a `--step` other than 1).
+
+    python decompress.py -p <run yaml> -c <.../compressed> --region :,:,: --view dz,dy,dx --view-surface LEVEL
+        [--view-surface-side above|below] [--view-refine N] [--view-channel C] [--view-light lz,ly,lx] -o out.png|out.tif|out.npy
+
+`--view-surface LEVEL` renders an ISOSURFACE instead of a projection: per ray the first sample at which channel C of the integer decode
+is >= LEVEL (`above`, default) or <= LEVEL (`below`), refined by N rounds of bisection (default 8, 0 .. 16), and Lambert-shaded with the
+stored net's own analytic normal, lit along `--view-light` (default: the view direction, a headlight).  LEVEL is a grey level of the
+integer decode, before `Decompress.postprocess`.  `.png` / `.tif` hold the shaded image as uint8, floor(255 * shade + 0.5); `.npy` holds
+float32 [rows, cols, 5] = depth, normal (z, y, x), shade, with NaN depth where no ray hits.  Artefacts other than an fp32 SIREN up to
+1024 features have no analytic normal: `.npy` then holds the depth alone, [rows, cols], and an image output is refused by name (the
+view options that shape the geometry apply; not with `--view-mode` or `--view-offset`).
 """
 import argparse
 import os
@@ -56,11 +67,19 @@ def main(argv=None):
     ap.add_argument("--view-depth-spacing", type=float, default=1.0, help="distance between the samples of a ray, in voxels (default 1)")
     ap.add_argument("--view-size", default=None, metavar="R,C", help="image size (default: the smallest image that covers the clip box)")
     ap.add_argument("--view-offset", type=float, default=None, help="slice: the plane's offset from the volume's centre along the direction (default 0)")
+    ap.add_argument("--view-surface", type=int, default=None, metavar="LEVEL", help="render the isosurface of this grey level of the integer decode: first-hit depth and shaded normals")
+    ap.add_argument("--view-surface-side", default=None, help="above (value >= LEVEL, default) | below (value <= LEVEL)")
+    ap.add_argument("--view-refine", type=int, default=None, metavar="N", help="rounds of bisection of the hit, 0 .. 16 (default 8)")
+    ap.add_argument("--view-channel", type=int, default=None, metavar="C", help="the channel the level is tested on (default 0)")
+    ap.add_argument("--view-light", default=None, metavar="lz,ly,lx", help="the physical direction the light travels (default: the view direction)")
     ap.add_argument("--voxel-size", default=None, metavar="sz,sy,sx", help="physical extent of a voxel per axis (default 1,1,1)")
     ap.add_argument("-o", required=True, help="output file (.tif / .tiff / .npy / .png / .jpg)")
     args = ap.parse_args(argv)
     if args.view is not None:
         _view_refusals(args)          # every refusal by name, before the GPU path is imported
+    elif args.view_surface is not None or any(v is not None for v in (args.view_surface_side, args.view_refine, args.view_channel, args.view_light)):
+        raise SystemExit("--view-surface / --view-surface-side / --view-refine / --view-channel / --view-light describe the isosurface of a "
+                         "--view: give its direction with --view dz,dy,dx")
     elif any(v is not None for v in (args.view_up, args.view_size, args.view_offset, args.voxel_size)) or args.view_mode != "max" \
             or args.view_spacing != 1.0 or args.view_depth_spacing != 1.0:
         raise SystemExit("--view-up / --view-mode / --view-spacing / --view-depth-spacing / --view-size / --view-offset / --voxel-size "
@@ -153,6 +172,28 @@ def _view_refusals(args):
             raise SystemExit("--view with %s: a view is one image of the fitted grid along its own direction (its sampling is set by "
                              "--view-spacing and --view-depth-spacing); ask for one of them" % flag)
     from brief_pytorch_amd.view import DIVIDE_REFUSAL, MODES
+    if args.view_surface is None:
+        for flag, v in (("--view-surface-side", args.view_surface_side), ("--view-refine", args.view_refine), ("--view-channel", args.view_channel),
+                        ("--view-light", args.view_light)):
+            if v is not None:
+                raise SystemExit("%s describes an isosurface: give its level with --view-surface LEVEL" % flag)
+    else:
+        from brief_pytorch_amd.view import MAX_REFINE, SIDES
+        if args.view_mode != "max":
+            raise SystemExit("--view-surface with --view-mode %s: an isosurface is a view of its own (the first crossing of a level along "
+                             "every ray); ask for one of them" % args.view_mode)
+        if args.view_offset is not None:
+            raise SystemExit("--view-surface with --view-offset: the offset names the plane of --view-mode slice")
+        if args.view_surface_side is not None and args.view_surface_side not in SIDES:
+            raise SystemExit("--view-surface-side %s: unknown side (%s)" % (args.view_surface_side, ", ".join(SIDES)))
+        if args.view_refine is not None and not 0 <= args.view_refine <= MAX_REFINE:
+            raise SystemExit("--view-refine %d: the rounds of bisection must be 0 .. %d" % (args.view_refine, MAX_REFINE))
+        if args.view_channel is not None and args.view_channel < 0:
+            raise SystemExit("--view-channel %d: a channel is 0 or above" % args.view_channel)
+        if args.view_surface < 0 or args.view_surface > 65535:
+            raise SystemExit("--view-surface %d: the level must be a grey level of the integer decode, 0 .. 65535" % args.view_surface)
+        if args.view_light is not None:
+            _floats(args.view_light, 3, "--view-light")
     if args.view_mode not in MODES:
         raise SystemExit("--view-mode %s: unknown mode (%s)" % (args.view_mode, ", ".join(MODES)))
     ext = os.path.splitext(args.o)[1].lower()
@@ -177,6 +218,8 @@ def _view(args, opt, region, divide):
     import torch
     from brief_pytorch_amd.framework import NFGR
     from brief_pytorch_amd.tool import save_img
+    if args.view_surface is not None:
+        return _surface(args, opt, region)
     t0 = time.perf_counter()
     try:
         img, hits, stats = NFGR.decompress_view(
@@ -196,6 +239,51 @@ def _view(args, opt, region, divide):
         save_img(args.o, img)
     print("SingleTask view %s (%s) of region %s: image %s, dtype %s, %d of %d rays hit, %d samples evaluated, decoded in %.3f s -> %s" % (
         args.view, args.view_mode, args.region, tuple(img.shape), img.dtype, stats["rays_hit"], stats["rays"], stats["samples_evaluated"], dt, args.o))
+    return 0
+
+
+def _surface(args, opt, region):
+    import numpy as np
+    import torch
+    from brief_pytorch_amd import gradient
+    from brief_pytorch_amd.framework import NFGR
+    from brief_pytorch_amd.io import load_yaml
+    from brief_pytorch_amd.tool import save_img
+    side_path = os.path.join(args.c, "sideinfos.yaml")
+    npy = os.path.splitext(args.o)[1].lower() == ".npy"
+    t0 = time.perf_counter()
+    try:
+        side = load_yaml(side_path)
+        precision = str(side.get("phi_precision", opt.CompressFramework.Compress.get("precision", "fp32")))
+        why = gradient.refusal(side.get("phi_name"), precision, side.get("phi_features", 0)) if "phi_features" in side else None
+        if why is not None and not npy:
+            raise ValueError("a shaded image needs the analytic Jacobian: %s; write the depth with -o <file>.npy" % why)
+        res = NFGR.decompress_surface(
+            opt, os.path.join(args.c, "module"), side, _floats(args.view, 3, "--view"), args.view_surface,
+            up=_floats(args.view_up, 3, "--view-up") if args.view_up is not None else None, region=region,
+            spacing=args.view_spacing, depth_spacing=args.view_depth_spacing,
+            size=[int(x) for x in _floats(args.view_size, 2, "--view-size")] if args.view_size is not None else None,
+            voxel_size=_floats(args.voxel_size, 3, "--voxel-size") if args.voxel_size is not None else (1, 1, 1),
+            channel=args.view_channel or 0, side=args.view_surface_side or "above", refine=8 if args.view_refine is None else args.view_refine,
+            shading=why is None, light=_floats(args.view_light, 3, "--view-light") if args.view_light is not None else None)
+    except ValueError as e:                                       # a refusal (artefact kind, dtype, normalisation, level, channel, net, geometry)
+        raise SystemExit("--view-surface: %s" % e)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    if not npy:
+        data = np.floor(255.0 * res["shade"].astype(np.float64) + 0.5).astype(np.uint8)[..., None]
+        save_img(args.o, data)
+    elif res["shade"] is None:
+        data = res["depth"]
+        np.save(args.o, data)
+    else:
+        data = np.concatenate([res["depth"][..., None], res["normal"], res["shade"][..., None]], axis=-1).astype(np.float32)
+        np.save(args.o, data)
+    stats = res["stats"]
+    print("SingleTask surface view %s (level %d, %s) of region %s: %s %s, dtype %s, %d of %d rays hit the surface (%d cut by the clip box), "
+          "%d samples evaluated, %d refinement points, decoded in %.3f s -> %s" % (
+              args.view, args.view_surface, args.view_surface_side or "above", args.region, "image" if not npy else "array", tuple(data.shape),
+              data.dtype, stats["rays_surface"], stats["rays"], stats["rays_cut"], stats["samples_evaluated"], stats["refine_points"], dt, args.o))
     return 0
 
 

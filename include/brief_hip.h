@@ -607,6 +607,46 @@ int brief_view_sample_host(const brief_view_desc *view, const int32_t *row, cons
                            uint8_t *inside);
 int brief_view_clip_host(const brief_view_desc *view, int32_t *k0, int32_t *cnt);
 
+/* ---- surface view: first-hit depth, sub-sample refinement and shaded normals of an isosurface (csrc/brief_view.inc) ----------------
+ * For every ray of a view: the first inside sample at which channel `channel` of the integer decode passes the side test,
+ * value >= level (BRIEF_SURFACE_ABOVE) or value <= level (BRIEF_SURFACE_BELOW); a bisection of that crossing; a Lambert shading from
+ * the analytic Jacobian at the hit.  Clip, scan and the march's coordinates are brief_view_clip / (caller) / brief_view_coords:
+ *   brief_surface_fold     brief_view_fold's arguments and walk; folds first[r] (int32, caller-initialised to INT32_MAX: the smallest
+ *                          inside k whose value passes) and hits[r] (int32, caller-initialised to 0), read-modify-write, one owner per
+ *                          pixel, no atomics;
+ *   brief_surface_bracket  t_lo[r], t_hi[r] (float): (first - 1, first) where first > k0 (sample first - 1 is inside and fails the test),
+ *                          (first, first) for a CUT ray (first == k0: the clip box slices the object open; never refined), (NaN, NaN)
+ *                          without a hit (first < 0 or INT32_MAX);
+ *   brief_surface_coords   DENSE coords[r][3], and pos[r][3] unless NULL, of every ray at depth t = fl(t_lo + fl(0.5f * fl(t_hi - t_lo)))
+ *                          where t_lo < t_hi and midpoint == 1, else at t = t_hi: position p_a = fl(base_a + fl(t * ddepth_a)), base_a
+ *                          the position of sample (row, col, 0); at an integer t the sample's own position, bit for bit.  A ray
+ *                          without a hit gets the clip box's corner box_lo as a valid coordinate (its value is never read), pos NaN;
+ *   (caller)               vals[r][channels] = the forward entry on coords, out_kind BRIEF_OUT_U8 | BRIEF_OUT_U16;
+ *   brief_surface_step     where t_lo < t_hi: t_hi = t_mid if vals[r][channel] passes the test, else t_lo = t_mid.  The test fails at
+ *                          t_lo and passes at t_hi before and after; t_hi is the hit;
+ *   brief_surface_shade    from jac[r][channels][3] (brief_siren_jac_forward on the hits' coordinates): g_a = jac[r][channel][a] *
+ *                          gscale[a] (the host's grey levels per physical unit), normal[r][3] = -g / |g| (ABOVE: out of a bright object)
+ *                          or +g / |g| (BELOW), shade[r] = max(0, -(normal . light)), light[3] the unit direction the light travels.
+ *                          normal and shade are 0 where t[r] is NaN (no hit) or |g| is 0 or not finite.
+ * Every decision compares decoded integers: first, t_lo and t_hi are exact and independent of chunking, `lanes` and the run.  gscale
+ * and light are HOST pointers to three floats; every other buffer is device memory.  Every device entry only enqueues on `stream`.
+ * brief_view_sample_t_host is brief_view_sample_host at a real depth 0 <= t <= depth - 1, on the host CPU.
+ * Limits (BRIEF_ERR_INVALID with a message naming the limit, before any launch): those of the view entries; no null buffer (pos of
+ * brief_surface_coords excepted); channels 1 .. 4; channel 0 .. channels - 1; level 0 .. 255 (uint8) or 0 .. 65535 (uint16); side
+ * BRIEF_SURFACE_ABOVE | _BELOW; midpoint 0 | 1; gscale and light finite. */
+enum { BRIEF_SURFACE_ABOVE = 0, BRIEF_SURFACE_BELOW = 1 };
+int brief_surface_fold(const brief_view_desc *view, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1, int64_t r0, int64_t r1,
+                       int32_t lanes, const void *vals, int elem_kind, int32_t channels, int32_t channel, int32_t level, int32_t side, int32_t *hits,
+                       int32_t *first, void *stream);
+int brief_surface_bracket(const brief_view_desc *view, const int32_t *k0, const int32_t *first, float *t_lo, float *t_hi, void *stream);
+int brief_surface_coords(const brief_view_desc *view, const float *t_lo, const float *t_hi, int32_t midpoint, float *coords, float *pos, void *stream);
+int brief_surface_step(const brief_view_desc *view, const void *vals, int elem_kind, int32_t channels, int32_t channel, int32_t level, int32_t side,
+                       float *t_lo, float *t_hi, void *stream);
+int brief_surface_shade(const brief_view_desc *view, const float *t, const float *jac, int32_t channels, int32_t channel, int32_t side,
+                        const float *gscale, const float *light, float *normal, float *shade, void *stream);
+int brief_view_sample_t_host(const brief_view_desc *view, const int32_t *row, const int32_t *col, const float *t, int64_t n, float *pos, float *coord,
+                             uint8_t *inside);
+
 #ifdef __cplusplus
 }
 #endif
