@@ -20,9 +20,10 @@ import torch
 
 from . import _lib, config, corrections, quantize
 from . import region as region_mod
+from .artefact import _coords_range, _load_corrections, _region_postprocess_check, check_error_bound      # noqa: F401 (re-exported: tests and bench.py import them from here)
+from .artefact import block_paths, divide_blocks, meeting, open_artefact
 from .fit import Fitter
-from .io import (get_folder_size, get_type_max, invnormalize_data, minmaxany_range, normalize_data, normalize_data_device, range_limit, save_yaml,
-                 load_yaml)
+from .io import get_folder_size, get_type_max, invnormalize_data, minmaxany_range, normalize_data, normalize_data_device, save_yaml, load_yaml
 from .metrics import cal_ssim, eval_performance, gpu_eval_u16, gpu_ssim_u16, psnr_from_sse
 from .misc import (alloc_param, cal_divide_num, divide_data, merge_divided_data, mip_ops, save_mips, parse_checkpoints,
                    parse_chunk_name, parse_weight, preprocess, preprocess_is_identity, weight_is_unit)
@@ -182,48 +183,24 @@ class NFGR:
         """opt: loaded options (or a path); sideinfos: dict (or a path).  Returns the numpy volume in
         the source dtype.  The whole grid is evaluated by the forward kernel with the de-normalise +
         truncating cast fused in when Normalize is 'minmaxany_a_b'."""
-        if isinstance(opt, str):
-            opt = config.load(opt)
-        if isinstance(sideinfos, str):
-            sideinfos = load_yaml(sideinfos)
-        cf = copy.deepcopy(opt.CompressFramework)
-        corr = _load_corrections(cf, module_path, sideinfos)      # error-bounded artefacts: raises before any decode if they cannot be honoured
-        cf.Module.phi.features = sideinfos["phi_features"]
-        cf.Module.phi.name = sideinfos["phi_name"]
-        shape = list(sideinfos["data_shape"])
-        dims = shape[:-1]
-        lo, hi = _coords_range(cf.Compress.coords_mode)
-        rng = minmaxany_range(cf.Normalize.name)
-        if rng is not None and sideinfos["dtype"] in ("uint8", "uint16"):
-            out = NFGR._decode_integer(cf, module_path, sideinfos, device)
+        art = open_artefact(opt, module_path, sideinfos)
+        corr = art.corrections()      # error-bounded artefacts: raises before any decode if they cannot be honoured
+        if art.integer:
+            out = _integer_grid(art, device)
             if corr is not None:
                 corrections.apply(out, corr[0], corr[1], corr[2]["bound"])
-            data = out.cpu().numpy().reshape(shape)
+            data = out.cpu().numpy().reshape(art.data_shape)
         else:
-            # decode in the arithmetic the net was fitted in (side info records it when it is not fp32)
-            phi = init_phi({**dict(cf.Module.phi), "precision": str(sideinfos.get("phi_precision", cf.Compress.get("precision", "fp32")))})
-            load_model(phi, module_path, "cpu")
-            phi.to(device)
-            yhat = phi.decode_grid(dims, lo, hi).cpu().reshape(shape)
-            data = invnormalize_data(yhat, sideinfos, cf.Normalize.name)
-        pp = cf.Decompress.postprocess
+            yhat = art.load_phi(device).decode_grid(art.dims, art.lo, art.hi).cpu().reshape(art.data_shape)
+            data = invnormalize_data(yhat, art.side, art.cf.Normalize.name)
+        pp = art.postprocess
         return preprocess(data, pp.denoise.level, pp.denoise.close, pp.clip)
 
     @staticmethod
     def _decode_integer(cf, module_path, sideinfos, device="cuda"):
         """the fused integer branch of decompress (uint8 / uint16 data under 'minmaxany_a_b'): the stored weights evaluated over the
         whole grid, as a device tensor [voxels, channels] in the source dtype, WITHOUT corrections.  cf: CompressFramework options."""
-        cf = copy.deepcopy(cf)
-        cf.Module.phi.features = sideinfos["phi_features"]
-        cf.Module.phi.name = sideinfos["phi_name"]
-        # decode in the arithmetic the net was fitted in (side info records it when it is not fp32)
-        phi = init_phi({**dict(cf.Module.phi), "precision": str(sideinfos.get("phi_precision", cf.Compress.get("precision", "fp32")))})
-        load_model(phi, module_path, "cpu")
-        phi.to(device)
-        lo, hi = _coords_range(cf.Compress.coords_mode)
-        kind = "u8" if sideinfos["dtype"] == "uint8" else "u16"
-        return phi.decode_grid(list(sideinfos["data_shape"])[:-1], lo, hi, out_kind=kind, scale=minmaxany_range(cf.Normalize.name),
-                               vrange=(sideinfos["min"], sideinfos["max"]))
+        return _integer_grid(open_artefact(cf, module_path, sideinfos), device)
 
     def sample_nf(self, coords):
         """main.py:266-268: the fitted network evaluated at `coords` without autograd"""
@@ -234,13 +211,9 @@ class NFGR:
         """main.py:299-320: decode every block of a stored DivideTask artefact (steps{k}/compressed/{module,sideinfos}/
         <block>/...) and paste the blocks back by the inclusive index ranges in their names.  `opt` defaults to this
         object's options (the reference re-reads the YAML given on the command line)."""
-        orig = load_yaml(orig_sideinfos_path)
-        data_shape = list(orig["data_shape"])
+        data_shape, blocks = divide_blocks(orig_sideinfos_path, module_save_dir, sideinfos_save_dir)
         opt = opt if opt is not None else _wrap(self.opt)
-        parts = []
-        for chunk_name in sorted(os.listdir(module_save_dir)):
-            dec = NFGR.decompress(opt, opj(module_save_dir, chunk_name, "module"), opj(sideinfos_save_dir, chunk_name, "sideinfos.yaml"), self.device)
-            parts.append({"data": dec, "name": chunk_name, **parse_chunk_name(chunk_name)})
+        parts = [{"data": NFGR.decompress(opt, b.module_path, b.side, self.device), "name": b.name, **b.ranges} for b in blocks]
         return merge_divided_data(parts, data_shape)
 
     # ---- region decode: a box of the volume without evaluating the rest (brief_siren_forward_box)
@@ -251,46 +224,31 @@ class NFGR:
         stride of the axes whose slice has none.  shape: evaluate the net on the linspace grid of that spatial shape instead of
         the fitted one (a resampled view); region and step then index that grid.  Normalisation, dtype and the pointwise
         Decompress.postprocess are decompress's; a denoise through a binary opening (not local to a voxel) raises."""
-        if isinstance(opt, str):
-            opt = config.load(opt)
-        if isinstance(sideinfos, str):
-            sideinfos = load_yaml(sideinfos)
-        cf = copy.deepcopy(opt.CompressFramework)
-        pp = cf.Decompress.postprocess
-        dtype = np.dtype(sideinfos["dtype"])
-        _region_postprocess_check(dtype, pp)
-        data_shape = list(sideinfos["data_shape"])
-        dims = data_shape[:-1]
-        if shape is not None and "error_bound" in sideinfos:
+        art = open_artefact(opt, module_path, sideinfos)
+        _region_postprocess_check(np.dtype(art.dtype), art.postprocess)
+        dims = art.dims
+        if shape is not None and "error_bound" in art.side:
             raise ValueError("a resampled view (shape) of an error-bounded artefact is refused: its corrections (error_bound %s) exist on the "
-                             "fitted grid %s only" % (sideinfos["error_bound"], dims))
-        corr = _load_corrections(cf, module_path, sideinfos)
+                             "fitted grid %s only" % (art.side["error_bound"], dims))
+        corr = art.corrections()
         if shape is not None:
             shape = [int(v) for v in shape]
             if len(shape) != len(dims) or any(v < 1 for v in shape):
                 raise ValueError("shape %s does not fit the %d spatial axes of the artefact" % (shape, len(dims)))
             dims = shape
         start, stop, stp = region_mod.normalize_region(dims, region, step)
-        cf.Module.phi.features = sideinfos["phi_features"]
-        cf.Module.phi.name = sideinfos["phi_name"]
-        phi = init_phi({**dict(cf.Module.phi), "precision": str(sideinfos.get("phi_precision", cf.Compress.get("precision", "fp32")))})
-        load_model(phi, module_path, "cpu")
-        phi.to(device)
-        lo, hi = _coords_range(cf.Compress.coords_mode)
-        rng = minmaxany_range(cf.Normalize.name)
-        if rng is not None and sideinfos["dtype"] in ("uint8", "uint16"):
-            kind = "u8" if sideinfos["dtype"] == "uint8" else "u16"
-            box = phi.decode_box(dims, start, stop, stp, lo, hi, out_kind=kind, scale=rng, vrange=(sideinfos["min"], sideinfos["max"]))
+        phi = art.load_phi(device)
+        if art.integer:
+            box = phi.decode_box(dims, start, stop, stp, art.lo, art.hi, out_kind=art.out_kind, scale=art.norm_range, vrange=art.vrange)
             if corr is not None:
                 # the block's corrections that fall on the box, as flat indices into it (the channel axis is whole)
-                cout = data_shape[-1]
-                bi, bq = corrections.select(corr[0], corr[1], dims + [cout], start + [0], stop + [cout], stp + [1])
+                bi, bq = corrections.select(corr[0], corr[1], art.data_shape, start + [0], stop + [art.cout], stp + [1])
                 corrections.apply(box, bi, bq, corr[2]["bound"])
             data = box.cpu().numpy()
         else:
-            yhat = phi.decode_box(dims, start, stop, stp, lo, hi).cpu()
-            data = invnormalize_data(yhat, sideinfos, cf.Normalize.name)
-        return preprocess(data, pp.denoise.level, False, pp.clip)
+            yhat = phi.decode_box(dims, start, stop, stp, art.lo, art.hi).cpu()
+            data = invnormalize_data(yhat, art.side, art.cf.Normalize.name)
+        return art.postprocess_local(data)
 
     def decompress_divide_region(self, orig_sideinfos_path, module_save_dir, sideinfos_save_dir, region, step=1, opt=None, shape=None):
         """decompress_divide(...)[region] evaluated on the region alone: only the blocks whose inclusive ranges meet it are decoded,
@@ -324,7 +282,7 @@ class NFGR:
         folds every ray of direction `direction` over the clip box `region`, 'slice' is one plane at any orientation.  Only the samples
         inside the clip box are evaluated; the volume is never decoded.  view.decompress_view has the arguments and the envelope."""
         from . import view
-        return view.decompress_view(opt, module_path, sideinfos, direction, **kwargs)
+        return view.decompress_view(view.open_single(opt, module_path, sideinfos), direction, **kwargs)
 
     @staticmethod
     def decompress_surface(opt, module_path, sideinfos, direction, level, **kwargs):
@@ -333,7 +291,7 @@ class NFGR:
         bisection (first, t, depth, position), and for an fp32 SIREN the unit normal and a Lambert-shaded image from the analytic
         Jacobian (normal, shade).  The volume is never decoded.  view.decompress_surface has the arguments and the envelope."""
         from . import view
-        return view.decompress_surface(opt, module_path, sideinfos, direction, level, **kwargs)
+        return view.decompress_surface(view.open_single(opt, module_path, sideinfos), direction, level, **kwargs)
 
     # ---- spatial-gradient decode: the analytic Jacobian of the stored net in grey levels per voxel (brief_pytorch_amd/gradient.py)
     @staticmethod
@@ -725,29 +683,27 @@ class NFGR:
         fused = tdt is not None and minmaxany_range(self.opt.Normalize.name) is not None and post_identity
         out_shape = ([z1 - z0] + list(shape[1:])) if three_d else list(shape)
         slab = torch.zeros(out_shape, dtype=tdt, device=self.device) if fused else np.zeros(out_shape, dtype=np.float32)
-        lo, hi = _coords_range(self.opt.Compress.coords_mode)
+        cdir = opj(step_dir, "compressed")
         for c in chunks:
             r = parse_chunk_name(c["name"])
             bz0, bz1 = (r["d"][0], r["d"][1] + 1) if three_d else (0, 1)
             za, zb = max(bz0, z0), min(bz1, z1)
             if za >= zb:
                 continue
-            mod = opj(step_dir, "compressed", "module", c["name"], "module")
-            side = load_yaml(opj(step_dir, "compressed", "sideinfos", c["name"], "sideinfos.yaml"))
+            mod, side_path = block_paths(opj(cdir, "module"), opj(cdir, "sideinfos"), c["name"])
+            side = load_yaml(side_path)
             y0, y1, x0, x1 = r["h"][0], r["h"][1] + 1, r["w"][0], r["w"][1] + 1
             if fused:
-                corr = _load_corrections(self.opt, mod, side)
-                cf = copy.deepcopy(self.opt)
-                cf.Module.phi.features = side["phi_features"]
-                cf.Module.phi.name = side.get("phi_name", cf.Module.phi.name)
-                phi = init_phi({**dict(cf.Module.phi), "precision": str(side.get("phi_precision", self.precision))})
-                load_model(phi, mod, "cpu")
-                phi.to(self.device)
-                dims = list(side["data_shape"])[:-1]
+                # this decoder alone reads a side info without `phi_precision` as this job's precision (bf16 under Compress.half; the others:
+                # Compress.precision) and one without `phi_name` as this job's net (the others: KeyError)
+                art = open_artefact(self.opt, mod, side, default_precision=self.precision, default_name=self.opt.Module.phi.name)
+                corr = art.corrections()
+                phi = art.load_phi(self.device)
+                dims = art.dims
                 plane = int(np.prod(dims[1:])) if three_d else int(np.prod(dims))
                 off, cnt = ((za - bz0) * plane, (zb - za) * plane) if three_d else (0, plane)
-                part = phi.decode_grid(dims, lo, hi, offset=off, count=cnt, out_kind="u8" if tdt == torch.uint8 else "u16",
-                                       scale=minmaxany_range(self.opt.Normalize.name), vrange=(side["min"], side["max"]))
+                part = phi.decode_grid(dims, art.lo, art.hi, offset=off, count=cnt, out_kind="u8" if tdt == torch.uint8 else "u16",
+                                       scale=art.norm_range, vrange=art.vrange)
                 if corr is not None:
                     # the block's corrections inside this z-range: a contiguous range of its flattened elements
                     e0 = off * part.shape[-1]
@@ -914,87 +870,26 @@ def error_bound_of(cf):
     return corrections.parse_bound(cf.Compress.get("error_bound", None))
 
 
-def check_error_bound(cf, dtype):
-    """the error-bounded mode acts on the integers of the fused decode epilogue: uint8 / uint16 data under a 'minmaxany_a_b'
-    normalisation, and nothing may change values behind it (Decompress.postprocess must be the identity).  Anything else is
-    refused by name: the bound could not be promised."""
-    dtype = np.dtype(dtype)
-    if dtype.name not in ("uint8", "uint16"):
-        raise ValueError("Compress.error_bound supports uint8 / uint16 data only: a bound in grey levels cannot be promised for %s data" % dtype.name)
-    if minmaxany_range(cf.Normalize.name) is None:
-        raise ValueError("Compress.error_bound supports the 'minmaxany_a_b' normalisations only (the fused integer decode): the bound "
-                         "cannot be promised under Normalize.name=%s" % cf.Normalize.name)
-    pp = cf.Decompress.postprocess
-    if not preprocess_is_identity(np.zeros(1, dtype), pp.denoise.level, pp.denoise.close, pp.clip):
-        raise ValueError("Compress.error_bound needs an identity Decompress.postprocess (denoise.level <= 0, a clip that covers the %s range): "
-                         "the bound cannot be promised behind postprocess denoise.level=%s clip=%s" % (dtype.name, pp.denoise.level, list(pp.clip)))
-
-
-def _load_corrections(cf, module_path, sideinfos):
-    """None for an artefact without `error_bound` in its side info; else (idx, q, header) of its corrections file.  A decoder never
-    hands back an unbounded volume silently: a missing or foreign file, or decode options the bound does not hold under, raise."""
-    if "error_bound" not in sideinfos:
-        return None
-    check_error_bound(cf, sideinfos["dtype"])
-    path = corrections.path_for(module_path)
-    if not os.path.isfile(path):
-        raise corrections.CorrectionsError("the side info promises error_bound=%s but %s is missing: refusing to decode an unbounded volume"
-                                           % (sideinfos["error_bound"], path))
-    idx, q, head = corrections.read(path)
-    n = int(np.prod(sideinfos["data_shape"]))
-    if head["bound"] != int(sideinfos["error_bound"]) or head["n"] != n or head["dtype"] != sideinfos["dtype"]:
-        raise corrections.CorrectionsError("%s (bound %d, %d %s elements) does not belong to this artefact (error_bound %s, %d %s elements)"
-                                           % (path, head["bound"], head["n"], head["dtype"], sideinfos["error_bound"], n, sideinfos["dtype"]))
-    return idx, q, head
-
-
-def _region_postprocess_check(dtype, pp):
-    """a region equals the slice of the whole decode only where Decompress.postprocess is local to a voxel: the clip and a plain
-    threshold are; a denoise through a binary opening (denoise.close) of a non-zero level is not.  (At level <= 0 the opening
-    only zeroes voxels the clip, whose floor is >= 0, sends to the same value, so a threshold gives the same result.)"""
-    if pp.denoise.level > 0 and pp.denoise.close is not False:
-        raise ValueError("Decompress.postprocess.denoise (level %s through a binary opening) is not local to a voxel: a region "
-                         "cannot equal the slice of the whole decode; decode the whole volume instead" % pp.denoise.level)
-    range_limit(np.zeros(1, dtype), pp.clip)      # the clip's own checks, before any decode
+def _integer_grid(art, device):
+    """the opened artefact's net over its whole grid through the fused integer epilogue: a device tensor [voxels, channels]"""
+    return art.load_phi(device).decode_grid(art.dims, art.lo, art.hi, out_kind=art.out_kind, scale=art.norm_range, vrange=art.vrange)
 
 
 def decompress_divide_region(opt, orig_sideinfos_path, module_save_dir, sideinfos_save_dir, region, step=1, device="cuda"):
     """the region of a stored DivideTask artefact (NFGR.decompress_divide_region); opt: the whole option tree"""
     if isinstance(opt, str):
         opt = config.load(opt)
-    orig = load_yaml(orig_sideinfos_path) if isinstance(orig_sideinfos_path, str) else orig_sideinfos_path
-    data_shape = list(orig["data_shape"])
-    dims, cout = data_shape[:-1], data_shape[-1]
-    start, stop, stp = region_mod.normalize_region(dims, region, step)
+    data_shape, blocks = divide_blocks(orig_sideinfos_path, module_save_dir, sideinfos_save_dir)
+    start, stop, stp = region_mod.normalize_region(data_shape[:-1], region, step)
     ext = region_mod.extents(start, stop, stp)
-    axes = "dhw" if len(dims) == 3 else "hw"
-    names = sorted(os.listdir(module_save_dir))
-    out = np.zeros(ext + [cout], dtype=np.float32)
-    dtype = None
-    for name in names:
-        side = load_yaml(opj(sideinfos_save_dir, name, "sideinfos.yaml"))
-        dtype = dtype or np.dtype(side["dtype"])        # merge_divided_data casts to the first block's dtype
-        _region_postprocess_check(np.dtype(side["dtype"]), opt.CompressFramework.Decompress.postprocess)
-        r = parse_chunk_name(name)
-        hit = region_mod.block_intersection(start, stp, ext, [r[a][0] for a in axes], [r[a][1] for a in axes])
-        if hit is None:
-            continue
-        o_lo, o_hi, l_start, l_stop = hit
-        dec = NFGR.decompress_region(opt, opj(module_save_dir, name, "module"), side,
-                                     tuple(slice(b, e) for b, e in zip(l_start, l_stop)), stp, device=device)
-        out[tuple(slice(b, e) for b, e in zip(o_lo, o_hi))] += dec
-    if dtype is None:
-        raise ValueError("no blocks under %s" % module_save_dir)
+    for b in blocks:        # every block's refusal before the first decode
+        _region_postprocess_check(np.dtype(b.side["dtype"]), opt.CompressFramework.Decompress.postprocess)
+    out = np.zeros(ext + [data_shape[-1]], dtype=np.float32)
+    for b, o_lo, o_hi, l_start, l_stop in meeting(blocks, start, stp, ext):
+        dec = NFGR.decompress_region(opt, b.module_path, b.side, tuple(slice(lo, hi) for lo, hi in zip(l_start, l_stop)), stp, device=device)
+        out[tuple(slice(lo, hi) for lo, hi in zip(o_lo, o_hi))] += dec
+    dtype = np.dtype(blocks[0].side["dtype"])        # merge_divided_data casts to the first block's dtype
     return out.clip(None, get_type_max(np.zeros(1, dtype))).astype(dtype)
-
-
-def _coords_range(mode):
-    if mode == "n11":
-        return -1.0, 1.0
-    if mode == "0p1":
-        return 0.0, 1.0
-    lo, hi = mode.split(",")
-    return float(lo), float(hi)
 
 
 class _Wrapped(config.Opt):

@@ -4,12 +4,9 @@ region semantics: a region equals the slice of the whole, results do not depend 
 call gives the same bits.  (DESIGN.md "Spatial-gradient decode".)
 
 voxel_scale, refusal and supported are host arithmetic; everything else needs a ROCm GPU (there is no CPU fallback)."""
-import copy
-import os
-
 import numpy as np
 
-from . import config
+from . import artefact, config
 from . import region as region_mod
 
 MAX_FEATURES = 1024
@@ -46,55 +43,36 @@ def supported(phi_name, precision, features):
     return refusal(phi_name, precision, features) is None
 
 
-def check_artefact(cf, sideinfos):
-    """what decompress_gradient supports, checked on option and side-info dicts before any decode; returns (a, b) of the normalisation"""
-    from .io import minmaxany_range
-    precision = str(sideinfos.get("phi_precision", cf.Compress.get("precision", "fp32")))
-    why = refusal(sideinfos["phi_name"], precision, sideinfos["phi_features"])
+def check_artefact(art):
+    """what decompress_gradient supports, checked on the opened artefact before any decode"""
+    why = refusal(art.phi_name, art.precision, art.phi_features)
     if why is not None:
         raise ValueError(why)
-    rng = minmaxany_range(cf.Normalize.name)
-    if rng is None:
-        raise ValueError("the spatial-gradient decode supports the 'minmaxany_a_b' normalisations only (their inverse is affine in the "
-                         "net's output), not Normalize.name=%s" % cf.Normalize.name)
-    return rng
+    artefact.check_envelope(art, need_minmaxany="the spatial-gradient decode supports the 'minmaxany_a_b' normalisations only (their inverse "
+                                                "is affine in the net's output), not Normalize.name=%s")
 
 
-def _block_gradient(cf, module_path, sideinfos, dims, start, stop, step, device, chunk=None):
+def _block_gradient(art, dims, start, stop, step, device, chunk=None):
     """the scaled Jacobian [*extent, cout, cin] (device, float32) of one stored net over the box start:stop:step of the grid `dims`"""
     import torch
-    from .framework import _coords_range
-    from .mip import _load_phi
-    rng = check_artefact(cf, sideinfos)
-    phi = _load_phi(cf, module_path, sideinfos, device)
-    lo, hi = _coords_range(cf.Compress.coords_mode)
-    jac, _ = phi.decode_gradient_box(dims, start, stop, step, lo, hi, chunk=chunk, want_value=False)
-    scale = voxel_scale(dims, lo, hi, rng, sideinfos["min"], sideinfos["max"])
+    phi = art.load_phi(device)
+    jac, _ = phi.decode_gradient_box(dims, start, stop, step, art.lo, art.hi, chunk=chunk, want_value=False)
+    scale = voxel_scale(dims, art.lo, art.hi, art.norm_range, art.vrange[0], art.vrange[1])
     return jac * torch.tensor(scale, dtype=torch.float32, device=jac.device)
-
-
-def _as_dicts(opt, sideinfos):
-    from .io import load_yaml
-    if isinstance(opt, str):
-        opt = config.load(opt)
-    if isinstance(sideinfos, str):
-        sideinfos = load_yaml(sideinfos)
-    return opt, sideinfos
 
 
 def decompress_gradient_device(opt, module_path, sideinfos, region=None, step=1, shape=None, device="cuda", chunk=None):
     """decompress_gradient's result as a device tensor (what the magnitude of decompress.py is taken of)"""
-    opt, sideinfos = _as_dicts(opt, sideinfos)
-    cf = copy.deepcopy(opt.CompressFramework)
-    check_artefact(cf, sideinfos)
-    dims = [int(v) for v in list(sideinfos["data_shape"])[:-1]]
+    art = artefact.open_artefact(opt, module_path, sideinfos)
+    check_artefact(art)
+    dims = art.dims
     if shape is not None:
         shape = [int(v) for v in shape]
         if len(shape) != len(dims) or any(v < 1 for v in shape):
             raise ValueError("shape %s does not fit the %d spatial axes of the artefact" % (shape, len(dims)))
         dims = shape
     start, stop, stp = region_mod.normalize_region(dims, region if region is not None else (slice(None),) * len(dims), step)
-    return _block_gradient(cf, module_path, sideinfos, dims, start, stop, stp, device, chunk)
+    return _block_gradient(art, dims, start, stop, stp, device, chunk)
 
 
 def decompress_gradient(opt, module_path, sideinfos, region=None, step=1, shape=None, device="cuda", chunk=None):
@@ -111,47 +89,27 @@ def decompress_gradient(opt, module_path, sideinfos, region=None, step=1, shape=
     return decompress_gradient_device(opt, module_path, sideinfos, region, step, shape, device, chunk).cpu().numpy()
 
 
-def _ranges_overlap(a, b, axes):
-    return all(a[k][0] <= b[k][1] and b[k][0] <= a[k][1] for k in axes)
-
-
 def decompress_divide_gradient_device(opt, orig_sideinfos, module_dir, sideinfos_dir, region=None, step=1, device="cuda", chunk=None):
     """decompress_divide_gradient's result as a device tensor"""
     import torch
-    from .io import load_yaml
-    from .misc import parse_chunk_name
-    opj = os.path.join
     if isinstance(opt, str):
         opt = config.load(opt)
-    orig = load_yaml(orig_sideinfos) if isinstance(orig_sideinfos, str) else orig_sideinfos
-    data_shape = [int(v) for v in orig["data_shape"]]
+    data_shape, blocks = artefact.divide_blocks(orig_sideinfos, module_dir, sideinfos_dir)
     dims, cout = data_shape[:-1], data_shape[-1]
-    axes = "dhw" if len(dims) == 3 else "hw"
     start, stop, stp = region_mod.normalize_region(dims, region if region is not None else (slice(None),) * len(dims), step)
     ext = region_mod.extents(start, stop, stp)
-    names = sorted(os.listdir(module_dir))
-    if not names:
-        raise ValueError("no blocks under %s" % module_dir)
     # every refusal before any decode
-    blocks = []
-    for name in names:
-        side = load_yaml(opj(sideinfos_dir, name, "sideinfos.yaml"))
-        check_artefact(opt.CompressFramework, side)
-        blocks.append((name, side, parse_chunk_name(name)))
-    for i, (na, _, ra) in enumerate(blocks):
-        for nb, _, rb in blocks[i + 1:]:
-            if _ranges_overlap(ra, rb, axes):
-                raise ValueError("the blocks %s and %s overlap: merge_divided_data adds overlapping blocks and clips the sum, which has "
-                                 "no single net's gradient; the spatial-gradient decode needs a partition without overlap" % (na, nb))
+    arts = {b.name: artefact.open_artefact(opt, b.module_path, b.side) for b in blocks}
+    for art in arts.values():
+        check_artefact(art)
+    pair = artefact.first_overlap(blocks, "dhw" if len(dims) == 3 else "hw")
+    if pair is not None:
+        raise ValueError("the blocks %s and %s overlap: merge_divided_data adds overlapping blocks and clips the sum, which has "
+                         "no single net's gradient; the spatial-gradient decode needs a partition without overlap" % (pair[0].name, pair[1].name))
     out = torch.zeros((*ext, cout, len(dims)), dtype=torch.float32, device=device)
-    for name, side, r in blocks:
-        hit = region_mod.block_intersection(start, stp, ext, [r[a][0] for a in axes], [r[a][1] for a in axes])
-        if hit is None:
-            continue
-        o_lo, o_hi, l_start, l_stop = hit
-        b_dims = [int(v) for v in list(side["data_shape"])[:-1]]
-        g = _block_gradient(copy.deepcopy(opt.CompressFramework), opj(module_dir, name, "module"), side, b_dims, l_start, l_stop, stp, device, chunk)
-        out[tuple(slice(b, e) for b, e in zip(o_lo, o_hi))] = g
+    for b, o_lo, o_hi, l_start, l_stop in artefact.meeting(blocks, start, stp, ext):
+        art = arts[b.name]
+        out[tuple(slice(lo, hi) for lo, hi in zip(o_lo, o_hi))] = _block_gradient(art, art.dims, l_start, l_stop, stp, device, chunk)
     return out
 
 

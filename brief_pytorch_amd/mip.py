@@ -4,12 +4,9 @@ an error-bounded artefact added back), each chunk is folded into three small ima
 forgotten.  (DESIGN.md "Projection decode".)
 
 plan_chunks is host arithmetic; everything else needs a ROCm GPU (there is no CPU fallback)."""
-import copy
-import os
-
 import numpy as np
 
-from . import _lib, config, corrections
+from . import _lib, artefact, config, corrections
 from . import region as region_mod
 
 DEFAULT_CHUNK = 1 << 24          # voxels decoded per step: 32 MiB of uint16, against 2 GiB for a whole 1024^3 volume
@@ -102,53 +99,35 @@ def decode_mips(phi, dims, start, stop, step, lo, hi, out_kind, scale, vrange, c
 
 
 # ---- artefacts ------------------------------------------------------------------------------------------------------------------
-def check_envelope(cf, sideinfos, shape=None):
-    """what the projection decode supports, checked on option and side-info dicts before any decode: 3-D uint8 / uint16 data under
-    a 'minmaxany_a_b' normalisation (the fused integer epilogue), a Decompress.postprocess that is local to a voxel, the fitted grid"""
-    from .framework import _region_postprocess_check
-    from .io import minmaxany_range
+ENVELOPE = dict(
+    need_3d="max-intensity projections are defined for 3-D data only (mip_ops needs ndim == 4): this artefact holds %d-D data of shape %s",
+    need_integer="the projection decode supports uint8 / uint16 data only (the fused integer decode); this artefact holds %s: "
+                 "decode it and take mip_ops",
+    need_minmaxany="the projection decode supports the 'minmaxany_a_b' normalisations only (the fused integer decode), not "
+                   "Normalize.name=%s: decode the volume and take mip_ops",
+    local_postprocess=True)
+
+
+def check_envelope(art, shape=None):
+    """what the projection decode supports, checked on the opened artefact before any decode: 3-D uint8 / uint16 data under a
+    'minmaxany_a_b' normalisation (the fused integer epilogue), a Decompress.postprocess that is local to a voxel, the fitted grid"""
     if shape is not None:
         raise ValueError(SHAPE_REFUSAL)
-    data_shape = list(sideinfos["data_shape"])
-    if len(data_shape) != 4:
-        raise ValueError("max-intensity projections are defined for 3-D data only (mip_ops needs ndim == 4): this artefact holds "
-                         "%d-D data of shape %s" % (len(data_shape) - 1, data_shape))
-    if sideinfos["dtype"] not in ("uint8", "uint16"):
-        raise ValueError("the projection decode supports uint8 / uint16 data only (the fused integer decode); this artefact holds %s: "
-                         "decode it and take mip_ops" % sideinfos["dtype"])
-    if minmaxany_range(cf.Normalize.name) is None:
-        raise ValueError("the projection decode supports the 'minmaxany_a_b' normalisations only (the fused integer decode), not "
-                         "Normalize.name=%s: decode the volume and take mip_ops" % cf.Normalize.name)
-    _region_postprocess_check(np.dtype(sideinfos["dtype"]), cf.Decompress.postprocess)
-
-
-def _postprocess(img, pp):
-    from .misc import preprocess
-    return preprocess(img, pp.denoise.level, False, pp.clip)
+    artefact.check_envelope(art, **ENVELOPE)
 
 
 def _load_phi(cf, module_path, sideinfos, device):
-    from .modelsave import load_model
-    from .networks import init_phi
-    cf.Module.phi.features = sideinfos["phi_features"]
-    cf.Module.phi.name = sideinfos["phi_name"]
-    phi = init_phi({**dict(cf.Module.phi), "precision": str(sideinfos.get("phi_precision", cf.Compress.get("precision", "fp32")))})
-    load_model(phi, module_path, "cpu")
-    phi.to(device)
-    return phi
+    """the stored net on `device` (artefact.Artefact.load_phi); the name the GPU tests load an artefact's net by.  No module of the
+    package uses it."""
+    return artefact.open_artefact(cf, module_path, sideinfos).load_phi(device)
 
 
-def _fold_artefact(cf, module_path, sideinfos, start, stop, step, device, chunk, into=None, origin=None):
-    """decode_mips of one stored net (a SingleTask artefact, or one block of a partition); cf: a private copy of CompressFramework"""
-    from .framework import _coords_range, _load_corrections
-    from .io import minmaxany_range
-    corr = _load_corrections(cf, module_path, sideinfos)         # raises when a promised bound cannot be honoured
-    phi = _load_phi(cf, module_path, sideinfos, device)
-    lo, hi = _coords_range(cf.Compress.coords_mode)
-    data_shape = list(sideinfos["data_shape"])
-    return decode_mips(phi, data_shape[:-1], start, stop, step, lo, hi, "u8" if sideinfos["dtype"] == "uint8" else "u16",
-                       minmaxany_range(cf.Normalize.name), (sideinfos["min"], sideinfos["max"]), corr=corr, data_shape=data_shape,
-                       chunk=chunk, into=into, origin=origin)
+def _fold_artefact(art, start, stop, step, device, chunk, into=None, origin=None):
+    """decode_mips of one stored net (a SingleTask artefact, or one block of a partition)"""
+    corr = art.corrections()         # raises when a promised bound cannot be honoured
+    phi = art.load_phi(device)
+    return decode_mips(phi, art.dims, start, stop, step, art.lo, art.hi, art.out_kind, art.norm_range, art.vrange, corr=corr,
+                       data_shape=art.data_shape, chunk=chunk, into=into, origin=origin)
 
 
 def decompress_mip(opt, module_path, sideinfos, region=None, step=1, device="cuda", shape=None, chunk=None):
@@ -158,21 +137,11 @@ def decompress_mip(opt, module_path, sideinfos, region=None, step=1, device="cud
     the clip are monotone non-decreasing maps, and a monotone map commutes with max, so the result is the same.  Supported: 3-D
     uint8 / uint16 data under 'minmaxany_a_b'; 2-D data, other dtypes or normalisations, a denoise through a binary opening and a
     resampled view (shape) are refused before any decode.  Error-bounded artefacts get their corrections per chunk."""
-    from .io import load_yaml
-    if isinstance(opt, str):
-        opt = config.load(opt)
-    if isinstance(sideinfos, str):
-        sideinfos = load_yaml(sideinfos)
-    cf = copy.deepcopy(opt.CompressFramework)
-    check_envelope(cf, sideinfos, shape)
-    dims = list(sideinfos["data_shape"])[:-1]
-    start, stop, stp = region_mod.normalize_region(dims, region if region is not None else (slice(None),) * 3, step)
-    images = _fold_artefact(cf, module_path, sideinfos, start, stop, stp, device, chunk)
-    return tuple(_postprocess(img.cpu().numpy(), cf.Decompress.postprocess) for img in images)
-
-
-def _ranges_overlap(a, b):
-    return all(a[k][0] <= b[k][1] and b[k][0] <= a[k][1] for k in "dhw")
+    art = artefact.open_artefact(opt, module_path, sideinfos)
+    check_envelope(art, shape)
+    start, stop, stp = region_mod.normalize_region(art.dims, region if region is not None else (slice(None),) * 3, step)
+    images = _fold_artefact(art, start, stop, stp, device, chunk)
+    return tuple(art.postprocess_local(img.cpu().numpy()) for img in images)
 
 
 def decompress_divide_mip(opt, orig_sideinfos, module_dir, sideinfos_dir, region=None, step=1, device="cuda", shape=None, chunk=None):
@@ -182,57 +151,37 @@ def decompress_divide_mip(opt, orig_sideinfos, module_dir, sideinfos_dir, region
     decompress_mip).  Blocks whose ranges overlap are refused: merge_divided_data ADDS there, and a max of sums is not a sum of
     maxima."""
     import torch
-    from .io import load_yaml
-    from .misc import parse_chunk_name
-    opj = os.path.join
     if isinstance(opt, str):
         opt = config.load(opt)
-    orig = load_yaml(orig_sideinfos) if isinstance(orig_sideinfos, str) else orig_sideinfos
     if shape is not None:
         raise ValueError(SHAPE_REFUSAL)
-    data_shape = list(orig["data_shape"])
+    data_shape, blocks = artefact.divide_blocks(orig_sideinfos, module_dir, sideinfos_dir, one_dtype="the projection decode")
     if len(data_shape) != 4:
-        raise ValueError("max-intensity projections are defined for 3-D data only (mip_ops needs ndim == 4): this artefact holds "
-                         "%d-D data of shape %s" % (len(data_shape) - 1, data_shape))
-    dims, cout = data_shape[:-1], data_shape[-1]
-    start, stop, stp = region_mod.normalize_region(dims, region if region is not None else (slice(None),) * 3, step)
+        raise ValueError(ENVELOPE["need_3d"] % (len(data_shape) - 1, data_shape))
+    start, stop, stp = region_mod.normalize_region(data_shape[:-1], region if region is not None else (slice(None),) * 3, step)
     ext = region_mod.extents(start, stop, stp)
-    names = sorted(os.listdir(module_dir))
-    if not names:
-        raise ValueError("no blocks under %s" % module_dir)
     # every refusal before any decode
-    blocks, dtype = [], None
-    for name in names:
-        side = load_yaml(opj(sideinfos_dir, name, "sideinfos.yaml"))
-        check_envelope(opt.CompressFramework, side)
-        dtype = dtype or side["dtype"]
-        if side["dtype"] != dtype:
-            raise ValueError("the projection decode needs one dtype for all blocks (%s is %s, %s is %s)" % (names[0], dtype, name, side["dtype"]))
-        blocks.append((name, side, parse_chunk_name(name)))
-    for i, (na, _, ra) in enumerate(blocks):
-        for nb, _, rb in blocks[i + 1:]:
-            if _ranges_overlap(ra, rb):
-                raise ValueError("the blocks %s and %s overlap: merge_divided_data adds overlapping blocks, and a max-intensity projection "
-                                 "of a sum is not the max of the blocks' projections; decode the region and take mip_ops" % (na, nb))
-    dt = torch.uint8 if dtype == "uint8" else torch.uint16
+    arts = {b.name: artefact.open_artefact(opt, b.module_path, b.side) for b in blocks}
+    for art in arts.values():
+        check_envelope(art)
+    pair = artefact.first_overlap(blocks, "dhw")
+    if pair is not None:
+        raise ValueError("the blocks %s and %s overlap: merge_divided_data adds overlapping blocks, and a max-intensity projection "
+                         "of a sum is not the max of the blocks' projections; decode the region and take mip_ops" % (pair[0].name, pair[1].name))
+    first, cout = arts[blocks[0].name], data_shape[-1]
+    dt = torch.uint8 if first.dtype == "uint8" else torch.uint16
     images = (torch.zeros((ext[1], ext[2], cout), dtype=dt, device=device), torch.zeros((ext[0], ext[2], cout), dtype=dt, device=device),
               torch.zeros((ext[0], ext[1], cout), dtype=dt, device=device))
     covered = (np.zeros((ext[1], ext[2]), bool), np.zeros((ext[0], ext[2]), bool), np.zeros((ext[0], ext[1]), bool))
-    for name, side, r in blocks:
-        hit = region_mod.block_intersection(start, stp, ext, [r[a][0] for a in "dhw"], [r[a][1] for a in "dhw"])
-        if hit is None:
-            continue
-        o_lo, o_hi, l_start, l_stop = hit
-        _fold_artefact(copy.deepcopy(opt.CompressFramework), opj(module_dir, name, "module"), side, l_start, l_stop, stp, device, chunk,
-                       into=images, origin=o_lo)
-        z, y, x = (slice(b, e) for b, e in zip(o_lo, o_hi))
+    for b, o_lo, o_hi, l_start, l_stop in artefact.meeting(blocks, start, stp, ext):
+        _fold_artefact(arts[b.name], l_start, l_stop, stp, device, chunk, into=images, origin=o_lo)
+        z, y, x = (slice(lo, hi) for lo, hi in zip(o_lo, o_hi))
         covered[0][y, x] = True
         covered[1][z, x] = True
         covered[2][z, y] = True
-    pp = opt.CompressFramework.Decompress.postprocess
     out = []
     for img, cov in zip(images, covered):
-        a = np.array(_postprocess(img.cpu().numpy(), pp), copy=True)
+        a = np.array(first.postprocess_local(img.cpu().numpy()), copy=True)
         a[~cov] = 0                                              # (the postprocess of a ray of uncovered zeros is never applied: they stay 0)
         out.append(a)
     return tuple(out)

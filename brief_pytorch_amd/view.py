@@ -9,14 +9,13 @@ crosses a level, refines that hit by bisection and shades it with the net's anal
 
 make_view is host arithmetic; brief_view_sample_host / brief_view_sample_t_host / brief_view_clip_host restate the device's geometry on the CPU; everything else
 needs a ROCm GPU (there is no CPU fallback)."""
-import copy
 import ctypes as C
 import math
 import os
 
 import numpy as np
 
-from . import _lib, config
+from . import _lib, artefact
 from . import region as region_mod
 
 MODES = ("max", "min", "mean", "slice")
@@ -381,42 +380,46 @@ def render_surface(phi, view, level, lo, hi, out_kind, scale, vrange, channel=0,
 
 
 # ---- artefacts ------------------------------------------------------------------------------------------------------------------
-def check_envelope(cf, sideinfos, mode, module_path=None):
-    """what the view decode supports, checked on option and side-info dicts before any decode: a SingleTask artefact without stored
-    corrections, 3-D uint8 / uint16 data with no axis of length 1 under a 'minmaxany_a_b' normalisation (the fused integer epilogue),
-    and a Decompress.postprocess that is local to a voxel (for a mean: the identity)"""
-    from .framework import _region_postprocess_check
-    from .io import minmaxany_range
+ENVELOPE = dict(
+    no_error_bound="a view of an error-bounded artefact is refused: its corrections (error_bound %s) exist on the points of the "
+                   "fitted grid %s only, and a view samples between them",
+    need_3d="a view is defined for 3-D data only: this artefact holds %d-D data of shape %s",
+    need_integer="the view decode supports uint8 / uint16 data only (the fused integer decode); this artefact holds %s",
+    need_minmaxany="the view decode supports the 'minmaxany_a_b' normalisations only (the fused integer decode), not Normalize.name=%s",
+    local_postprocess=True,
+    min_axis=(2, "a view needs every axis of the grid to be at least 2 voxels long (got %s): an axis of length 1 has no coordinate "
+                 "range to sample"))
+
+
+def open_single(opt, module_path, sideinfos):
+    """artefact.open_artefact for the view decodes, which exist for SingleTask artefacts only: the side info of a whole DivideTask job
+    (it describes no net, so it cannot be opened) and blocks beside the module directory are refused by name"""
+    from .io import load_yaml
+    if isinstance(sideinfos, str):
+        sideinfos = load_yaml(sideinfos)
+    if "phi_features" not in sideinfos or os.path.isdir(os.path.join(os.path.dirname(str(module_path)), "sideinfos")):
+        raise ValueError(DIVIDE_REFUSAL)
+    return artefact.open_artefact(opt, module_path, sideinfos)
+
+
+def check_envelope(art, mode):
+    """what the view decode supports, checked on the opened artefact before any decode: a SingleTask artefact (open_single) without
+    stored corrections, 3-D uint8 / uint16 data with no axis of length 1 under a 'minmaxany_a_b' normalisation (the fused integer
+    epilogue), and a Decompress.postprocess that is local to a voxel (for a mean: the identity)"""
     from .misc import preprocess_is_identity
     if mode not in MODES:
         raise ValueError("view mode %r is not one of %s" % (mode, " | ".join(MODES)))
-    if "phi_features" not in sideinfos or (module_path is not None and os.path.isdir(os.path.join(os.path.dirname(str(module_path)), "sideinfos"))):
-        raise ValueError(DIVIDE_REFUSAL)
-    data_shape = list(sideinfos["data_shape"])
-    if "error_bound" in sideinfos:
-        raise ValueError("a view of an error-bounded artefact is refused: its corrections (error_bound %s) exist on the points of the "
-                         "fitted grid %s only, and a view samples between them" % (sideinfos["error_bound"], data_shape[:-1]))
-    if len(data_shape) != 4:
-        raise ValueError("a view is defined for 3-D data only: this artefact holds %d-D data of shape %s" % (len(data_shape) - 1, data_shape))
-    if sideinfos["dtype"] not in ("uint8", "uint16"):
-        raise ValueError("the view decode supports uint8 / uint16 data only (the fused integer decode); this artefact holds %s"
-                         % sideinfos["dtype"])
-    if minmaxany_range(cf.Normalize.name) is None:
-        raise ValueError("the view decode supports the 'minmaxany_a_b' normalisations only (the fused integer decode), not "
-                         "Normalize.name=%s" % cf.Normalize.name)
-    pp = cf.Decompress.postprocess
-    _region_postprocess_check(np.dtype(sideinfos["dtype"]), pp)
-    if any(int(n) < 2 for n in data_shape[:-1]):
-        raise ValueError("a view needs every axis of the grid to be at least 2 voxels long (got %s): an axis of length 1 has no coordinate "
-                         "range to sample" % (data_shape[:-1],))
-    if mode == "mean" and not preprocess_is_identity(np.zeros(1, np.dtype(sideinfos["dtype"])), pp.denoise.level, pp.denoise.close, pp.clip):
+    artefact.check_envelope(art, **ENVELOPE)
+    pp = art.postprocess
+    if mode == "mean" and not preprocess_is_identity(np.zeros(1, np.dtype(art.dtype)), pp.denoise.level, pp.denoise.close, pp.clip):
         raise ValueError("a mean view with a Decompress.postprocess that changes values is refused: a threshold or a clip does not "
                          "commute with a mean (denoise.level %s, clip %s); use an identity postprocess" % (pp.denoise.level, list(pp.clip)))
 
 
-def decompress_view(opt, module_path, sideinfos, direction, up=None, mode="max", region=None, centre=None, spacing=1.0, depth_spacing=1.0,
+def decompress_view(art, direction, up=None, mode="max", region=None, centre=None, spacing=1.0, depth_spacing=1.0,
                     size=None, depth=None, offset=None, voxel_size=(1, 1, 1), device="cuda", chunk=None, return_hits=False):
-    """an orthographic view of a stored SingleTask artefact as a numpy image [rows, cols, channels], without decoding the volume.
+    """an orthographic view of a stored SingleTask artefact (art: open_single's) as a numpy image [rows, cols, channels], without
+    decoding the volume.
     mode 'max' | 'min' (source dtype) or 'mean' (float32) folds every ray over the clip box `region` (None: the whole grid);
     'slice' (source dtype) is the one plane at `offset` along `direction` from `centre` (default 0: through the centre).  The
     geometry arguments are make_view's.  Decompress.postprocess is applied to the IMAGE for max, min and slice: on unsigned data the
@@ -425,38 +428,26 @@ def decompress_view(opt, module_path, sideinfos, direction, up=None, mode="max",
     postprocess other than the identity is refused.  Refused by name before any decode: DivideTask and error-bounded artefacts, 2-D
     data, dtypes other than uint8 / uint16, normalisations other than 'minmaxany_a_b', a denoise through a binary opening, an axis
     of length 1.  return_hits: (image, hits [rows, cols] int32, stats) instead of the image."""
-    from .io import load_yaml, minmaxany_range
-    from .framework import _coords_range
-    from .mip import _load_phi, _postprocess
-    if isinstance(opt, str):
-        opt = config.load(opt)
-    if isinstance(sideinfos, str):
-        sideinfos = load_yaml(sideinfos)
-    cf = copy.deepcopy(opt.CompressFramework)
-    check_envelope(cf, sideinfos, mode, module_path)
+    check_envelope(art, mode)
     if mode == "slice":
         if depth is not None:
             raise ValueError("mode 'slice' takes the plane's `offset`, not a `depth` range")
         depth = 0.0 if offset is None else float(offset)
     elif offset is not None:
         raise ValueError("`offset` names the plane of mode 'slice'; mode %r takes a `depth` range" % mode)
-    dims = list(sideinfos["data_shape"])[:-1]
-    view = make_view(dims, direction, up, centre, spacing, depth_spacing, size, depth, voxel_size, region)
-    phi = _load_phi(cf, module_path, sideinfos, device)
-    lo, hi = _coords_range(cf.Compress.coords_mode)
-    image, hits, stats = render(phi, view, mode, lo, hi, "u8" if sideinfos["dtype"] == "uint8" else "u16", minmaxany_range(cf.Normalize.name),
-                                (sideinfos["min"], sideinfos["max"]), chunk=chunk)
+    view = make_view(art.dims, direction, up, centre, spacing, depth_spacing, size, depth, voxel_size, region)
+    image, hits, stats = render(art.load_phi(device), view, mode, art.lo, art.hi, art.out_kind, art.norm_range, art.vrange, chunk=chunk)
     img = image.cpu().numpy()
     if mode != "mean":
-        img = np.array(_postprocess(img, cf.Decompress.postprocess), copy=True)
+        img = np.array(art.postprocess_local(img), copy=True)
         img[hits.cpu().numpy() == 0] = 0                            # (a ray without a sample stays 0 whatever the clip's floor is)
     return (img, hits.cpu().numpy(), stats) if return_hits else img
 
 
-def decompress_surface(opt, module_path, sideinfos, direction, level, up=None, region=None, centre=None, spacing=1.0, depth_spacing=1.0,
+def decompress_surface(art, direction, level, up=None, region=None, centre=None, spacing=1.0, depth_spacing=1.0,
                        size=None, depth=None, voxel_size=(1, 1, 1), channel=0, side="above", refine=8, shading=True, light=None, device="cuda",
                        chunk=None):
-    """the isosurface view of a stored SingleTask artefact, without decoding the volume: a dict of numpy arrays, render_surface's
+    """the isosurface view of a stored SingleTask artefact (art: open_single's), without decoding the volume: a dict of numpy arrays, render_surface's
     first, t_lo, t_hi, t, position, normal, shade, hits and stats, plus depth = t * depth_spacing (float32, physical units along the
     ray from the view's first sample plane; NaN without a hit).  The geometry arguments are make_view's; `region` is the clip box.
 
@@ -469,30 +460,16 @@ def decompress_surface(opt, module_path, sideinfos, direction, level, up=None, r
     0 .. 16, and shading behind a net without the Jacobian kernel (anything but an fp32 SIREN of at most 1024 features; ask for
     shading=False to get first, depth and position)."""
     from . import gradient
-    from .io import load_yaml, minmaxany_range
-    from .framework import _coords_range
-    from .mip import _load_phi
-    if isinstance(opt, str):
-        opt = config.load(opt)
-    if isinstance(sideinfos, str):
-        sideinfos = load_yaml(sideinfos)
-    cf = copy.deepcopy(opt.CompressFramework)
-    check_envelope(cf, sideinfos, "max", module_path)
-    data_shape = list(sideinfos["data_shape"])
-    check_surface(level, channel, side, refine, data_shape[-1], sideinfos["dtype"])
+    check_envelope(art, "max")
+    check_surface(level, channel, side, refine, art.cout, art.dtype)
     if shading:
-        why = gradient.refusal(sideinfos["phi_name"], str(sideinfos.get("phi_precision", cf.Compress.get("precision", "fp32"))),
-                               sideinfos["phi_features"])
+        why = gradient.refusal(art.phi_name, art.precision, art.phi_features)
         if why is not None:
             raise ValueError("normals and shading need the analytic Jacobian: %s; ask for shading=False" % why)
-    dims = data_shape[:-1]
-    view = make_view(dims, direction, up, centre, spacing, depth_spacing, size, depth, voxel_size, region)
+    view = make_view(art.dims, direction, up, centre, spacing, depth_spacing, size, depth, voxel_size, region)
     physical = frame(direction, up)[2] if light is None else _unit3(light, "light")
-    rng = minmaxany_range(cf.Normalize.name)
-    lo, hi = _coords_range(cf.Compress.coords_mode)
-    gscale = gradient.voxel_scale(dims, lo, hi, rng, sideinfos["min"], sideinfos["max"]) / _vec3(voxel_size, "voxel_size")
-    phi = _load_phi(cf, module_path, sideinfos, device)
-    out = render_surface(phi, view, level, lo, hi, "u8" if sideinfos["dtype"] == "uint8" else "u16", rng, (sideinfos["min"], sideinfos["max"]),
+    gscale = gradient.voxel_scale(art.dims, art.lo, art.hi, art.norm_range, art.vrange[0], art.vrange[1]) / _vec3(voxel_size, "voxel_size")
+    out = render_surface(art.load_phi(device), view, level, art.lo, art.hi, art.out_kind, art.norm_range, art.vrange,
                          channel=channel, side=side, refine=refine, shading=shading, light=physical, gscale=gscale, chunk=chunk)
     res = {k: (x.cpu().numpy() if hasattr(x, "cpu") else x) for k, x in out.items()}
     res["depth"] = res["t"] * np.float32(depth_spacing)

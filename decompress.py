@@ -50,6 +50,12 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 
+def _paths(c):
+    """(module, sideinfos.yaml, sideinfos) under the artefact directory `c`.  SingleTask: the net and its side info, no `sideinfos`
+    directory.  DivideTask: the job's side info is sideinfos.yaml, the blocks are listed under module/ and sideinfos/"""
+    return os.path.join(c, "module"), os.path.join(c, "sideinfos.yaml"), os.path.join(c, "sideinfos")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="decode a region of a BRIEF artefact (MI355X fused path)")
     ap.add_argument("-p", required=True, help="the run's yaml file")
@@ -93,7 +99,7 @@ def main(argv=None):
         if os.path.splitext(args.o)[1].lower() != ".npy":
             raise SystemExit("--gradient writes float32 arrays as .npy only (got %s): gradient output in image formats is not supported"
                              % (os.path.splitext(args.o)[1] or "no extension"))
-        if args.shape and os.path.isdir(os.path.join(args.c, "sideinfos")):
+        if args.shape and os.path.isdir(_paths(args.c)[2]):
             raise SystemExit("--gradient --shape: resampling is not defined for a DivideTask artefact (every block has its own linspace grid)")
     if args.mip and args.shape:
         from brief_pytorch_amd.mip import SHAPE_REFUSAL
@@ -108,7 +114,8 @@ def main(argv=None):
     opt = config.load(args.p)
     region = parse_region(args.region)
     shape = parse_shape(args.shape) if args.shape else None
-    divide = os.path.isdir(os.path.join(args.c, "sideinfos"))
+    module, side_path, blocks_dir = _paths(args.c)
+    divide = os.path.isdir(blocks_dir)
     if args.view is not None:
         return _view(args, opt, region, divide)
     if args.mip:
@@ -119,11 +126,9 @@ def main(argv=None):
     if divide:
         if shape is not None:
             raise SystemExit("--shape: resampling is not defined for a DivideTask artefact (every block has its own linspace grid)")
-        data = decompress_divide_region(opt, os.path.join(args.c, "sideinfos.yaml"), os.path.join(args.c, "module"),
-                                        os.path.join(args.c, "sideinfos"), region, args.step)
+        data = decompress_divide_region(opt, side_path, module, blocks_dir, region, args.step)
     else:
-        data = NFGR.decompress_region(opt, os.path.join(args.c, "module"), os.path.join(args.c, "sideinfos.yaml"), region, args.step,
-                                      shape=shape)
+        data = NFGR.decompress_region(opt, module, side_path, region, args.step, shape=shape)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     save_img(args.o, data)
@@ -136,13 +141,13 @@ def _mip(args, opt, region, divide):
     import torch
     from brief_pytorch_amd.framework import NFGR, decompress_divide_mip
     from brief_pytorch_amd.misc import save_mips
+    module, side_path, blocks_dir = _paths(args.c)
     t0 = time.perf_counter()
     try:
         if divide:
-            mips = decompress_divide_mip(opt, os.path.join(args.c, "sideinfos.yaml"), os.path.join(args.c, "module"),
-                                         os.path.join(args.c, "sideinfos"), region, args.step)
+            mips = decompress_divide_mip(opt, side_path, module, blocks_dir, region, args.step)
         else:
-            mips = NFGR.decompress_mip(opt, os.path.join(args.c, "module"), os.path.join(args.c, "sideinfos.yaml"), region, args.step)
+            mips = NFGR.decompress_mip(opt, module, side_path, region, args.step)
     except ValueError as e:                                       # a refusal (2-D data, dtype, normalisation, postprocess, region)
         raise SystemExit("--mip: %s" % e)
     torch.cuda.synchronize()
@@ -209,7 +214,7 @@ def _view_refusals(args):
         _floats(args.voxel_size, 3, "--voxel-size")
     if args.view_size is not None:
         _floats(args.view_size, 2, "--view-size")
-    if os.path.isdir(os.path.join(args.c, "sideinfos")):
+    if os.path.isdir(_paths(args.c)[2]):
         raise SystemExit("--view: " + DIVIDE_REFUSAL)
 
 
@@ -220,10 +225,11 @@ def _view(args, opt, region, divide):
     from brief_pytorch_amd.tool import save_img
     if args.view_surface is not None:
         return _surface(args, opt, region)
+    module, side_path, _ = _paths(args.c)
     t0 = time.perf_counter()
     try:
         img, hits, stats = NFGR.decompress_view(
-            opt, os.path.join(args.c, "module"), os.path.join(args.c, "sideinfos.yaml"), _floats(args.view, 3, "--view"),
+            opt, module, side_path, _floats(args.view, 3, "--view"),
             up=_floats(args.view_up, 3, "--view-up") if args.view_up is not None else None, mode=args.view_mode, region=region,
             spacing=args.view_spacing, depth_spacing=args.view_depth_spacing,
             size=[int(x) for x in _floats(args.view_size, 2, "--view-size")] if args.view_size is not None else None,
@@ -245,21 +251,18 @@ def _view(args, opt, region, divide):
 def _surface(args, opt, region):
     import numpy as np
     import torch
-    from brief_pytorch_amd import gradient
-    from brief_pytorch_amd.framework import NFGR
-    from brief_pytorch_amd.io import load_yaml
+    from brief_pytorch_amd import gradient, view
     from brief_pytorch_amd.tool import save_img
-    side_path = os.path.join(args.c, "sideinfos.yaml")
+    module, side_path, _ = _paths(args.c)
     npy = os.path.splitext(args.o)[1].lower() == ".npy"
     t0 = time.perf_counter()
     try:
-        side = load_yaml(side_path)
-        precision = str(side.get("phi_precision", opt.CompressFramework.Compress.get("precision", "fp32")))
-        why = gradient.refusal(side.get("phi_name"), precision, side.get("phi_features", 0)) if "phi_features" in side else None
+        art = view.open_single(opt, module, side_path)
+        why = gradient.refusal(art.phi_name, art.precision, art.phi_features)
         if why is not None and not npy:
             raise ValueError("a shaded image needs the analytic Jacobian: %s; write the depth with -o <file>.npy" % why)
-        res = NFGR.decompress_surface(
-            opt, os.path.join(args.c, "module"), side, _floats(args.view, 3, "--view"), args.view_surface,
+        res = view.decompress_surface(
+            art, _floats(args.view, 3, "--view"), args.view_surface,
             up=_floats(args.view_up, 3, "--view-up") if args.view_up is not None else None, region=region,
             spacing=args.view_spacing, depth_spacing=args.view_depth_spacing,
             size=[int(x) for x in _floats(args.view_size, 2, "--view-size")] if args.view_size is not None else None,
@@ -291,14 +294,13 @@ def _gradient(args, opt, region, shape, divide):
     import numpy as np
     import torch
     from brief_pytorch_amd import gradient
+    module, side_path, blocks_dir = _paths(args.c)
     t0 = time.perf_counter()
     try:
         if divide:
-            g = gradient.decompress_divide_gradient_device(opt, os.path.join(args.c, "sideinfos.yaml"), os.path.join(args.c, "module"),
-                                                           os.path.join(args.c, "sideinfos"), region, args.step)
+            g = gradient.decompress_divide_gradient_device(opt, side_path, module, blocks_dir, region, args.step)
         else:
-            g = gradient.decompress_gradient_device(opt, os.path.join(args.c, "module"), os.path.join(args.c, "sideinfos.yaml"), region, args.step,
-                                                    shape=shape)
+            g = gradient.decompress_gradient_device(opt, module, side_path, region, args.step, shape=shape)
     except ValueError as e:                                       # a refusal (net class, precision, width, normalisation, overlap, region)
         raise SystemExit("--gradient: %s" % e)
     if args.gradient == "magnitude":
