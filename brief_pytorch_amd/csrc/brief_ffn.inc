@@ -68,36 +68,10 @@ struct FfnArgs {
     float scale_min, den, span, vmin;
 };
 
-// box-linear index b -> coordinates (the arithmetic of box_coords, on the box of FfnArgs): bit-identical to the whole-grid decode
-__device__ __forceinline__ void ffn_box_coords(const GridArgs &g, const BoxArgs &bx, int cin, int64_t b, float &x0, float &x1, float &x2)
-{
-    uint32_t i0, i1, i2 = 0u;
-    if (cin == 3) {
-        const uint32_t e2 = (uint32_t)bx.extent[2], e1 = (uint32_t)bx.extent[1];
-        if (bx.fast) {
-            const uint32_t bu = (uint32_t)b;
-            const uint32_t t2 = fast_div(bu, bx.magic[2], e2);
-            const uint32_t t1 = fast_div(t2, bx.magic[1], e1);
-            i0 = t1; i1 = t2 - t1 * e1; i2 = bu - t2 * e2;
-        } else {
-            const int64_t t2 = b / (int64_t)e2, t1 = t2 / (int64_t)e1;
-            i0 = (uint32_t)t1; i1 = (uint32_t)(t2 - t1 * e1); i2 = (uint32_t)(b - t2 * e2);
-        }
-    } else {
-        const uint32_t e1 = (uint32_t)bx.extent[1];
-        if (bx.fast) {
-            const uint32_t bu = (uint32_t)b;
-            const uint32_t t1 = fast_div(bu, bx.magic[1], e1);
-            i0 = t1; i1 = bu - t1 * e1;
-        } else {
-            const int64_t t1 = b / (int64_t)e1;
-            i0 = (uint32_t)t1; i1 = (uint32_t)(b - t1 * e1);
-        }
-    }
-    x0 = lin_coord32(g, 0, (uint32_t)bx.start[0] + (uint32_t)bx.step[0] * i0);
-    x1 = lin_coord32(g, 1, (uint32_t)bx.start[1] + (uint32_t)bx.step[1] * i1);
-    if (cin == 3) x2 = lin_coord32(g, 2, (uint32_t)bx.start[2] + (uint32_t)bx.step[2] * i2);
-}
+// the tile helpers ffn_box_coords, ffn_chain, ffn_bias, ffn_write_image, ffn_stash and ffn_frag: the one text of brief_tile.inc, compiled
+// here under the ffn_ prefix (every family includes it under its own; the note at its top says why they are not one set of functions)
+#define TILE_(name) ffn_##name
+#include "brief_tile.inc"
 
 // the embedding of one (coordinate, frequency row) pair: t = sum_c x_c B[e][c] as an fma chain in c order, in revolutions
 __device__ __forceinline__ void ffn_embed(float x0, float x1, float x2, float4 b, int cin, float &s, float &c)
@@ -108,75 +82,6 @@ __device__ __forceinline__ void ffn_embed(float x0, float x1, float x2, float4 b
     const float f = __builtin_amdgcn_fractf(t);
     s = BRIEF_SIN_REV(f);
     c = BRIEF_COS_REV(f);
-}
-
-// acc[t] += A(mt = wv + 4 t, steps [0, ksteps)) * image, for the tiles mt < mts; A block (mt, step) at A + ((mt * KS + step) * 64 + lane) * 4
-template <int MTW>
-__device__ __forceinline__ void ffn_chain(f32x16 (&acc)[MTW], const float *__restrict__ A, int KS, int ksteps, int mts,
-                                          const float4 *Xs, int wv, int lane)
-{
-    float4 an[MTW];
-#pragma unroll
-    for (int t = 0; t < MTW; ++t)
-        if (wv + 4 * t < mts) an[t] = *reinterpret_cast<const float4 *>(A + ((int64_t)(wv + 4 * t) * KS * 64 + lane) * 4);
-    for (int it = 0; it < ksteps; ++it) {
-        float4 ac[MTW];
-#pragma unroll
-        for (int t = 0; t < MTW; ++t) ac[t] = an[t];
-        if (it + 1 < ksteps) {
-#pragma unroll
-            for (int t = 0; t < MTW; ++t)
-                if (wv + 4 * t < mts) an[t] = *reinterpret_cast<const float4 *>(A + (((int64_t)(wv + 4 * t) * KS + it + 1) * 64 + lane) * 4);
-        }
-        const float4 b = Xs[it * 64 + lane];
-#pragma unroll
-        for (int t = 0; t < MTW; ++t) {
-            if (wv + 4 * t < mts) {
-                acc[t] = MFMA(ac[t].x, b.x, acc[t]);
-                acc[t] = MFMA(ac[t].y, b.y, acc[t]);
-                acc[t] = MFMA(ac[t].z, b.z, acc[t]);
-                acc[t] = MFMA(ac[t].w, b.w, acc[t]);
-            }
-        }
-    }
-}
-
-template <int MTW>
-__device__ __forceinline__ void ffn_bias(f32x16 (&acc)[MTW], const float *__restrict__ b, int nt, int wv, int hi)
-{
-#pragma unroll
-    for (int t = 0; t < MTW; ++t) {
-        const int mt = wv + 4 * t;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = mt < nt ? b[32 * mt + ROWMAP(r, hi)] : 0.f;
-    }
-}
-
-template <int MTW>
-__device__ __forceinline__ void ffn_write_image(float4 *Xs, const f32x16 (&h)[MTW], int nt, int wv, int lane)
-{
-#pragma unroll
-    for (int t = 0; t < MTW; ++t) {
-        const int mt = wv + 4 * t;
-        if (mt < nt) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) Xs[(mt * 4 + q) * 64 + lane] = make_float4(h[t][4 * q], h[t][4 * q + 1], h[t][4 * q + 2], h[t][4 * q + 3]);
-        }
-    }
-}
-
-// plane[row][col0 + s] for every accumulator element this lane holds
-template <int MTW>
-__device__ __forceinline__ void ffn_stash(float *__restrict__ plane, int64_t npad, int64_t col0, const f32x16 (&h)[MTW], int nt, int wv, int hi, int s)
-{
-#pragma unroll
-    for (int t = 0; t < MTW; ++t) {
-        const int mt = wv + 4 * t;
-        if (mt < nt) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) plane[(int64_t)(32 * mt + ROWMAP(r, hi)) * npad + col0 + s] = h[t][r];
-        }
-    }
 }
 
 // One 32-sample tile per workgroup iteration (persistent grid over the tiles), 4 waves; wave wv owns feature tiles wv, wv + 4, ...
@@ -482,17 +387,9 @@ __global__ void k_ffn_repack(const brief_ffn_desc d, const float *__restrict__ p
     if (e >= lay.total) return;
     const int F = d.features, E = d.embsize, cin = d.cin, cout = d.cout, FP = lay.FP;
     float v = 0.f;
-    // fragment element q of a block sequence with KS steps per row tile: (row, k)
-    auto frag = [](int64_t q, int KS, int &row, int &k) {
-        const int j = (int)(q & 3), lanei = (int)((q >> 2) & 63);
-        const int64_t blk = q >> 8;
-        const int step = (int)(blk % KS), mt = (int)(blk / KS);
-        row = 32 * mt + (lanei & 31);
-        k = 8 * step + 4 * (lanei >> 5) + j;
-    };
     int row, k;
     if (e < lay.b0) {
-        frag(e - lay.w0f, lay.K0 / 8, row, k);
+        ffn_frag(e - lay.w0f, lay.K0 / 8, row, k);
         const int col = k < lay.EP ? (k < E ? k : -1) : (k - lay.EP < E ? E + (k - lay.EP) : -1);
         if (row < F && col >= 0) v = params[ffn_canon_w0(d) + (int64_t)row * 2 * E + col];
     } else if (e < lay.hid) {
@@ -504,17 +401,17 @@ __global__ void k_ffn_repack(const brief_ffn_desc d, const float *__restrict__ p
         const float *W = params + ffn_canon_hidden(d, l);
         if (r < 2 * (int64_t)FP * FP) {
             const bool bwd = r >= (int64_t)FP * FP;
-            frag(bwd ? r - (int64_t)FP * FP : r, FP / 8, row, k);
+            ffn_frag(bwd ? r - (int64_t)FP * FP : r, FP / 8, row, k);
             if (row < F && k < F) v = bwd ? W[(int64_t)k * F + row] : W[(int64_t)row * F + k];
         } else {
             const int f = (int)(r - 2 * (int64_t)FP * FP);
             if (f < F) v = W[(int64_t)F * F + f];
         }
     } else if (e < lay.whb) {
-        frag(e - lay.whf, FP / 8, row, k);
+        ffn_frag(e - lay.whf, FP / 8, row, k);
         if (row < cout && k < F) v = params[ffn_canon_head(d) + (int64_t)row * F + k];
     } else if (e < lay.bh) {
-        frag(e - lay.whb, 4, row, k);
+        ffn_frag(e - lay.whb, 4, row, k);
         if (row < F && k < cout) v = params[ffn_canon_head(d) + (int64_t)k * F + row];
     } else if (e < lay.bv) {
         const int c = (int)(e - lay.bh);

@@ -20,7 +20,8 @@
 // (brief_device.inc shared definitions, brief_fused.inc k_fused, brief_lean.inc k_lean, brief_small.inc k_small, brief_wgrad.inc k_wgrad,
 //  brief_x3.inc split precision, brief_reduce.inc optimizer + k_reduce, brief_bf16.inc the bf16 path, brief_aux.inc repack / metrics / deblocking).
 // The families with kernels of their own (brief_ffn.inc, brief_nerf.inc, brief_mfn.inc, brief_taper.inc) share ONE host driver and keep their
-// C-ABI entries in brief_family_host.inc, included at the end of this file.
+// C-ABI entries in brief_family_host.inc, included at the end of this file.  Their tile helpers, and brief_jac.inc's, are the one text of
+// brief_tile.inc, which each of those files includes under its own name prefix (not listed below: brief_hip.hip does not include it).
 //
 //   k_fused<NT,TRAIN>  coords -> layer0 -> hidden layers -> head -> loss -> dgrad chain.
 //                      TRAIN stores Z_l (phases w z reduced to revolutions) and D_l (deltas) as [feature][sample]

@@ -1,7 +1,9 @@
 // brief_jac.inc — spatial-gradient decode of an fp32 SIREN: k_jac_fwd<MTW, BOX>, k_jac_repack (part of the single translation unit
 // brief_hip.hip, included behind brief_quant.inc so that its kernels are named last; the host entries are brief_jac_host.inc).
-// Only new kernels: no kernel, device function or argument struct of another file is changed or shared; the tile helpers are the ones of
-// brief_taper.inc restated under jac names (see the note in brief_nerf.inc: sharing them changes the code of the existing kernels).
+// Only new kernels: no kernel, device function or argument struct of another file is changed or shared.  The tile helpers jac_box_coords,
+// jac_chain and jac_write_image are the one text of brief_tile.inc compiled under the jac_ prefix (TILE_CHAIN_PACKED form; not functions
+// shared with the families: that changes the code of 88 of the 330 kernels, see the note in brief_nerf.inc).  jac_bias (one parameter
+// more) and the frag lambda of k_jac_repack (it captures ks) are this file's own; the included jac_bias, jac_stash and jac_frag are unused.
 //
 // Forward mode: the value and its cin tangents travel through the layers together,
 //   z_0 = W_0 x + b_0,            dz_0/dx_a = W_0[:, a]
@@ -56,72 +58,14 @@ struct JacArgs {
     float *jac;               // [n][cout][cin]
 };
 
-// box-linear index b -> coordinates (the arithmetic of box_coords): bit-identical to the whole-grid decode
-__device__ __forceinline__ void jac_box_coords(const GridArgs &g, const BoxArgs &bx, int cin, int64_t b, float &x0, float &x1, float &x2)
-{
-    uint32_t i0, i1, i2 = 0u;
-    if (cin == 3) {
-        const uint32_t e2 = (uint32_t)bx.extent[2], e1 = (uint32_t)bx.extent[1];
-        if (bx.fast) {
-            const uint32_t bu = (uint32_t)b;
-            const uint32_t t2 = fast_div(bu, bx.magic[2], e2);
-            const uint32_t t1 = fast_div(t2, bx.magic[1], e1);
-            i0 = t1; i1 = t2 - t1 * e1; i2 = bu - t2 * e2;
-        } else {
-            const int64_t t2 = b / (int64_t)e2, t1 = t2 / (int64_t)e1;
-            i0 = (uint32_t)t1; i1 = (uint32_t)(t2 - t1 * e1); i2 = (uint32_t)(b - t2 * e2);
-        }
-    } else {
-        const uint32_t e1 = (uint32_t)bx.extent[1];
-        if (bx.fast) {
-            const uint32_t bu = (uint32_t)b;
-            const uint32_t t1 = fast_div(bu, bx.magic[1], e1);
-            i0 = t1; i1 = bu - t1 * e1;
-        } else {
-            const int64_t t1 = b / (int64_t)e1;
-            i0 = (uint32_t)t1; i1 = (uint32_t)(b - t1 * e1);
-        }
-    }
-    x0 = lin_coord32(g, 0, (uint32_t)bx.start[0] + (uint32_t)bx.step[0] * i0);
-    x1 = lin_coord32(g, 1, (uint32_t)bx.start[1] + (uint32_t)bx.step[1] * i1);
-    if (cin == 3) x2 = lin_coord32(g, 2, (uint32_t)bx.start[2] + (uint32_t)bx.step[2] * i2);
-}
+#define TILE_CHAIN_PACKED
+#define TILE_(name) jac_##name
+#include "brief_tile.inc"
 
 // the value lane 4 (lane / 4) holds, in every lane of its quad (DPP quad_perm [0, 0, 0, 0]); call it from wave-uniform control flow
 __device__ __forceinline__ float jac_quad0(float v)
 {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x00, 0xf, 0xf, false));
-}
-
-// acc[t] += A(mt = wv + 4 t, steps [0, ksteps)) * image, for the tiles mt < mts; A block (mt, step) at A + ((mt * ksteps + step) * 64 + lane) * 4
-template <int MTW>
-__device__ __forceinline__ void jac_chain(f32x16 (&acc)[MTW], const float *__restrict__ A, int ksteps, int mts,
-                                          const float4 *Xs, int wv, int lane)
-{
-    float4 an[MTW];
-#pragma unroll
-    for (int t = 0; t < MTW; ++t)
-        if (wv + 4 * t < mts) an[t] = *reinterpret_cast<const float4 *>(A + ((int64_t)(wv + 4 * t) * ksteps * 64 + lane) * 4);
-    for (int it = 0; it < ksteps; ++it) {
-        float4 ac[MTW];
-#pragma unroll
-        for (int t = 0; t < MTW; ++t) ac[t] = an[t];
-        if (it + 1 < ksteps) {
-#pragma unroll
-            for (int t = 0; t < MTW; ++t)
-                if (wv + 4 * t < mts) an[t] = *reinterpret_cast<const float4 *>(A + (((int64_t)(wv + 4 * t) * ksteps + it + 1) * 64 + lane) * 4);
-        }
-        const float4 b = Xs[it * 64 + lane];
-#pragma unroll
-        for (int t = 0; t < MTW; ++t) {
-            if (wv + 4 * t < mts) {
-                acc[t] = MFMA(ac[t].x, b.x, acc[t]);
-                acc[t] = MFMA(ac[t].y, b.y, acc[t]);
-                acc[t] = MFMA(ac[t].z, b.z, acc[t]);
-                acc[t] = MFMA(ac[t].w, b.w, acc[t]);
-            }
-        }
-    }
 }
 
 // the bias in the value column (q == 0), zero in the tangent columns
@@ -133,19 +77,6 @@ __device__ __forceinline__ void jac_bias(f32x16 (&acc)[MTW], const float *__rest
         const int mt = wv + 4 * t;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = mt < nt && value_col ? b[32 * mt + ROWMAP(r, hi)] : 0.f;
-    }
-}
-
-template <int MTW>
-__device__ __forceinline__ void jac_write_image(float4 *Xs, const f32x16 (&h)[MTW], int nt, int wv, int lane)
-{
-#pragma unroll
-    for (int t = 0; t < MTW; ++t) {
-        const int mt = wv + 4 * t;
-        if (mt < nt) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) Xs[(mt * 4 + q) * 64 + lane] = make_float4(h[t][4 * q], h[t][4 * q + 1], h[t][4 * q + 2], h[t][4 * q + 3]);
-        }
     }
 }
 

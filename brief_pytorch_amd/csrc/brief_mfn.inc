@@ -74,106 +74,11 @@ struct MfnArgs {
     float scale_min, den, span, vmin;
 };
 
-// ---- the tile helpers of brief_nerf.inc, restated under MFN names (each kernel family carries its own copies, so that no existing
-// kernel's code changes)
-__device__ __forceinline__ void mfn_box_coords(const GridArgs &g, const BoxArgs &bx, int cin, int64_t b, float &x0, float &x1, float &x2)
-{
-    uint32_t i0, i1, i2 = 0u;
-    if (cin == 3) {
-        const uint32_t e2 = (uint32_t)bx.extent[2], e1 = (uint32_t)bx.extent[1];
-        if (bx.fast) {
-            const uint32_t bu = (uint32_t)b;
-            const uint32_t t2 = fast_div(bu, bx.magic[2], e2);
-            const uint32_t t1 = fast_div(t2, bx.magic[1], e1);
-            i0 = t1; i1 = t2 - t1 * e1; i2 = bu - t2 * e2;
-        } else {
-            const int64_t t2 = b / (int64_t)e2, t1 = t2 / (int64_t)e1;
-            i0 = (uint32_t)t1; i1 = (uint32_t)(t2 - t1 * e1); i2 = (uint32_t)(b - t2 * e2);
-        }
-    } else {
-        const uint32_t e1 = (uint32_t)bx.extent[1];
-        if (bx.fast) {
-            const uint32_t bu = (uint32_t)b;
-            const uint32_t t1 = fast_div(bu, bx.magic[1], e1);
-            i0 = t1; i1 = bu - t1 * e1;
-        } else {
-            const int64_t t1 = b / (int64_t)e1;
-            i0 = (uint32_t)t1; i1 = (uint32_t)(b - t1 * e1);
-        }
-    }
-    x0 = lin_coord32(g, 0, (uint32_t)bx.start[0] + (uint32_t)bx.step[0] * i0);
-    x1 = lin_coord32(g, 1, (uint32_t)bx.start[1] + (uint32_t)bx.step[1] * i1);
-    if (cin == 3) x2 = lin_coord32(g, 2, (uint32_t)bx.start[2] + (uint32_t)bx.step[2] * i2);
-}
-
-// acc[t] += A(mt = wv + 4 t, steps [0, ksteps)) * image, for the tiles mt < mts; A block (mt, step) at A + ((mt * KS + step) * 64 + lane) * 4
-template <int MTW>
-__device__ __forceinline__ void mfn_chain(f32x16 (&acc)[MTW], const float *__restrict__ A, int KS, int ksteps, int mts,
-                                          const float4 *Xs, int wv, int lane)
-{
-    float4 an[MTW];
-#pragma unroll
-    for (int t = 0; t < MTW; ++t)
-        if (wv + 4 * t < mts) an[t] = *reinterpret_cast<const float4 *>(A + ((int64_t)(wv + 4 * t) * KS * 64 + lane) * 4);
-    for (int it = 0; it < ksteps; ++it) {
-        float4 ac[MTW];
-#pragma unroll
-        for (int t = 0; t < MTW; ++t) ac[t] = an[t];
-        if (it + 1 < ksteps) {
-#pragma unroll
-            for (int t = 0; t < MTW; ++t)
-                if (wv + 4 * t < mts) an[t] = *reinterpret_cast<const float4 *>(A + (((int64_t)(wv + 4 * t) * KS + it + 1) * 64 + lane) * 4);
-        }
-        const float4 b = Xs[it * 64 + lane];
-#pragma unroll
-        for (int t = 0; t < MTW; ++t) {
-            if (wv + 4 * t < mts) {
-                acc[t] = MFMA(ac[t].x, b.x, acc[t]);
-                acc[t] = MFMA(ac[t].y, b.y, acc[t]);
-                acc[t] = MFMA(ac[t].z, b.z, acc[t]);
-                acc[t] = MFMA(ac[t].w, b.w, acc[t]);
-            }
-        }
-    }
-}
-
-template <int MTW>
-__device__ __forceinline__ void mfn_bias(f32x16 (&acc)[MTW], const float *__restrict__ b, int nt, int wv, int hi)
-{
-#pragma unroll
-    for (int t = 0; t < MTW; ++t) {
-        const int mt = wv + 4 * t;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = mt < nt ? b[32 * mt + ROWMAP(r, hi)] : 0.f;
-    }
-}
-
-template <int MTW>
-__device__ __forceinline__ void mfn_write_image(float4 *Xs, const f32x16 (&h)[MTW], int nt, int wv, int lane)
-{
-#pragma unroll
-    for (int t = 0; t < MTW; ++t) {
-        const int mt = wv + 4 * t;
-        if (mt < nt) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) Xs[(mt * 4 + q) * 64 + lane] = make_float4(h[t][4 * q], h[t][4 * q + 1], h[t][4 * q + 2], h[t][4 * q + 3]);
-        }
-    }
-}
-
-// plane[row][col0 + s] for every accumulator element this lane holds
-template <int MTW>
-__device__ __forceinline__ void mfn_stash(float *__restrict__ plane, int64_t npad, int64_t col0, const f32x16 (&h)[MTW], int nt, int wv, int hi, int s)
-{
-#pragma unroll
-    for (int t = 0; t < MTW; ++t) {
-        const int mt = wv + 4 * t;
-        if (mt < nt) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) plane[(int64_t)(32 * mt + ROWMAP(r, hi)) * npad + col0 + s] = h[t][r];
-        }
-    }
-}
+// ---- the tile helpers (mfn_box_coords .. mfn_frag): the one text of brief_tile.inc, compiled here under the mfn_ prefix; functions of
+// this family's own, because one set of functions called by every family changes the code of existing kernels (88 of 330: the note in
+// brief_nerf.inc).  Nothing stayed a copy.
+#define TILE_(name) mfn_##name
+#include "brief_tile.inc"
 
 // filter of feature f at x = (x_0, x_1, x_2, |x|^2): sin(a), cos(a) and the envelope e (1 for Fourier); fb: the filter's packed block
 template <bool GABOR>
@@ -543,14 +448,6 @@ __global__ void k_mfn_repack(const brief_mfn_desc d, const float *__restrict__ p
     if (e >= lay.total) return;
     const int F = d.features, cin = d.cin, cout = d.cout, FP = lay.FP;
     float v = 0.f;
-    // fragment element q of a block sequence with KS steps per row tile: (row, k)
-    auto frag = [](int64_t q, int KS, int &row, int &k) {
-        const int j = (int)(q & 3), lanei = (int)((q >> 2) & 63);
-        const int64_t blk = q >> 8;
-        const int step = (int)(blk % KS), mt = (int)(blk / KS);
-        row = 32 * mt + (lanei & 31);
-        k = 8 * step + 4 * (lanei >> 5) + j;
-    };
     int row, k;
     if (e < lay.whf) {
         const int l = 1 + (int)((e - lay.hid) / lay.hid_stride);
@@ -558,17 +455,17 @@ __global__ void k_mfn_repack(const brief_mfn_desc d, const float *__restrict__ p
         const float *W = params + mfn_canon_hidden(d, l);
         if (r < 2 * (int64_t)FP * FP) {
             const bool bwd = r >= (int64_t)FP * FP;
-            frag(bwd ? r - (int64_t)FP * FP : r, FP / 8, row, k);
+            mfn_frag(bwd ? r - (int64_t)FP * FP : r, FP / 8, row, k);
             if (row < F && k < F) v = bwd ? W[(int64_t)k * F + row] : W[(int64_t)row * F + k];
         } else {
             const int f = (int)(r - 2 * (int64_t)FP * FP);
             if (f < F) v = W[(int64_t)F * F + f];
         }
     } else if (e < lay.whb) {
-        frag(e - lay.whf, FP / 8, row, k);
+        mfn_frag(e - lay.whf, FP / 8, row, k);
         if (row < cout && k < F) v = params[mfn_canon_head(d) + (int64_t)row * F + k];
     } else if (e < lay.bh) {
-        frag(e - lay.whb, 4, row, k);
+        mfn_frag(e - lay.whb, 4, row, k);
         if (row < F && k < cout) v = params[mfn_canon_head(d) + (int64_t)k * F + row];
     } else if (e < lay.filt) {
         const int c = (int)(e - lay.bh);

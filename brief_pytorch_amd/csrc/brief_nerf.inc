@@ -77,112 +77,12 @@ struct NerfArgs {
     float scale_min, den, span, vmin;
 };
 
-// ---- the tile helpers of brief_ffn.inc (ffn_box_coords, ffn_chain, ffn_bias, ffn_write_image, ffn_stash), restated under NeRF names:
-// calling the FFN helpers from a second kernel family changed the register allocation of the existing k_ffn_fwd instantiations, so the
-// NeRF kernels carry their own copies and every FFN kernel compiles to the code it had before this file existed.
-// (Measured again with four families in the file, the NeRF, MFN and taper copies replaced by calls to the ffn_* helpers: 88 of the 330
-// kernels compile to other code, 24 k_ffn_fwd instantiations whose source did not change among them; k_mfn_fwd<1|2, false, ., .> gains
-// 4 VGPRs, k_mfn_fwd<8, false, false, false> goes from 144 to 76 bytes of scratch, k_ffn_fwd<7|8, false, false> change instruction
-// counts.  So the copies stay; what the families share is their host side, brief_family_host.inc.)
-// box-linear index b -> coordinates (the arithmetic of box_coords, on the box of NerfArgs): bit-identical to the whole-grid decode
-__device__ __forceinline__ void nerf_box_coords(const GridArgs &g, const BoxArgs &bx, int cin, int64_t b, float &x0, float &x1, float &x2)
-{
-    uint32_t i0, i1, i2 = 0u;
-    if (cin == 3) {
-        const uint32_t e2 = (uint32_t)bx.extent[2], e1 = (uint32_t)bx.extent[1];
-        if (bx.fast) {
-            const uint32_t bu = (uint32_t)b;
-            const uint32_t t2 = fast_div(bu, bx.magic[2], e2);
-            const uint32_t t1 = fast_div(t2, bx.magic[1], e1);
-            i0 = t1; i1 = t2 - t1 * e1; i2 = bu - t2 * e2;
-        } else {
-            const int64_t t2 = b / (int64_t)e2, t1 = t2 / (int64_t)e1;
-            i0 = (uint32_t)t1; i1 = (uint32_t)(t2 - t1 * e1); i2 = (uint32_t)(b - t2 * e2);
-        }
-    } else {
-        const uint32_t e1 = (uint32_t)bx.extent[1];
-        if (bx.fast) {
-            const uint32_t bu = (uint32_t)b;
-            const uint32_t t1 = fast_div(bu, bx.magic[1], e1);
-            i0 = t1; i1 = bu - t1 * e1;
-        } else {
-            const int64_t t1 = b / (int64_t)e1;
-            i0 = (uint32_t)t1; i1 = (uint32_t)(b - t1 * e1);
-        }
-    }
-    x0 = lin_coord32(g, 0, (uint32_t)bx.start[0] + (uint32_t)bx.step[0] * i0);
-    x1 = lin_coord32(g, 1, (uint32_t)bx.start[1] + (uint32_t)bx.step[1] * i1);
-    if (cin == 3) x2 = lin_coord32(g, 2, (uint32_t)bx.start[2] + (uint32_t)bx.step[2] * i2);
-}
-
-// acc[t] += A(mt = wv + 4 t, steps [0, ksteps)) * image, for the tiles mt < mts; A block (mt, step) at A + ((mt * KS + step) * 64 + lane) * 4
-template <int MTW>
-__device__ __forceinline__ void nerf_chain(f32x16 (&acc)[MTW], const float *__restrict__ A, int KS, int ksteps, int mts,
-                                           const float4 *Xs, int wv, int lane)
-{
-    float4 an[MTW];
-#pragma unroll
-    for (int t = 0; t < MTW; ++t)
-        if (wv + 4 * t < mts) an[t] = *reinterpret_cast<const float4 *>(A + ((int64_t)(wv + 4 * t) * KS * 64 + lane) * 4);
-    for (int it = 0; it < ksteps; ++it) {
-        float4 ac[MTW];
-#pragma unroll
-        for (int t = 0; t < MTW; ++t) ac[t] = an[t];
-        if (it + 1 < ksteps) {
-#pragma unroll
-            for (int t = 0; t < MTW; ++t)
-                if (wv + 4 * t < mts) an[t] = *reinterpret_cast<const float4 *>(A + (((int64_t)(wv + 4 * t) * KS + it + 1) * 64 + lane) * 4);
-        }
-        const float4 b = Xs[it * 64 + lane];
-#pragma unroll
-        for (int t = 0; t < MTW; ++t) {
-            if (wv + 4 * t < mts) {
-                acc[t] = MFMA(ac[t].x, b.x, acc[t]);
-                acc[t] = MFMA(ac[t].y, b.y, acc[t]);
-                acc[t] = MFMA(ac[t].z, b.z, acc[t]);
-                acc[t] = MFMA(ac[t].w, b.w, acc[t]);
-            }
-        }
-    }
-}
-
-template <int MTW>
-__device__ __forceinline__ void nerf_bias(f32x16 (&acc)[MTW], const float *__restrict__ b, int nt, int wv, int hi)
-{
-#pragma unroll
-    for (int t = 0; t < MTW; ++t) {
-        const int mt = wv + 4 * t;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = mt < nt ? b[32 * mt + ROWMAP(r, hi)] : 0.f;
-    }
-}
-
-template <int MTW>
-__device__ __forceinline__ void nerf_write_image(float4 *Xs, const f32x16 (&h)[MTW], int nt, int wv, int lane)
-{
-#pragma unroll
-    for (int t = 0; t < MTW; ++t) {
-        const int mt = wv + 4 * t;
-        if (mt < nt) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) Xs[(mt * 4 + q) * 64 + lane] = make_float4(h[t][4 * q], h[t][4 * q + 1], h[t][4 * q + 2], h[t][4 * q + 3]);
-        }
-    }
-}
-
-// plane[row][col0 + s] for every accumulator element this lane holds
-template <int MTW>
-__device__ __forceinline__ void nerf_stash(float *__restrict__ plane, int64_t npad, int64_t col0, const f32x16 (&h)[MTW], int nt, int wv, int hi, int s)
-{
-#pragma unroll
-    for (int t = 0; t < MTW; ++t) {
-        const int mt = wv + 4 * t;
-        if (mt < nt) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) plane[(int64_t)(32 * mt + ROWMAP(r, hi)) * npad + col0 + s] = h[t][r];
-        }
-    }
-}
+// ---- the tile helpers nerf_box_coords, nerf_chain, nerf_bias, nerf_write_image, nerf_stash and nerf_frag: the one text of brief_tile.inc,
+// compiled here under the nerf_ prefix.  One text, not one set of functions: with the NeRF, MFN and taper kernels calling the ffn_*
+// helpers, 88 of the 330 kernels compiled to other code, 24 k_ffn_fwd instantiations whose source did not change among them.  No
+// family keeps a copy; only brief_jac.inc has a bias (jac_bias, one parameter more) and a frag lambda of its own.
+#define TILE_(name) nerf_##name
+#include "brief_tile.inc"
 
 // image element (k, s) of a 32-sample tile (the layout of brief_ffn.inc)
 __device__ __forceinline__ int nerf_img(int k, int s) { return ((k >> 3) * 64 + 32 * ((k >> 2) & 1) + s) * 4 + (k & 3); }
@@ -482,17 +382,9 @@ __global__ void k_nerf_repack(const brief_nerf_desc d, const float *__restrict__
     if (e >= lay.total) return;
     const int F = d.features, dd = lay.d, cout = d.cout, FP = lay.FP;
     float v = 0.f;
-    // fragment element q of a block sequence with KS steps per row tile: (row, k)
-    auto frag = [](int64_t q, int KS, int &row, int &k) {
-        const int j = (int)(q & 3), lanei = (int)((q >> 2) & 63);
-        const int64_t blk = q >> 8;
-        const int step = (int)(blk % KS), mt = (int)(blk / KS);
-        row = 32 * mt + (lanei & 31);
-        k = 8 * step + 4 * (lanei >> 5) + j;
-    };
     int row, k;
     if (e < lay.b0) {
-        frag(e - lay.w0f, lay.DP / 8, row, k);
+        nerf_frag(e - lay.w0f, lay.DP / 8, row, k);
         if (row < F && k < dd) v = params[(int64_t)row * dd + k];
     } else if (e < lay.hid) {
         const int f = (int)(e - lay.b0);
@@ -504,23 +396,23 @@ __global__ void k_nerf_repack(const brief_nerf_desc d, const float *__restrict__
         const float *W = params + nerf_canon_hidden(d, l);
         if (r < 2 * (int64_t)FP * FP) {
             const bool bwd = r >= (int64_t)FP * FP;
-            frag(bwd ? r - (int64_t)FP * FP : r, FP / 8, row, k);
+            nerf_frag(bwd ? r - (int64_t)FP * FP : r, FP / 8, row, k);
             if (row < F && k < F) v = bwd ? W[(int64_t)k * ldw + coff + row] : W[(int64_t)row * ldw + coff + k];
         } else {
             const int f = (int)(r - 2 * (int64_t)FP * FP);
             if (f < F) v = W[(int64_t)F * ldw + f];
         }
     } else if (e < lay.whb) {
-        frag(e - lay.whf, FP / 8, row, k);
+        nerf_frag(e - lay.whf, FP / 8, row, k);
         if (row < cout && k < F) v = params[nerf_canon_head(d) + (int64_t)row * F + k];
     } else if (e < lay.bh) {
-        frag(e - lay.whb, 4, row, k);
+        nerf_frag(e - lay.whb, 4, row, k);
         if (row < F && k < cout) v = params[nerf_canon_head(d) + (int64_t)k * F + row];
     } else if (e < lay.wse) {
         const int c = (int)(e - lay.bh);
         if (c < cout) v = params[nerf_canon_head(d) + (int64_t)cout * F + c];
     } else {
-        frag(e - lay.wse, lay.DP / 8, row, k);
+        nerf_frag(e - lay.wse, lay.DP / 8, row, k);
         if (row < F && k < dd) v = params[nerf_canon_hidden(d, lay.sl) + (int64_t)row * (dd + F) + k];
     }
     pk[e] = v;

@@ -11,8 +11,9 @@
 //
 // Every layer is padded on its own: OP_l = 32 ceil(out_l / 32) output rows, K steps of 8 rows: ks_l = ceil(in_l / 8) forward,
 // kb_l = ceil(out_l / 8) backward.  Padded rows / columns and biases are zero: a padded unit has phase 0, emits sin(0) = 0 and receives
-// a zero gradient.  The tile helpers are the ones of brief_nerf.inc restated under taper names (see the note there: sharing them
-// between kernel families changes the code of the existing kernels).
+// a zero gradient.  The tile helpers are the one text of brief_tile.inc compiled under the taper_ prefix (not functions shared with
+// the other families: that changes the code of 88 of the 330 kernels, see the note in brief_nerf.inc); the chain is that file's
+// TILE_CHAIN_PACKED form, a layer's fragment rows being exactly ksteps steps long.  Nothing stayed a copy.
 //
 // LDS per workgroup: the image [max_l OP_l rows][32 samples] plus 32 x float4 of coordinates (1024 rows: 131 584 bytes).
 //
@@ -90,105 +91,9 @@ struct TaperArgs {
     float scale_min, den, span, vmin;
 };
 
-// box-linear index b -> coordinates (the arithmetic of box_coords): bit-identical to the whole-grid decode
-__device__ __forceinline__ void taper_box_coords(const GridArgs &g, const BoxArgs &bx, int cin, int64_t b, float &x0, float &x1, float &x2)
-{
-    uint32_t i0, i1, i2 = 0u;
-    if (cin == 3) {
-        const uint32_t e2 = (uint32_t)bx.extent[2], e1 = (uint32_t)bx.extent[1];
-        if (bx.fast) {
-            const uint32_t bu = (uint32_t)b;
-            const uint32_t t2 = fast_div(bu, bx.magic[2], e2);
-            const uint32_t t1 = fast_div(t2, bx.magic[1], e1);
-            i0 = t1; i1 = t2 - t1 * e1; i2 = bu - t2 * e2;
-        } else {
-            const int64_t t2 = b / (int64_t)e2, t1 = t2 / (int64_t)e1;
-            i0 = (uint32_t)t1; i1 = (uint32_t)(t2 - t1 * e1); i2 = (uint32_t)(b - t2 * e2);
-        }
-    } else {
-        const uint32_t e1 = (uint32_t)bx.extent[1];
-        if (bx.fast) {
-            const uint32_t bu = (uint32_t)b;
-            const uint32_t t1 = fast_div(bu, bx.magic[1], e1);
-            i0 = t1; i1 = bu - t1 * e1;
-        } else {
-            const int64_t t1 = b / (int64_t)e1;
-            i0 = (uint32_t)t1; i1 = (uint32_t)(b - t1 * e1);
-        }
-    }
-    x0 = lin_coord32(g, 0, (uint32_t)bx.start[0] + (uint32_t)bx.step[0] * i0);
-    x1 = lin_coord32(g, 1, (uint32_t)bx.start[1] + (uint32_t)bx.step[1] * i1);
-    if (cin == 3) x2 = lin_coord32(g, 2, (uint32_t)bx.start[2] + (uint32_t)bx.step[2] * i2);
-}
-
-// acc[t] += A(mt = wv + 4 t, steps [0, ksteps)) * image, for the tiles mt < mts; A block (mt, step) at A + ((mt * ksteps + step) * 64 + lane) * 4
-template <int MTW>
-__device__ __forceinline__ void taper_chain(f32x16 (&acc)[MTW], const float *__restrict__ A, int ksteps, int mts,
-                                            const float4 *Xs, int wv, int lane)
-{
-    float4 an[MTW];
-#pragma unroll
-    for (int t = 0; t < MTW; ++t)
-        if (wv + 4 * t < mts) an[t] = *reinterpret_cast<const float4 *>(A + ((int64_t)(wv + 4 * t) * ksteps * 64 + lane) * 4);
-    for (int it = 0; it < ksteps; ++it) {
-        float4 ac[MTW];
-#pragma unroll
-        for (int t = 0; t < MTW; ++t) ac[t] = an[t];
-        if (it + 1 < ksteps) {
-#pragma unroll
-            for (int t = 0; t < MTW; ++t)
-                if (wv + 4 * t < mts) an[t] = *reinterpret_cast<const float4 *>(A + (((int64_t)(wv + 4 * t) * ksteps + it + 1) * 64 + lane) * 4);
-        }
-        const float4 b = Xs[it * 64 + lane];
-#pragma unroll
-        for (int t = 0; t < MTW; ++t) {
-            if (wv + 4 * t < mts) {
-                acc[t] = MFMA(ac[t].x, b.x, acc[t]);
-                acc[t] = MFMA(ac[t].y, b.y, acc[t]);
-                acc[t] = MFMA(ac[t].z, b.z, acc[t]);
-                acc[t] = MFMA(ac[t].w, b.w, acc[t]);
-            }
-        }
-    }
-}
-
-template <int MTW>
-__device__ __forceinline__ void taper_bias(f32x16 (&acc)[MTW], const float *__restrict__ b, int nt, int wv, int hi)
-{
-#pragma unroll
-    for (int t = 0; t < MTW; ++t) {
-        const int mt = wv + 4 * t;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = mt < nt ? b[32 * mt + ROWMAP(r, hi)] : 0.f;
-    }
-}
-
-template <int MTW>
-__device__ __forceinline__ void taper_write_image(float4 *Xs, const f32x16 (&h)[MTW], int nt, int wv, int lane)
-{
-#pragma unroll
-    for (int t = 0; t < MTW; ++t) {
-        const int mt = wv + 4 * t;
-        if (mt < nt) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) Xs[(mt * 4 + q) * 64 + lane] = make_float4(h[t][4 * q], h[t][4 * q + 1], h[t][4 * q + 2], h[t][4 * q + 3]);
-        }
-    }
-}
-
-// plane[row][col0 + s] for every accumulator element this lane holds (rows < 32 nt: the plane's own height)
-template <int MTW>
-__device__ __forceinline__ void taper_stash(float *__restrict__ plane, int64_t npad, int64_t col0, const f32x16 (&h)[MTW], int nt, int wv, int hi, int s)
-{
-#pragma unroll
-    for (int t = 0; t < MTW; ++t) {
-        const int mt = wv + 4 * t;
-        if (mt < nt) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) plane[(int64_t)(32 * mt + ROWMAP(r, hi)) * npad + col0 + s] = h[t][r];
-        }
-    }
-}
+#define TILE_CHAIN_PACKED
+#define TILE_(name) taper_##name
+#include "brief_tile.inc"
 
 // One 32-sample tile per workgroup iteration (persistent grid over the tiles), 4 waves; wave wv owns feature tiles wv, wv + 4, ... of
 // every layer (fewer of them in a narrower layer).  TRAIN: forward, loss, dgrad chain and the stash for k_taper_wgrad.  Inference:
@@ -498,14 +403,6 @@ __global__ void k_taper_repack(const brief_taper_desc d, const TaperLayout lay, 
     const float *W = params + lay.canon[l], *b = W + (int64_t)out * in;
     const float sf = l < L - 1 ? d.w0[l] * 0.15915494309189535f : 1.0f;      // w0_l / 2 pi (the head is not scaled)
     float v = 0.f;
-    // fragment element q of a block sequence with KS steps per row tile: (row, k)
-    auto frag = [](int64_t q, int KS, int &row, int &k) {
-        const int j = (int)(q & 3), lanei = (int)((q >> 2) & 63);
-        const int64_t blk = q >> 8;
-        const int step = (int)(blk % KS), mt = (int)(blk / KS);
-        row = 32 * mt + (lanei & 31);
-        k = 8 * step + 4 * (lanei >> 5) + j;
-    };
     int row, k;
     if (l == 0) {
         const int64_t q = e - lay.wf[0];
@@ -515,10 +412,10 @@ __global__ void k_taper_repack(const brief_taper_desc d, const TaperLayout lay, 
             else if (k == 3) v = b[row] * sf;
         }
     } else if (e < lay.wb[l]) {
-        frag(e - lay.wf[l], lay.ks[l], row, k);
+        taper_frag(e - lay.wf[l], lay.ks[l], row, k);
         if (row < out && k < in) v = W[(int64_t)row * in + k] * sf;
     } else if (e < lay.bias[l]) {
-        frag(e - lay.wb[l], lay.kb[l], row, k);
+        taper_frag(e - lay.wb[l], lay.kb[l], row, k);
         if (row < in && k < out) v = W[(int64_t)k * in + row] * d.w0[l - 1];
     } else {
         const int f = (int)(e - lay.bias[l]);
