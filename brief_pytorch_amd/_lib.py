@@ -128,7 +128,8 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_siren_jac_packed_count", "brief_siren_jac_repack", "brief_siren_jac_forward", "brief_siren_jac_forward_box",
            "brief_view_clip", "brief_view_coords", "brief_view_fold", "brief_view_finish", "brief_view_sample_host", "brief_view_clip_host",
            "brief_surface_fold", "brief_surface_bracket", "brief_surface_coords", "brief_surface_step", "brief_surface_shade",
-           "brief_view_sample_t_host"] \
+           "brief_view_sample_t_host",
+           "brief_siren_hess_forward", "brief_siren_hess_forward_box"] \
     + ["brief_%s_%s" % (prefix, entry) for prefix, _, _ in FAMILIES for entry in FAMILY_ENTRIES]
 
 
@@ -242,6 +243,8 @@ def lib():
     L.brief_siren_jac_repack.argtypes = [dp, vp, vp, vp]
     L.brief_siren_jac_forward.argtypes = [dp, vp, gp, bp, vp, vp, vp]
     L.brief_siren_jac_forward_box.argtypes = [dp, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, vp, vp]
+    L.brief_siren_hess_forward.argtypes = [dp, vp, gp, bp, vp, vp, vp, vp]
+    L.brief_siren_hess_forward_box.argtypes = [dp, vp, C.POINTER(GridBox), C.c_int64, C.c_int64, vp, vp, vp, vp]
     wp, i64, i32 = C.POINTER(ViewDesc), C.c_int64, C.c_int32
     L.brief_view_clip.argtypes = [wp, vp, vp, vp]
     L.brief_view_coords.argtypes = [wp, vp, vp, i64, i64, i64, i64, i32, vp, vp]

@@ -308,6 +308,23 @@ class NFGR:
         return gradient.decompress_divide_gradient(opt if opt is not None else _wrap(self.opt), orig_sideinfos_path, module_save_dir,
                                                    sideinfos_save_dir, region, step, self.device)
 
+    # ---- Hessian decode: the analytic second derivatives of the stored net in grey levels per voxel squared (brief_pytorch_amd/hessian.py)
+    @staticmethod
+    def decompress_hessian(opt, module_path, sideinfos, region=None, step=1, shape=None, mode="components", device="cuda", **kwargs):
+        """numpy float32: the Hessian of the stored fp32 SIREN over the region ("components": [*extent, cout, nh], grey levels per voxel
+        step squared) or a map derived from it ("laplacian", "eigenvalues", "vesselness"); hessian.decompress_hessian has the
+        definition, the units and the scope"""
+        from . import hessian
+        return hessian.decompress_hessian(opt, module_path, sideinfos, region, step, shape, mode, device, **kwargs)
+
+    def decompress_divide_hessian(self, orig_sideinfos_path, module_save_dir, sideinfos_save_dir, region=None, step=1, mode="components",
+                                  opt=None, **kwargs):
+        """the same for a stored DivideTask artefact: every block on its own grid and scale, discontinuous at the block faces
+        (hessian.decompress_divide_hessian)"""
+        from . import hessian
+        return hessian.decompress_divide_hessian(opt if opt is not None else _wrap(self.opt), orig_sideinfos_path, module_save_dir,
+                                                 sideinfos_save_dir, region, step, mode, self.device, **kwargs)
+
     # ---- SingleTask encode (main.py:322-454)
     def prepare_fit(self, data_path, data=None, logdir=None):
         """everything main.py:322-384 sets up before the loop: preprocess, loss weights, normalise, size the

@@ -447,6 +447,76 @@ class SIREN:
                                                               _lib.stream_ptr()))
         return jac, value
 
+    # ---- spatial Hessians: value, Jacobian and analytic second derivatives with respect to the coordinates (csrc/brief_hess.inc)
+    def spatial_hessian(self, coords, want_value=True, want_jac=True):
+        """(value [n, cout], jac [n, cout, cin], hess [n, cout, nh]) at arbitrary device coordinates [n, cin]: the net's output, its
+        analytic Jacobian and its analytic Hessian d2 phi_c / d x_a d x_b in coordinate units (with output_act, of the activated
+        output); float32, from brief_siren_hess_forward.  nh = 6 in the order (00, 01, 02, 11, 12, 22) for cin = 3 and nh = 3 in the
+        order (00, 01, 11) for cin = 2 (hessian.full() expands to the symmetric matrix).  value / jac are None with want_value /
+        want_jac False.  fp32 SIREN up to 1024 features only (BriefError otherwise).  The kernel reads the Jacobian decode's
+        fragment copy (_sync_jac), written anew at the head of every call."""
+        pk = self._sync_hess()
+        cin, cout = self.coords_channel, self.data_channel
+        nh = cin * (cin + 1) // 2
+        c = coords.to(self.params.device, torch.float32).reshape(-1, cin).contiguous()
+        n = c.shape[0]
+        value = torch.empty((n, cout), dtype=torch.float32, device=c.device) if want_value else None
+        jac = torch.empty((n, cout, cin), dtype=torch.float32, device=c.device) if want_jac else None
+        hess = torch.empty((n, cout, nh), dtype=torch.float32, device=c.device)
+        if n:
+            b = _lib.BatchDesc(c.data_ptr(), None, None, None, 0, n, 0, 0, 0)
+            _lib.check(_lib.lib().brief_siren_hess_forward(C.byref(self.desc), _lib.ptr(pk), None, C.byref(b), _lib.ptr(value), _lib.ptr(jac),
+                                                           _lib.ptr(hess), _lib.stream_ptr()))
+        return value, jac, hess
+
+    def _sync_hess(self):
+        """_sync_jac behind the Hessian decode's own refusal text"""
+        from . import hessian
+        self._require_gpu()
+        why = hessian.refusal(getattr(type(self), "kind", "SIREN"), self.precision, self.features)
+        if why is not None:
+            raise _lib.BriefError(why)
+        return self._sync_jac()
+
+    def decode_hessian_box(self, dims, start=None, stop=None, step=1, lo=-1.0, hi=1.0, chunk=None, want_value=False, want_jac=False):
+        """hess [*extent, cout, nh] over the box start:stop:step of the linspace grid `dims`, with decode_box's region semantics,
+        coordinates (bit for bit) and chunk loop: a box equals the slice of the whole grid's result, and neither `chunk` nor a repeat
+        of the call changes a bit.  Coordinate units: per unit of [lo, hi] squared (hessian.voxel_scale converts to grey levels per
+        voxel step squared).  With want_value or want_jac the result is (hess, value [*extent, cout] | None, jac [*extent, cout, cin]
+        | None)."""
+        pk = self._sync_hess()
+        nd = len(dims)
+        per = (lambda v: [v] * nd if v is None or np.isscalar(v) else list(v))
+        b, e = per(start), per(stop)
+        if len(b) != nd or len(e) != nd:
+            raise ValueError("start / stop need one entry per axis of dims")
+        b0, e0, st = region.normalize_region(dims, tuple(slice(x, y) for x, y in zip(b, e)), step)
+        ext = region.extents(b0, e0, st)
+        total = int(np.prod(ext))
+        cin, cout = self.coords_channel, self.data_channel
+        nh = cin * (cin + 1) // 2
+        dev = self.params.device
+        hess = torch.empty((*ext, cout, nh), dtype=torch.float32, device=dev)
+        value = torch.empty((*ext, cout), dtype=torch.float32, device=dev) if want_value else None
+        jac = torch.empty((*ext, cout, cin), dtype=torch.float32, device=dev) if want_jac else None
+        box = _lib.GridBox()
+        box.grid = self._grid(dims, lo, hi)
+        for a in range(nd):
+            box.start[a], box.step[a], box.extent[a] = b0[a], st[a], ext[a]
+        chunk = int(chunk or self.BOX_CHUNK)
+        if chunk < 1:
+            raise ValueError("chunk must be >= 1")
+        fh = hess.view(total, cout, nh)
+        fv = value.view(total, cout) if want_value else None
+        fj = jac.view(total, cout, cin) if want_jac else None
+        for off in range(0, total, chunk):
+            cnt = min(chunk, total - off)
+            _lib.check(_lib.lib().brief_siren_hess_forward_box(C.byref(self.desc), _lib.ptr(pk), C.byref(box), off, cnt,
+                                                               _lib.ptr(fv[off:off + cnt]) if want_value else None,
+                                                               _lib.ptr(fj[off:off + cnt]) if want_jac else None,
+                                                               _lib.ptr(fh[off:off + cnt]), _lib.stream_ptr()))
+        return (hess, value, jac) if want_value or want_jac else hess
+
     def train_step(self, n, targets, idx=None, coords=None, weights=None, grid=None, offset=0,
                    loss="datal2", thr=0.0, beta=0.01, want_yhat=False, rng=None):
         """zero_grad + forward + loss + backward of main.py:385-396 for one batch of n samples.

@@ -20,6 +20,14 @@ uint16 artefacts; not with `--shape`).
 grey levels per voxel step; `--gradient magnitude` writes its Euclidean norm over the axes, float32 [*extent, channels] (fp32 SIREN
 artefacts up to 1024 features under a `minmaxany_a_b` normalisation; `.npy` output only; not with `--mip`; `--shape` on SingleTask only).
 
+    python decompress.py -p <run yaml> -c <.../compressed> --region :,:,: --hessian components|laplacian|eigenvalues|vesselness -o hess.npy
+
+`--hessian components` writes the analytic Hessian of the stored net over the region, float32 [*extent, channels, 6] in the order
+(zz, zy, zx, yy, yx, xx) ([..., 3] = (yy, yx, xx) for 2-D data), in grey levels per voxel step squared; `laplacian` its trace
+[*extent, channels], `eigenvalues` its eigenvalues by increasing absolute value [*extent, channels, axes], `vesselness` Frangi's
+single-scale measure [*extent, channels] (the envelope of `--gradient`; `.npy` output only; not with `--mip`, `--gradient`, `--view` or
+`--view-surface`; `--step` keeps the unit, `--shape` (SingleTask only) uses the resampled grid's spacing).
+
     python decompress.py -p <run yaml> -c <.../compressed> --region :,:,: --view dz,dy,dx [--view-up uz,uy,ux]
         [--view-mode max|min|mean|slice] [--view-spacing s] [--view-depth-spacing t] [--view-size R,C] [--view-offset t]
         [--voxel-size sz,sy,sx] -o out.tif|out.npy|out.png
@@ -66,6 +74,8 @@ def main(argv=None):
     ap.add_argument("--mip", action="store_true", help="write the region's three max-intensity projections <out>_mip_{d,h,w}<ext> instead of the region")
     ap.add_argument("--gradient", default=None, metavar="{components,magnitude}",
                     help="write the region's analytic spatial gradient (grey levels per voxel step) or its magnitude instead of the region (.npy)")
+    ap.add_argument("--hessian", default=None, metavar="{components,laplacian,eigenvalues,vesselness}",
+                    help="write the region's analytic Hessian (grey levels per voxel step squared) or a map derived from it instead of the region (.npy)")
     ap.add_argument("--view", default=None, metavar="dz,dy,dx", help="write the orthographic view along this direction instead of the region (--region is the clip box)")
     ap.add_argument("--view-up", default=None, metavar="uz,uy,ux", help="the direction the image's rows run along (default: the grid axis the view direction has least of)")
     ap.add_argument("--view-mode", default="max", help="max | min | mean | slice (default max)")
@@ -81,6 +91,19 @@ def main(argv=None):
     ap.add_argument("--voxel-size", default=None, metavar="sz,sy,sx", help="physical extent of a voxel per axis (default 1,1,1)")
     ap.add_argument("-o", required=True, help="output file (.tif / .tiff / .npy / .png / .jpg)")
     args = ap.parse_args(argv)
+    if args.hessian is not None:
+        # every refusal by name, before the GPU path is imported
+        if args.hessian not in ("components", "laplacian", "eigenvalues", "vesselness"):
+            raise SystemExit("--hessian %s: unknown mode (components, laplacian, eigenvalues or vesselness)" % args.hessian)
+        for flag, on in (("--mip", args.mip), ("--gradient", args.gradient is not None), ("--view-surface", args.view_surface is not None),
+                         ("--view", args.view is not None)):
+            if on:
+                raise SystemExit("--hessian with %s: each writes a result of its own; ask for one of them" % flag)
+        if os.path.splitext(args.o)[1].lower() != ".npy":
+            raise SystemExit("--hessian writes float32 arrays as .npy only (got %s): Hessian output in image formats is not supported"
+                             % (os.path.splitext(args.o)[1] or "no extension"))
+        if args.shape and os.path.isdir(_paths(args.c)[2]):
+            raise SystemExit("--hessian --shape: resampling is not defined for a DivideTask artefact (every block has its own linspace grid)")
     if args.view is not None:
         _view_refusals(args)          # every refusal by name, before the GPU path is imported
     elif args.view_surface is not None or any(v is not None for v in (args.view_surface_side, args.view_refine, args.view_channel, args.view_light)):
@@ -122,6 +145,8 @@ def main(argv=None):
         return _mip(args, opt, region, divide)
     if args.gradient is not None:
         return _gradient(args, opt, region, shape, divide)
+    if args.hessian is not None:
+        return _hessian(args, opt, region, shape, divide)
     t0 = time.perf_counter()
     if divide:
         if shape is not None:
@@ -311,6 +336,28 @@ def _gradient(args, opt, region, shape, divide):
     np.save(args.o, data)
     print("%s region %s: spatial gradient (%s, grey levels per voxel), shape %s, dtype %s, decoded in %.3f s -> %s" % (
         "DivideTask" if divide else "SingleTask", args.region, args.gradient, tuple(data.shape), data.dtype, dt, args.o))
+    return 0
+
+
+def _hessian(args, opt, region, shape, divide):
+    import numpy as np
+    import torch
+    from brief_pytorch_amd import hessian
+    module, side_path, blocks_dir = _paths(args.c)
+    t0 = time.perf_counter()
+    try:
+        if divide:
+            h = hessian.decompress_divide_hessian_device(opt, side_path, module, blocks_dir, region, args.step, mode=args.hessian)
+        else:
+            h = hessian.decompress_hessian_device(opt, module, side_path, region, args.step, shape=shape, mode=args.hessian)
+    except ValueError as e:                                       # a refusal (net class, precision, width, normalisation, overlap, region)
+        raise SystemExit("--hessian: %s" % e)
+    data = h.cpu().numpy()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    np.save(args.o, data)
+    print("%s region %s: Hessian (%s, grey levels per voxel squared), shape %s, dtype %s, decoded in %.3f s -> %s" % (
+        "DivideTask" if divide else "SingleTask", args.region, args.hessian, tuple(data.shape), data.dtype, dt, args.o))
     return 0
 
 

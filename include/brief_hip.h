@@ -647,6 +647,24 @@ int brief_surface_shade(const brief_view_desc *view, const float *t, const float
 int brief_view_sample_t_host(const brief_view_desc *view, const int32_t *row, const int32_t *col, const float *t, int64_t n, float *pos, float *coord,
                              uint8_t *inside);
 
+/* ---- Hessian decode of an fp32 SIREN (csrc/brief_hess.inc) ------------------------------------------------------------------------
+ * value[n][cout] and jac[n][cout][cin] as brief_siren_jac_forward gives them, and hess[n][cout][nh] = d2 phi_c / d x_a d x_b (x_n), the
+ * analytic second derivatives with respect to the coordinates in coordinate units; with output_act, of the activated output.  nh = 6 in
+ * the order (00, 01, 02, 11, 12, 22) over the axes in coordinate order for cin = 3, nh = 3 in the order (00, 01, 11) for cin = 2 (the
+ * Hessian is symmetric: only the upper triangle is stored).  Forward mode of second order on the matrix pipe: the value, its tangents and
+ * its second derivatives travel through the layers together, a 10-column slot (cin = 3: 3 samples per 32-column MFMA tile) or a
+ * 6-column slot (cin = 2: 5 samples) per sample.  All outputs are float32; value and jac may be NULL, hess may not.  `packed` is the
+ * Jacobian decode's fragment buffer (brief_siren_jac_packed_count floats, written by brief_siren_jac_repack: call it after every change
+ * of the parameters).  Sample sources, box rules, refusals and the envelope are those of brief_siren_jac_forward / _forward_box
+ * (precision BRIEF_PREC_F32, features 1 .. 1024, layers >= 2, cin 2 | 3, cout 1 .. 4, packed and hess not NULL, n >= 1); the messages
+ * name the limit.  Enqueue-only on `stream`: no allocation, no synchronisation.  The result is deterministic, and a sample's result does
+ * not depend on its slot in a tile, on its neighbours or on how a box is cut into calls. */
+int brief_siren_hess_forward(const brief_siren_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
+                             float *value /* [n][cout] or NULL */, float *jac /* [n][cout][cin] or NULL */, float *hess /* [n][cout][nh] */,
+                             void *stream);
+int brief_siren_hess_forward_box(const brief_siren_desc *d, const float *packed, const brief_grid_box *box, int64_t offset, int64_t n,
+                                 float *value, float *jac, float *hess, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
