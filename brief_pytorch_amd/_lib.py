@@ -93,6 +93,10 @@ class ViewDesc(C.Structure):        # brief_view_desc
                 ("box_lo", C.c_float * 3), ("box_hi", C.c_float * 3)]
 
 
+class ViewPart(C.Structure):        # brief_view_part
+    _fields_ = [("start", C.c_int64 * 3), ("dims", C.c_int64 * 3), ("row0", C.c_int32), ("col0", C.c_int32), ("wrows", C.c_int32), ("wcols", C.c_int32)]
+
+
 VIEW_MODE = {"max": 0, "min": 1, "mean": 2, "slice": 3}      # BRIEF_VIEW_MAX .. BRIEF_VIEW_SLICE
 SURFACE_SIDE = {"above": 0, "below": 1}                      # BRIEF_SURFACE_ABOVE, BRIEF_SURFACE_BELOW
 
@@ -129,6 +133,7 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_view_clip", "brief_view_coords", "brief_view_fold", "brief_view_finish", "brief_view_sample_host", "brief_view_clip_host",
            "brief_surface_fold", "brief_surface_bracket", "brief_surface_coords", "brief_surface_step", "brief_surface_shade",
            "brief_view_sample_t_host",
+           "brief_view_part_clip", "brief_view_part_coords", "brief_view_part_fold", "brief_view_part_clip_host", "brief_view_part_sample_host",
            "brief_siren_hess_forward", "brief_siren_hess_forward_box"] \
     + ["brief_%s_%s" % (prefix, entry) for prefix, _, _ in FAMILIES for entry in FAMILY_ENTRIES]
 
@@ -258,6 +263,12 @@ def lib():
     L.brief_surface_step.argtypes = [wp, vp, C.c_int, i32, i32, i32, i32, vp, vp, vp]
     L.brief_surface_shade.argtypes = [wp, vp, vp, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp, vp]
     L.brief_view_sample_t_host.argtypes = [wp, vp, vp, vp, i64, vp, vp, vp]
+    pp = C.POINTER(ViewPart)
+    L.brief_view_part_clip.argtypes = [wp, pp, vp, vp, vp]
+    L.brief_view_part_coords.argtypes = [wp, pp, vp, vp, i64, i64, i64, i64, i32, vp, vp]
+    L.brief_view_part_fold.argtypes = [wp, pp, vp, vp, i64, i64, i64, i64, i32, vp, C.c_int, i32, i32, vp, vp, vp]
+    L.brief_view_part_clip_host.argtypes = [wp, pp, vp, vp]
+    L.brief_view_part_sample_host.argtypes = [wp, pp, vp, vp, vp, i64, vp, vp, vp, vp, vp]
     _LIB = L
     return L
 

@@ -124,3 +124,75 @@ BRIEF_HD void brief_view_ray_range(const brief_view_desc &v, int32_t row, int32_
     cnt = e > b ? e - b : 0;
     k0 = cnt ? b : 0;
 }
+
+// ---- a view of a PARTITION (a DivideTask artefact: one net per block): the nearest block owns a sample.
+// The lattice stays the view's, in the voxel-index space of the WHOLE volume: p_a is brief_view_pos, unchanged.  A block with the
+// inclusive index range [s_a, e_a], n_a = e_a - s_a + 1, owns the half-open CELL
+//     owned       (float)s_a - 0.5f <= p_a < (float)(s_a + n_a) - 0.5f on every axis      (exact floats: every axis is below 2^23)
+// and a sample is evaluated for the block iff it is inside the clip box (brief_view_inside) AND owned.  Both tests read the global
+// float p_a, and the cells of a tiling partition are disjoint and cover [-0.5, N - 0.5): a sample inside the clip box has exactly ONE
+// owner, whatever the roundings do at a face a ray skims; a sample in a gap no block covers has none.
+//     local       q_a = fl(p_a - (float)s_a)
+//     coordinate  brief_view_coord's two-sided form on the block's own grid: step_a = fl(fl(hi - lo) / (float)(n_a - 1)),
+//                 x_a = q_a < (float)(n_a / 2) ? fma(step_a, q_a, lo) : fma(-step_a, (float)(n_a - 1) - q_a, hi)
+// At an integer position q_a is exact and x_a is the block grid's own coordinate, bit for bit.  For q_a in [-0.5, 0) or
+// (n_a - 1, n_a - 0.5) the block's net is evaluated up to half a voxel OUTSIDE its grid: that is what "nearest" means.
+// Ray range: p_a(k) is monotone, so "inside the clip box and owned" is still one interval of k, the intersection of
+// brief_view_ray_range's with the cell's; the cell's ends are found by the same bisection (brief_view_first).
+// Only the rays of the block's WINDOW, [row0, row0 + wrows) x [col0, col0 + wcols) of the image, are clipped and walked: the host
+// computes it so that every ray outside it misses the block (view.make_part).  The view's origin is NOT moved into the window: that
+// would change the roundings of p and break single ownership.
+BRIEF_HD float brief_view_part_cell_lo(const brief_view_part &pt, int a) { return (float)pt.start[a] - 0.5f; }
+BRIEF_HD float brief_view_part_cell_hi(const brief_view_part &pt, int a) { return (float)(pt.start[a] + pt.dims[a]) - 0.5f; }
+
+BRIEF_HD bool brief_view_part_owned(const brief_view_part &pt, float p0, float p1, float p2)
+{
+    return brief_view_part_cell_lo(pt, 0) <= p0 && p0 < brief_view_part_cell_hi(pt, 0) && brief_view_part_cell_lo(pt, 1) <= p1 &&
+           p1 < brief_view_part_cell_hi(pt, 1) && brief_view_part_cell_lo(pt, 2) <= p2 && p2 < brief_view_part_cell_hi(pt, 2);
+}
+
+BRIEF_HD float brief_view_part_step(const brief_view_desc &v, const brief_view_part &pt, int a)
+{
+    BRIEF_VIEW_NO_CONTRACT
+    const float spread = v.hi - v.lo;
+    return pt.dims[a] > 1 ? spread / (float)(pt.dims[a] - 1) : 0.f;
+}
+
+BRIEF_HD float brief_view_part_local(const brief_view_part &pt, int a, float p)
+{
+    BRIEF_VIEW_NO_CONTRACT
+    return p - (float)pt.start[a];
+}
+
+BRIEF_HD float brief_view_part_coord(const brief_view_desc &v, const brief_view_part &pt, int a, float step, float q)
+{
+    BRIEF_VIEW_NO_CONTRACT
+    const int64_t nn = pt.dims[a];
+    if (q < (float)(nn / 2)) return fmaf(step, q, v.lo);
+    const float back = (float)(nn - 1) - q;
+    return fmaf(-step, back, v.hi);
+}
+
+// the samples of ray (row, col) the block evaluates are exactly k0 <= k < k0 + cnt (cnt == 0: none; k0 is 0 then)
+BRIEF_HD void brief_view_part_ray_range(const brief_view_desc &v, const brief_view_part &pt, int32_t row, int32_t col, int32_t &k0, int32_t &cnt)
+{
+    int32_t b = 0, e = v.depth;
+    for (int a = 0; a < 3; ++a) {
+        const float base = brief_view_base(v, a, row, col);
+        const bool rising = !(v.ddepth[a] < 0.f);
+        const float c_lo = brief_view_part_cell_lo(pt, a), c_hi = brief_view_part_cell_hi(pt, a);
+        // the clip box, closed: brief_view_ray_range's two bounds
+        int32_t first = brief_view_first(v, a, base, rising ? v.box_lo[a] : v.box_hi[a], rising, false);
+        int32_t end = brief_view_first(v, a, base, rising ? v.box_hi[a] : v.box_lo[a], rising, true);
+        b = first > b ? first : b;
+        e = end < e ? end : e;
+        // the cell, half-open.  rising: from the first p >= s - 0.5 up to the first p >= e + 0.5; falling: from the first p < e + 0.5 up
+        // to the first p < s - 0.5
+        first = brief_view_first(v, a, base, rising ? c_lo : c_hi, rising, !rising);
+        end = brief_view_first(v, a, base, rising ? c_hi : c_lo, rising, !rising);
+        b = first > b ? first : b;
+        e = end < e ? end : e;
+    }
+    cnt = e > b ? e - b : 0;
+    k0 = cnt ? b : 0;
+}

@@ -1,6 +1,6 @@
 // brief_view.inc — orthographic view decode: k_view_clip, k_view_coords, k_view_fold, k_view_finish and their C-ABI entries brief_view_*
 // (part of the single translation unit brief_hip.hip, included at its very end: kernels and host code of a feature that touches no
-// other kernel).  The geometry is csrc/brief_view.h, compiled here for the device and for the host entries alike.
+// other kernel); behind them k_view_part_clip / _coords / _fold, the same for one block of a partition, and the surface view.  The geometry is csrc/brief_view.h, compiled here for the device and for the host entries alike.
 //
 // A view is rows x cols rays of `depth` samples each.  The net is evaluated by its own forward entry on explicit coordinates; these
 // kernels only say WHERE (clip, coords) and reduce WHAT came back (fold, finish):
@@ -279,6 +279,228 @@ int brief_view_clip_host(const brief_view_desc *view, int32_t *k0, int32_t *cnt)
             const int64_t r = (int64_t)row * view->cols + col;
             brief_view_ray_range(*view, row, col, k0[r], cnt[r]);
         }
+    return 0;
+}
+
+}   // extern "C"
+
+// ---- view of a partition: the nearest block owns a sample (csrc/brief_view.h "a view of a PARTITION"; view.render_partition).
+//   k_view_part_clip    one thread per WINDOW ray: the interval of its samples inside the clip box and the block's cell.
+//   k_view_part_coords  k_view_coords on the block's compacted list, giving block-local coordinates.
+//   k_view_part_fold    k_view_fold with the exact test (clip box and cell) on every sample.
+// The layout is that of k_view_coords / k_view_fold: ray-major list, a group of G = 2^lg lanes per ray, contiguous spans per wave.
+// k0 and off are indexed by window ray, hits and acc by image ray (the pixel).  No atomics: within a launch a pixel has one owner, and
+// the launches of a view, block after block, follow each other on one stream.
+struct ViewPartRay { ViewRay q; int64_t pixel; };
+__device__ __forceinline__ ViewPartRay view_part_ray(const brief_view_desc &v, const brief_view_part &pt, const ViewChunk &ch,
+                                                     const int64_t *__restrict__ off, int64_t g)
+{
+    ViewPartRay w;
+    ViewRay &q = w.q;
+    const bool live = g < ch.r1 - ch.r0;
+    q.r = ch.r0 + (live ? g : 0);
+    q.a = off[q.r];
+    const int64_t b = off[q.r + 1];
+    q.lo = q.a > ch.s0 ? q.a : ch.s0;
+    q.hi = live ? (b < ch.s1 ? b : ch.s1) : q.lo;
+    const int32_t wr = (int32_t)(q.r / pt.wcols);
+    const int32_t row = pt.row0 + wr, col = pt.col0 + (int32_t)(q.r - (int64_t)wr * pt.wcols);
+    w.pixel = (int64_t)row * v.cols + col;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) q.base[a] = brief_view_base(v, a, row, col);
+    return w;
+}
+
+__global__ __launch_bounds__(256) void k_view_part_clip(brief_view_desc v, brief_view_part pt, int32_t *__restrict__ k0, int32_t *__restrict__ cnt)
+{
+    const int64_t rays = (int64_t)pt.wrows * pt.wcols;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rays; r += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t wr = (int32_t)(r / pt.wcols);
+        int32_t b, n;
+        brief_view_part_ray_range(v, pt, pt.row0 + wr, pt.col0 + (int32_t)(r - (int64_t)wr * pt.wcols), b, n);
+        k0[r] = b;
+        cnt[r] = n;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_view_part_coords(brief_view_desc v, brief_view_part pt, ViewChunk ch, const int32_t *__restrict__ k0,
+                                                          const int64_t *__restrict__ off, float *__restrict__ coords)
+{
+    const int G = 1 << ch.lg, sub = threadIdx.x & (G - 1);
+    const int64_t groups = ((int64_t)gridDim.x * blockDim.x) >> ch.lg;
+    for (int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> ch.lg; g < ch.r1 - ch.r0; g += groups) {
+        const ViewRay q = view_part_ray(v, pt, ch, off, g).q;
+        const int32_t kb = k0[q.r];
+        for (int64_t s = q.lo + sub; s < q.hi; s += G) {
+            const int32_t k = kb + (int32_t)(s - q.a);
+            float *x = coords + (s - ch.s0) * 3;
+#pragma unroll
+            for (int a = 0; a < 3; ++a)      // (ch.step: the BLOCK grid's step, brief_view_part_step)
+                x[a] = brief_view_part_coord(v, pt, a, ch.step[a], brief_view_part_local(pt, a, brief_view_at(v, a, q.base[a], k)));
+        }
+    }
+}
+
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void k_view_part_fold(brief_view_desc v, brief_view_part pt, ViewChunk ch, const int32_t *__restrict__ k0,
+                                                        const int64_t *__restrict__ off, const T *__restrict__ vals, int C, int32_t *__restrict__ hits,
+                                                        void *__restrict__ acc)
+{
+    typedef typename std::conditional<MODE == 2, long long, int>::type A;
+    const int G = 1 << ch.lg, sub = threadIdx.x & (G - 1);
+    const int64_t groups = ((int64_t)gridDim.x * blockDim.x) >> ch.lg, nr = ch.r1 - ch.r0;
+    const int64_t iters = (nr + groups - 1) / groups;               // the same for every lane: the butterfly below needs the whole group
+    int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> ch.lg;
+    for (int64_t it = 0; it < iters; ++it, g += groups) {
+        const ViewPartRay w = view_part_ray(v, pt, ch, off, g);
+        const ViewRay &q = w.q;
+        const int32_t kb = k0[q.r];
+        int n = 0;
+        A m[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) m[c] = MODE == 1 ? (A)INT32_MAX : (A)0;
+        for (int64_t s = q.lo + sub; s < q.hi; s += G) {
+            const int32_t k = kb + (int32_t)(s - q.a);
+            const float p0 = brief_view_at(v, 0, q.base[0], k), p1 = brief_view_at(v, 1, q.base[1], k), p2 = brief_view_at(v, 2, q.base[2], k);
+            if (!(brief_view_inside(v, p0, p1, p2) && brief_view_part_owned(pt, p0, p1, p2))) continue;
+            ++n;
+            const T *x = vals + (s - ch.s0) * C;
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (c < C) {
+                    const A y = (A)x[c];
+                    m[c] = MODE == 0 ? (y > m[c] ? y : m[c]) : (MODE == 1 ? (y < m[c] ? y : m[c]) : m[c] + y);
+                }
+        }
+        for (int o = G >> 1; o >= 1; o >>= 1) {                      // (G is the launch's: every group of the wave takes the same steps)
+            n += __shfl_xor(n, o);
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (c < C) {
+                    const A y = __shfl_xor(m[c], o);
+                    m[c] = MODE == 0 ? (y > m[c] ? y : m[c]) : (MODE == 1 ? (y < m[c] ? y : m[c]) : m[c] + y);
+                }
+        }
+        if (sub == 0 && n > 0) {                                     // the pixel's owner in this launch
+            hits[w.pixel] += n;
+            A *d = (A *)acc + w.pixel * C;
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (c < C) d[c] = MODE == 0 ? (m[c] > d[c] ? m[c] : d[c]) : (MODE == 1 ? (m[c] < d[c] ? m[c] : d[c]) : d[c] + m[c]);
+        }
+    }
+}
+
+// ---- host side of the partition entries
+static const int64_t kViewPartMaxDim = (int64_t)1 << 23;      // s - 0.5 and e + 0.5 are exact floats below it
+
+static int check_view_part(const brief_view_desc *v, const brief_view_part *pt)
+{
+    if (int rc = check_view(v)) return rc;
+    if (!pt) return fail(BRIEF_ERR_INVALID, "view: null block descriptor");
+    for (int a = 0; a < 3; ++a) {
+        if (v->dims[a] >= kViewPartMaxDim)
+            return fail(BRIEF_ERR_INVALID, "view: a partition needs every axis of the volume below 2^23 (the cell bounds s - 0.5 and e + 0.5 must be exact floats)");
+        if (pt->start[a] < 0 || pt->dims[a] < 2 || pt->start[a] > v->dims[a] - pt->dims[a])
+            return fail(BRIEF_ERR_INVALID, "view: a block needs start >= 0, dims >= 2 and start + dims <= the volume's dims on every axis");
+    }
+    if (pt->row0 < 0 || pt->col0 < 0 || pt->wrows < 1 || pt->wcols < 1 || pt->row0 > v->rows - pt->wrows || pt->col0 > v->cols - pt->wcols)
+        return fail(BRIEF_ERR_INVALID, "view: a block's window must be at least 1 x 1 and lie inside the image rows x cols");
+    return 0;
+}
+
+static int check_view_part_chunk(const brief_view_desc *v, const brief_view_part *pt, const void *k0, const void *off, int64_t s0, int64_t s1, int64_t r0,
+                                 int64_t r1, int32_t lanes, ViewChunk *ch)
+{
+    if (int rc = check_view_part(v, pt)) return rc;
+    if (int rc = check_view_chunk(v, k0, off, s0, s1, 0, 1, lanes, ch)) return rc;
+    if (r0 < 0 || r1 <= r0 || r1 > (int64_t)pt->wrows * pt->wcols) return fail(BRIEF_ERR_INVALID, "view: the ray range must lie inside 0 .. wrows * wcols of the block's window");
+    ch->r0 = r0; ch->r1 = r1;
+    for (int a = 0; a < 3; ++a) ch->step[a] = brief_view_part_step(*v, *pt, a);
+    return 0;
+}
+
+extern "C" {
+
+int brief_view_part_clip(const brief_view_desc *view, const brief_view_part *part, int32_t *k0, int32_t *cnt, void *stream)
+{
+    if (int rc = check_view_part(view, part)) return rc;
+    if (!k0 || !cnt) return fail(BRIEF_ERR_INVALID, "view: null buffer");
+    hipLaunchKernelGGL(k_view_part_clip, dim3(view_blocks((int64_t)part->wrows * part->wcols)), dim3(256), 0, (hipStream_t)stream, *view, *part, k0, cnt);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_view_part_coords(const brief_view_desc *view, const brief_view_part *part, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1,
+                           int64_t r0, int64_t r1, int32_t lanes, float *coords, void *stream)
+{
+    ViewChunk ch;
+    if (int rc = check_view_part_chunk(view, part, k0, off, s0, s1, r0, r1, lanes, &ch)) return rc;
+    if (!coords) return fail(BRIEF_ERR_INVALID, "view: null buffer");
+    hipLaunchKernelGGL(k_view_part_coords, dim3(view_blocks((r1 - r0) << ch.lg)), dim3(256), 0, (hipStream_t)stream, *view, *part, ch, k0, off, coords);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_view_part_fold(const brief_view_desc *view, const brief_view_part *part, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1,
+                         int64_t r0, int64_t r1, int32_t lanes, const void *vals, int elem_kind, int32_t channels, int32_t mode, int32_t *hits,
+                         void *acc, void *stream)
+{
+    ViewChunk ch;
+    if (int rc = check_view_part_chunk(view, part, k0, off, s0, s1, r0, r1, lanes, &ch)) return rc;
+    if (!vals || !hits || !acc) return fail(BRIEF_ERR_INVALID, "view: null buffer");
+    if (elem_kind != BRIEF_OUT_U8 && elem_kind != BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "view: elem_kind must be BRIEF_OUT_U8 (1) or BRIEF_OUT_U16 (2)");
+    if (channels < 1 || channels > 4) return fail(BRIEF_ERR_INVALID, "view: channels must be 1..4");
+    if (mode < BRIEF_VIEW_MAX || mode > BRIEF_VIEW_SLICE) return fail(BRIEF_ERR_INVALID, "view: mode must be BRIEF_VIEW_MAX, _MIN, _MEAN or _SLICE");
+    const dim3 grid(view_blocks((r1 - r0) << ch.lg)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    const int m = mode == BRIEF_VIEW_SLICE ? 0 : mode;      // a slice has at most one sample per ray over ALL blocks: its max is that sample
+#define VIEW_PART_FOLD(T, M) hipLaunchKernelGGL((k_view_part_fold<T, M>), grid, block, 0, st, *view, *part, ch, k0, off, (const T *)vals, (int)channels, hits, acc)
+    if (elem_kind == BRIEF_OUT_U8) {
+        if (m == 0) VIEW_PART_FOLD(uint8_t, 0); else if (m == 1) VIEW_PART_FOLD(uint8_t, 1); else VIEW_PART_FOLD(uint8_t, 2);
+    } else {
+        if (m == 0) VIEW_PART_FOLD(uint16_t, 0); else if (m == 1) VIEW_PART_FOLD(uint16_t, 1); else VIEW_PART_FOLD(uint16_t, 2);
+    }
+#undef VIEW_PART_FOLD
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the same header on the host CPU: no GPU call
+int brief_view_part_clip_host(const brief_view_desc *view, const brief_view_part *part, int32_t *k0, int32_t *cnt)
+{
+    if (int rc = check_view_part(view, part)) return rc;
+    if (!k0 || !cnt) return fail(BRIEF_ERR_INVALID, "view: null buffer");
+    for (int32_t wr = 0; wr < part->wrows; ++wr)
+        for (int32_t wc = 0; wc < part->wcols; ++wc) {
+            const int64_t r = (int64_t)wr * part->wcols + wc;
+            brief_view_part_ray_range(*view, *part, part->row0 + wr, part->col0 + wc, k0[r], cnt[r]);
+        }
+    return 0;
+}
+
+int brief_view_part_sample_host(const brief_view_desc *view, const brief_view_part *part, const int32_t *row, const int32_t *col, const int32_t *k,
+                                int64_t n, float *pos, float *local, float *coord, uint8_t *inside, uint8_t *owned)
+{
+    if (int rc = check_view_part(view, part)) return rc;
+    if (!row || !col || !k || n < 0) return fail(BRIEF_ERR_INVALID, "view: null index buffer or negative count");
+    float step[3];
+    for (int a = 0; a < 3; ++a) step[a] = brief_view_part_step(*view, *part, a);
+    for (int64_t i = 0; i < n; ++i) {
+        if (row[i] < 0 || row[i] >= view->rows || col[i] < 0 || col[i] >= view->cols || k[i] < 0 || k[i] >= view->depth)
+            return fail(BRIEF_ERR_INVALID, "view: a sample index outside rows x cols x depth");
+        float p[3], q[3];
+        for (int a = 0; a < 3; ++a) {
+            p[a] = brief_view_pos(*view, a, row[i], col[i], k[i]);
+            q[a] = brief_view_part_local(*part, a, p[a]);
+        }
+        if (pos) { pos[3 * i] = p[0]; pos[3 * i + 1] = p[1]; pos[3 * i + 2] = p[2]; }
+        if (local) { local[3 * i] = q[0]; local[3 * i + 1] = q[1]; local[3 * i + 2] = q[2]; }
+        if (coord)
+            for (int a = 0; a < 3; ++a) coord[3 * i + a] = brief_view_part_coord(*view, *part, a, step[a], q[a]);
+        if (inside) inside[i] = brief_view_inside(*view, p[0], p[1], p[2]) ? 1 : 0;
+        if (owned) owned[i] = brief_view_part_owned(*part, p[0], p[1], p[2]) ? 1 : 0;
+    }
     return 0;
 }
 

@@ -284,6 +284,13 @@ class NFGR:
         from . import view
         return view.decompress_view(view.open_single(opt, module_path, sideinfos), direction, **kwargs)
 
+    def decompress_divide_view(self, orig_sideinfos_path, module_save_dir, sideinfos_save_dir, direction, opt=None, **kwargs):
+        """the same for a stored DivideTask artefact: a view of the whole volume in which the nearest block owns a sample
+        (view.decompress_divide_view)"""
+        from . import view
+        return view.decompress_divide_view(opt if opt is not None else _wrap(self.opt), orig_sideinfos_path, module_save_dir, sideinfos_save_dir,
+                                           direction, **{"device": self.device, **kwargs})
+
     @staticmethod
     def decompress_surface(opt, module_path, sideinfos, direction, level, **kwargs):
         """the isosurface view of a stored SingleTask artefact as a dict of numpy arrays: per ray of direction `direction` the first
@@ -1036,6 +1043,12 @@ def decompress_divide_mip(opt, orig_sideinfos, module_dir, sideinfos_dir, region
     """the three max-intensity projections of a region of a stored DivideTask artefact (mip.decompress_divide_mip); opt: the whole option tree"""
     from . import mip
     return mip.decompress_divide_mip(opt, orig_sideinfos, module_dir, sideinfos_dir, region, step, device)
+
+
+def decompress_divide_view(opt, orig_sideinfos, module_dir, sideinfos_dir, direction, **kwargs):
+    """an orthographic view of a stored DivideTask artefact, the nearest block owning a sample (view.decompress_divide_view); opt: the whole option tree"""
+    from . import view
+    return view.decompress_divide_view(opt, orig_sideinfos, module_dir, sideinfos_dir, direction, **kwargs)
 
 
 def decompress_divide_gradient(opt, orig_sideinfos, module_dir, sideinfos_dir, region=None, step=1, device="cuda"):

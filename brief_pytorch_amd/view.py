@@ -7,8 +7,12 @@ accumulators on the device (max | min | mean along the ray, or a single plane: s
 The surface view (render_surface, decompress_surface) folds the same march to the FIRST sample of every ray at which a channel
 crosses a level, refines that hit by bisection and shades it with the net's analytic normal (DESIGN.md "Surface view").
 
-make_view is host arithmetic; brief_view_sample_host / brief_view_sample_t_host / brief_view_clip_host restate the device's geometry on the CPU; everything else
-needs a ROCm GPU (there is no CPU fallback)."""
+A view of a DivideTask artefact (render_partition, decompress_divide_view) is the same lattice over the whole volume with one net per
+block: the nearest block owns a sample (DESIGN.md "View decode of a partition").
+
+make_view, part_window and make_part are host arithmetic; brief_view_sample_host / brief_view_sample_t_host / brief_view_clip_host and
+brief_view_part_clip_host / brief_view_part_sample_host restate the device's geometry on the CPU; everything else needs a ROCm GPU
+(there is no CPU fallback)."""
 import ctypes as C
 import math
 import os
@@ -20,8 +24,11 @@ from . import region as region_mod
 
 MODES = ("max", "min", "mean", "slice")
 MAX_COUNT = 1 << 24          # rows, cols and depth travel as floats
-DIVIDE_REFUSAL = ("view decode of a DivideTask artefact is refused: every block has its own net and coordinate grid, and a sample between "
-                  "two blocks has no owner yet (a follow-up will add partitioned artefacts); decode the region and resample it")
+OWNERS = ("nearest",)
+DIVIDE_REFUSAL = ("view decode of a DivideTask artefact is refused unless the ownership rule is named: every block has its own net and "
+                  "coordinate grid, and a sample between two blocks needs an owner; ask for --view-owner nearest "
+                  "(decompress_divide_view: the nearest block owns a sample).  The surface view of a partition is a follow-up")
+PART_MAX_DIM = 1 << 23       # a block's cell bounds s - 0.5 and e + 0.5 are exact floats below it
 
 
 def _vec3(v, what):
@@ -260,6 +267,192 @@ def render(phi, view, mode, lo, hi, out_kind, scale, vrange, chunk=None):
     return image, hits.view(v.rows, v.cols), stats
 
 
+# ---- a view of a partition: the nearest block owns a sample (csrc/brief_view.h "a view of a PARTITION") -------------------------------
+def part_window(view, start, dims):
+    """(row0, col0, wrows, wcols): a rectangle of image rays that holds every ray which can meet the block's cell
+    [start - 0.5, start + dims - 0.5] intersected with the clip box; (0, 0, 0, 0) where that intersection is empty.  Float64: the box's
+    corners are taken through the inverse of (drow, dcol, ddepth); their (row, col) bounding rectangle is the box's shadow along the
+    rays.  It is padded by one pixel plus a bound on what the fp32 roundings of a position (three products, three sums, each half an
+    ulp of at most the largest position) can move a sample across the image, so every ray outside it misses the block exactly."""
+    return tuple(int(x) for x in _windows(view, [start], [dims])[0])
+
+
+def _windows(view, starts, dims):
+    """part_window of many blocks at once: int64 [blocks, 4]"""
+    f = lambda a: np.array(list(a), np.float64)
+    starts, dims = np.asarray(starts, np.float64).reshape(-1, 3), np.asarray(dims, np.float64).reshape(-1, 3)
+    lo, hi = np.maximum(f(view.box_lo), starts - 0.5), np.minimum(f(view.box_hi), starts + dims - 0.5)
+    m = np.stack([f(view.drow), f(view.dcol), f(view.ddepth)], 1)
+    inv = np.linalg.inv(m)
+    upper = np.array([[(i >> a) & 1 for a in range(3)] for i in range(8)], bool)
+    corners = np.where(upper[None], hi[:, None, :], lo[:, None, :])
+    t = (corners - f(view.origin)) @ inv.T
+    reach = np.abs(f(view.origin)) + view.rows * np.abs(m[:, 0]) + view.cols * np.abs(m[:, 1]) + view.depth * np.abs(m[:, 2])
+    pad = 1.0 + np.abs(inv[:2]) @ (8.0 * 2.0 ** -24 * reach)
+    r0, r1 = np.maximum(np.floor(t[..., 0].min(1) - pad[0]), 0), np.minimum(np.ceil(t[..., 0].max(1) + pad[0]), view.rows - 1)
+    c0, c1 = np.maximum(np.floor(t[..., 1].min(1) - pad[1]), 0), np.minimum(np.ceil(t[..., 1].max(1) + pad[1]), view.cols - 1)
+    out = np.stack([r0, c0, r1 - r0 + 1, c1 - c0 + 1], 1)
+    out[(lo > hi).any(1) | (r1 < r0) | (c1 < c0)] = 0
+    return out.astype(np.int64)
+
+
+def make_part(view, start, dims, window=None):
+    """the block descriptor (_lib.ViewPart = brief_view_part) of the block whose first voxel is `start` and whose own grid is `dims`, in
+    the volume view.dims.  window: (row0, col0, wrows, wcols), default part_window's; 'image' is the whole image.  An empty window has
+    wrows == wcols == 0 and is never handed to the library."""
+    start, dims, whole = [int(x) for x in start], [int(x) for x in dims], [int(x) for x in view.dims]
+    if len(start) != 3 or len(dims) != 3:
+        raise ValueError("a block of a view is 3-D: start and dims need three entries (got %r, %r)" % (start, dims))
+    if any(n >= PART_MAX_DIM for n in whole):
+        raise ValueError("a view of a partition is refused for a volume of %s: an axis of 2^23 or more does not keep the cell bounds "
+                         "s - 0.5 and e + 0.5 exact in a float" % (whole,))
+    if any(n < 2 for n in dims):
+        raise ValueError(ENVELOPE["min_axis"][1] % (dims,))
+    if any(s < 0 or s + n > w for s, n, w in zip(start, dims, whole)):
+        raise ValueError("the block at %s of dims %s does not lie inside the volume %s" % (start, dims, whole))
+    pt = _lib.ViewPart()
+    for a in range(3):
+        pt.start[a], pt.dims[a] = start[a], dims[a]
+    if window is None:
+        window = part_window(view, start, dims)
+    elif isinstance(window, str) and window == "image":
+        window = (0, 0, view.rows, view.cols)
+    pt.row0, pt.col0, pt.wrows, pt.wcols = (int(x) for x in window)
+    return pt
+
+
+def part_clip_host(view, part):
+    """(k0 [wrows, wcols], cnt [wrows, wcols]) int32: the samples of every ray of the block's window that the block evaluates (inside
+    the clip box and owned), k0 <= k < k0 + cnt, on the host CPU (brief_view_part_clip_host)"""
+    shape = (part.wrows, part.wcols)
+    k0, cnt = np.zeros(shape, np.int32), np.zeros(shape, np.int32)
+    if k0.size:
+        _lib.check(_lib.lib().brief_view_part_clip_host(C.byref(view), C.byref(part), k0.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p)))
+    return k0, cnt
+
+
+def part_sample_host(view, part, row, col, k):
+    """(pos [n, 3], local [n, 3], coord [n, 3] float32, inside [n], owned [n] bool) of the samples (row, col, k) as the device computes
+    them for the block: the global position, the block-local position q = fl(p - start), the block-local coordinate, the clip box's
+    closed test and the cell's half-open test (brief_view_part_sample_host; the window plays no part)"""
+    row, col, k = (np.ascontiguousarray(x, np.int32).ravel() for x in (row, col, k))
+    n = len(row)
+    if len(col) != n or len(k) != n:
+        raise ValueError("row, col and k must have one entry per sample")
+    pos, local, coord = (np.empty((n, 3), np.float32) for _ in range(3))
+    inside, owned = np.empty(n, np.uint8), np.empty(n, np.uint8)
+    if part.wrows < 1 or part.wcols < 1:
+        part = make_part(view, list(part.start), list(part.dims), "image")
+    p = (lambda a: a.ctypes.data_as(C.c_void_p))
+    _lib.check(_lib.lib().brief_view_part_sample_host(C.byref(view), C.byref(part), p(row), p(col), p(k), n, p(pos), p(local), p(coord), p(inside),
+                                                      p(owned)))
+    return pos, local, coord, inside.astype(bool), owned.astype(bool)
+
+
+def render_partition(parts, view, mode, out_kind, chunk=None):
+    """render for a PARTITION of the grid view.dims: parts is a list of blocks (phi, start, dims, lo, hi, scale, vrange), one net per
+    block on its own linspace grid `dims` over [lo, hi] whose first voxel is `start` in the whole volume, with its own integer
+    epilogue (scale, vrange).  The nearest block owns a sample: a block evaluates exactly the samples inside the clip box whose
+    global position lies in its half-open cell start - 0.5 <= p < start + dims - 0.5, on block-local coordinates (up to half a voxel
+    outside its own grid).  Blocks must not overlap; a sample in a gap no block covers is neither evaluated nor folded.  Returns
+    render's (image, hits, stats); every fold is an integer fold, so the order of the blocks and the chunking change no bit.
+
+    All blocks are clipped first, each over its own WINDOW of rays (part_window), into one block-major array; one scan and one read of
+    the per-block totals follow, then block by block the net's own forward entry on chunks of the block's span (a chunk never spans
+    two blocks) and the fold.  A block whose window or total is empty launches nothing after the clip.  The nets may be of different
+    kinds; their channel count must agree.  Memory: one chunk, the window arrays and the accumulators (and the nets themselves).
+    stats: render's keys over the whole image, plus blocks, blocks_hit (blocks that own a sample) and rays_clipped (the windows' sum)."""
+    import torch
+    from . import mip
+    if mode not in MODES:
+        raise ValueError("view mode %r is not one of %s" % (mode, " | ".join(MODES)))
+    if out_kind not in ("u8", "u16"):
+        raise ValueError("render_partition folds the integer decode only: out_kind must be 'u8' or 'u16' (got %r)" % (out_kind,))
+    if mode == "slice" and view.depth != 1:
+        raise ValueError("mode 'slice' needs a view of one plane (depth 1); this one has %d samples per ray" % view.depth)
+    parts = list(parts)
+    if not parts:
+        raise ValueError("render_partition needs at least one block")
+    ch = int(parts[0][0].data_channel)
+    for phi, *_ in parts:
+        if int(phi.coords_channel) != 3:
+            raise ValueError("a view is defined for 3-D data only (the net takes %d coordinates)" % phi.coords_channel)
+        if int(phi.data_channel) != ch:
+            raise ValueError("the blocks of a view must agree in their channel count (got %d and %d)" % (ch, phi.data_channel))
+    chunk = int(chunk or mip.DEFAULT_CHUNK)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    first = np.array([[int(x) for x in p[1]] for p in parts], np.int64).reshape(len(parts), -1)
+    size = np.array([[int(x) for x in p[2]] for p in parts], np.int64).reshape(len(parts), -1)
+    for i in range(len(parts) - 1):
+        meet = ((first[i] < first[i + 1:] + size[i + 1:]) & (first[i + 1:] < first[i] + size[i])).all(1)
+        if meet.any():
+            raise ValueError("the blocks at %s and %s overlap: a sample there would have two owners"
+                             % (first[i].tolist(), first[i + 1 + int(np.argmax(meet))].tolist()))
+    pts = [make_part(view, s, n, w) for s, n, w in zip(first.tolist(), size.tolist(), _windows(view, first, size).tolist())]
+    for phi, *_ in parts:
+        phi._require_gpu()
+    L, stream = _lib.lib(), _lib.stream_ptr()
+    vs = [_with_range(view, lo, hi) for _, _, _, lo, hi, _, _ in parts]
+    dev = parts[0][0].params.device
+    rays = view.rows * view.cols
+    kind, dt = (_lib.OUT_U8, torch.uint8) if out_kind == "u8" else (_lib.OUT_U16, torch.uint16)
+    m = _lib.VIEW_MODE[mode]
+    hits = torch.zeros(rays, dtype=torch.int32, device=dev)
+    if mode == "mean":
+        acc = torch.zeros((rays, ch), dtype=torch.int64, device=dev)
+    else:
+        acc = torch.full((rays, ch), 0x7FFFFFFF if mode == "min" else 0, dtype=torch.int32, device=dev)
+    sizes = [pt.wrows * pt.wcols for pt in pts]
+    edges = [0]
+    for n in sizes:
+        edges.append(edges[-1] + n)
+    window_rays, evaluated, blocks_hit = edges[-1], 0, 0
+    if window_rays > 0:
+        k0, cnt = torch.empty(window_rays, dtype=torch.int32, device=dev), torch.empty(window_rays, dtype=torch.int32, device=dev)
+        at_ray = lambda t, base: C.c_void_p(t.data_ptr() + t.element_size() * base)      # a block's slice of a window-ray array
+        for v, pt, base, n in zip(vs, pts, edges, sizes):            # the clip needs no net
+            if n:
+                _lib.check(L.brief_view_part_clip(C.byref(v), C.byref(pt), at_ray(k0, base), at_ray(cnt, base), stream))
+        # ONE scan of the counts (and of the hit flags, for the lanes per ray) and ONE read of the per-block totals
+        off = torch.zeros((2, window_rays + 1), dtype=torch.int64, device=dev)
+        torch.cumsum(cnt, 0, dtype=torch.int64, out=off[0, 1:])
+        torch.cumsum(cnt > 0, 0, dtype=torch.int64, out=off[1, 1:])
+        at = off[:, torch.tensor(edges, dtype=torch.int64, device=dev)].cpu().tolist()
+        off = off[0]
+        totals = [b - a for a, b in zip(at[0][:-1], at[0][1:])]
+        hit_rays = [b - a for a, b in zip(at[1][:-1], at[1][1:])]
+        evaluated, blocks_hit = at[0][-1], sum(1 for t in totals if t > 0)
+        if evaluated > 0:
+            # the chunks of every block's span, and the window rays that may hold a sample of each, in ONE search and read
+            plan = [(i, s0, min(s0 + chunk, at[0][i + 1])) for i, t in enumerate(totals) if t > 0 for s0 in range(at[0][i], at[0][i + 1], chunk)]
+            cuts = torch.tensor([[p[1] for p in plan], [p[2] for p in plan]], dtype=torch.int64, device=dev)
+            r0s, r1s = torch.stack([torch.searchsorted(off[1:], cuts[0], right=True),      # the first ray that ends behind s0
+                                    torch.searchsorted(off[:-1], cuts[1], right=False)]).cpu().tolist()      # ... that starts at or behind s1
+            room = min(chunk, max(totals))
+            coords = torch.empty((room, 3), dtype=torch.float32, device=dev)
+            vals = torch.empty((room, ch), dtype=dt, device=dev)
+            p_coords, p_vals, p_hits, p_acc = _lib.ptr(coords), _lib.ptr(vals), _lib.ptr(hits), _lib.ptr(acc)
+            block = -1
+            for (i, s0, s1), r0, r1 in zip(plan, r0s, r1s):
+                if i != block:                                       # the block's net, descriptors and slices, once per block
+                    block, phi, base = i, parts[i][0], edges[i]
+                    phi.sync_packed()
+                    v, pt, k0_b, off_b = C.byref(vs[i]), C.byref(pts[i]), at_ray(k0, base), at_ray(off, base)
+                    lanes = _lanes(totals[i] / hit_rays[i])
+                n = s1 - s0
+                _lib.check(L.brief_view_part_coords(v, pt, k0_b, off_b, s0, s1, r0 - base, r1 - base, lanes, p_coords, stream))
+                b = _lib.BatchDesc(coords.data_ptr(), None, None, None, 0, n, 0, 0, 0)
+                _lib.check(phi._abi_forward(None, b, vals, kind, parts[i][5], parts[i][6], n))
+                _lib.check(L.brief_view_part_fold(v, pt, k0_b, off_b, s0, s1, r0 - base, r1 - base, lanes, p_vals, kind, ch, m, p_hits, p_acc, stream))
+    image = torch.empty((view.rows, view.cols, ch), dtype=torch.float32 if mode == "mean" else dt, device=dev)
+    _lib.check(L.brief_view_finish(C.byref(vs[0]), kind, ch, m, _lib.ptr(hits), _lib.ptr(acc), _lib.ptr(image), stream))
+    rays_hit, inside = torch.stack([(hits > 0).sum(), hits.sum(dtype=torch.int64)]).cpu().tolist()      # (a ray's range is exact: hit <=> hits > 0)
+    stats = {"rays": rays, "rays_hit": rays_hit, "samples_inside": inside, "samples_evaluated": evaluated, "blocks": len(parts),
+             "blocks_hit": blocks_hit, "rays_clipped": window_rays}
+    return image, hits.view(view.rows, view.cols), stats
+
+
 # ---- surface view: first-hit depth, refined, and shaded normals ---------------------------------------------------------------------
 SIDES = ("above", "below")
 MAX_REFINE = 16
@@ -416,6 +609,17 @@ def check_envelope(art, mode):
                          "commute with a mean (denoise.level %s, clip %s); use an identity postprocess" % (pp.denoise.level, list(pp.clip)))
 
 
+def _plane_depth(mode, depth, offset):
+    """make_view's `depth` of a decode: a slice takes its plane's `offset`, every other mode a `depth` range"""
+    if mode == "slice":
+        if depth is not None:
+            raise ValueError("mode 'slice' takes the plane's `offset`, not a `depth` range")
+        return 0.0 if offset is None else float(offset)
+    if offset is not None:
+        raise ValueError("`offset` names the plane of mode 'slice'; mode %r takes a `depth` range" % mode)
+    return depth
+
+
 def decompress_view(art, direction, up=None, mode="max", region=None, centre=None, spacing=1.0, depth_spacing=1.0,
                     size=None, depth=None, offset=None, voxel_size=(1, 1, 1), device="cuda", chunk=None, return_hits=False):
     """an orthographic view of a stored SingleTask artefact (art: open_single's) as a numpy image [rows, cols, channels], without
@@ -429,17 +633,52 @@ def decompress_view(art, direction, up=None, mode="max", region=None, centre=Non
     data, dtypes other than uint8 / uint16, normalisations other than 'minmaxany_a_b', a denoise through a binary opening, an axis
     of length 1.  return_hits: (image, hits [rows, cols] int32, stats) instead of the image."""
     check_envelope(art, mode)
-    if mode == "slice":
-        if depth is not None:
-            raise ValueError("mode 'slice' takes the plane's `offset`, not a `depth` range")
-        depth = 0.0 if offset is None else float(offset)
-    elif offset is not None:
-        raise ValueError("`offset` names the plane of mode 'slice'; mode %r takes a `depth` range" % mode)
+    depth = _plane_depth(mode, depth, offset)
     view = make_view(art.dims, direction, up, centre, spacing, depth_spacing, size, depth, voxel_size, region)
     image, hits, stats = render(art.load_phi(device), view, mode, art.lo, art.hi, art.out_kind, art.norm_range, art.vrange, chunk=chunk)
     img = image.cpu().numpy()
     if mode != "mean":
         img = np.array(art.postprocess_local(img), copy=True)
+        img[hits.cpu().numpy() == 0] = 0                            # (a ray without a sample stays 0 whatever the clip's floor is)
+    return (img, hits.cpu().numpy(), stats) if return_hits else img
+
+
+def decompress_divide_view(opt, orig_sideinfos, module_dir, sideinfos_dir, direction, up=None, mode="max", region=None, centre=None, spacing=1.0,
+                           depth_spacing=1.0, size=None, depth=None, offset=None, voxel_size=(1, 1, 1), device="cuda", chunk=None, return_hits=False):
+    """decompress_view for a stored DivideTask artefact (orig_sideinfos: the job's side info, dict or path; module_dir / sideinfos_dir:
+    the blocks' trees), without decoding the volume or any block: the view is a view of the WHOLE volume, `region` and `centre` index
+    it, and the nearest block owns a sample (render_partition: a sample belongs to the block whose half-open cell, half a voxel
+    around its index range, holds it; the block's net is evaluated up to half a voxel outside its own grid there; nothing is blended
+    across a face).  An axis-aligned view of unit spacing samples voxels only and equals decompress_divide_mip's image / a plane of
+    decompress_divide_region bit for bit.  A sample in a gap no block covers is not evaluated: a ray that meets no block is 0.
+    Decompress.postprocess acts on the image as in decompress_view.  Refused by name before any net is opened: per block everything
+    check_envelope refuses (error-bounded blocks, dtype, normalisation, postprocess, an axis of length 1), blocks of different
+    dtypes or channel counts, overlapping blocks, 2-D data, an axis of 2^23 or more."""
+    from . import config
+    if isinstance(opt, str):
+        opt = config.load(opt)
+    data_shape, blocks = artefact.divide_blocks(orig_sideinfos, module_dir, sideinfos_dir, one_dtype="the view decode")
+    if len(data_shape) != 4:
+        raise ValueError(ENVELOPE["need_3d"] % (len(data_shape) - 1, data_shape))
+    arts = [artefact.open_artefact(opt, b.module_path, b.side) for b in blocks]
+    for art in arts:
+        check_envelope(art, mode)
+    pair = artefact.first_overlap(blocks, "dhw")
+    if pair is not None:
+        raise ValueError("the blocks %s and %s overlap: merge_divided_data adds overlapping blocks, and a sample of a view has one owner; "
+                         "decode the region and resample it" % (pair[0].name, pair[1].name))
+    starts = [[b.ranges[a][0] for a in "dhw"] for b in blocks]
+    for b, art, s in zip(blocks, arts, starts):
+        if art.cout != data_shape[-1] or art.dims != [b.ranges[a][1] - b.ranges[a][0] + 1 for a in "dhw"]:
+            raise ValueError("the block %s holds data of shape %s: not its index range of a volume with %d channels" % (b.name, art.data_shape, data_shape[-1]))
+    depth = _plane_depth(mode, depth, offset)
+    view = make_view(data_shape[:-1], direction, up, centre, spacing, depth_spacing, size, depth, voxel_size, region)
+    make_part(view, starts[0], arts[0].dims, "image")             # (the 2^23 rule, before any net is opened)
+    parts = [(art.load_phi(device), s, art.dims, art.lo, art.hi, art.norm_range, art.vrange) for art, s in zip(arts, starts)]
+    image, hits, stats = render_partition(parts, view, mode, arts[0].out_kind, chunk=chunk)
+    img = image.cpu().numpy()
+    if mode != "mean":
+        img = np.array(arts[0].postprocess_local(img), copy=True)
         img[hits.cpu().numpy() == 0] = 0                            # (a ray without a sample stays 0 whatever the clip's floor is)
     return (img, hits.cpu().numpy(), stats) if return_hits else img
 

@@ -38,6 +38,13 @@ through the volume's centre, `--view-offset` voxels along the direction, at any 
 the clip box are evaluated; the volume is never decoded (SingleTask 3-D uint8 / uint16 artefacts; `mean` writes float32 `.npy` only;
 not with `--mip`, `--gradient`, `--shape` or a `--step` other than 1).
 
+    python decompress.py -p <run yaml> -c <.../compressed of a DivideTask job> --region :,:,: --view dz,dy,dx --view-owner nearest ... -o out.tif
+
+A DivideTask artefact has one net per block, so a sample between two blocks needs an owner: `--view-owner nearest` names the rule (the
+block whose cell, half a voxel around its index range, holds the sample evaluates it; nothing is blended across a face).  The view is
+a view of the whole volume.  Without the option a DivideTask artefact is refused; the option on a SingleTask artefact, without
+`--view`, or with `--view-surface` is refused by name.
+
     python decompress.py -p <run yaml> -c <.../compressed> --region :,:,: --view dz,dy,dx --view-surface LEVEL
         [--view-surface-side above|below] [--view-refine N] [--view-channel C] [--view-light lz,ly,lx] -o out.png|out.tif|out.npy
 
@@ -83,6 +90,9 @@ def main(argv=None):
     ap.add_argument("--view-depth-spacing", type=float, default=1.0, help="distance between the samples of a ray, in voxels (default 1)")
     ap.add_argument("--view-size", default=None, metavar="R,C", help="image size (default: the smallest image that covers the clip box)")
     ap.add_argument("--view-offset", type=float, default=None, help="slice: the plane's offset from the volume's centre along the direction (default 0)")
+    ap.add_argument("--view-owner", default=None, metavar="{nearest}",
+                    help="the rule that gives every sample of a --view of a DivideTask artefact its block: nearest (the block whose cell, half a voxel "
+                         "around its index range, holds the sample); without it a DivideTask artefact is refused")
     ap.add_argument("--view-surface", type=int, default=None, metavar="LEVEL", help="render the isosurface of this grey level of the integer decode: first-hit depth and shaded normals")
     ap.add_argument("--view-surface-side", default=None, help="above (value >= LEVEL, default) | below (value <= LEVEL)")
     ap.add_argument("--view-refine", type=int, default=None, metavar="N", help="rounds of bisection of the hit, 0 .. 16 (default 8)")
@@ -106,6 +116,9 @@ def main(argv=None):
             raise SystemExit("--hessian --shape: resampling is not defined for a DivideTask artefact (every block has its own linspace grid)")
     if args.view is not None:
         _view_refusals(args)          # every refusal by name, before the GPU path is imported
+    elif args.view_owner is not None:
+        raise SystemExit("--view-owner names the rule that gives the samples of a --view of a DivideTask artefact their blocks: give the "
+                         "view's direction with --view dz,dy,dx")
     elif args.view_surface is not None or any(v is not None for v in (args.view_surface_side, args.view_refine, args.view_channel, args.view_light)):
         raise SystemExit("--view-surface / --view-surface-side / --view-refine / --view-channel / --view-light describe the isosurface of a "
                          "--view: give its direction with --view dz,dy,dx")
@@ -201,7 +214,7 @@ def _view_refusals(args):
         if on:
             raise SystemExit("--view with %s: a view is one image of the fitted grid along its own direction (its sampling is set by "
                              "--view-spacing and --view-depth-spacing); ask for one of them" % flag)
-    from brief_pytorch_amd.view import DIVIDE_REFUSAL, MODES
+    from brief_pytorch_amd.view import DIVIDE_REFUSAL, MODES, OWNERS
     if args.view_surface is None:
         for flag, v in (("--view-surface-side", args.view_surface_side), ("--view-refine", args.view_refine), ("--view-channel", args.view_channel),
                         ("--view-light", args.view_light)):
@@ -239,27 +252,39 @@ def _view_refusals(args):
         _floats(args.voxel_size, 3, "--voxel-size")
     if args.view_size is not None:
         _floats(args.view_size, 2, "--view-size")
-    if os.path.isdir(_paths(args.c)[2]):
+    divide = os.path.isdir(_paths(args.c)[2])
+    if args.view_owner is not None:
+        if args.view_owner not in OWNERS:
+            raise SystemExit("--view-owner %s: unknown rule (%s)" % (args.view_owner, ", ".join(OWNERS)))
+        if args.view_surface is not None:
+            raise SystemExit("--view-surface with --view-owner: the isosurface of a DivideTask artefact is refused: the refinement of a hit and its "
+                             "normal need per-point routing between blocks (a bracket can straddle a face); decode the region and render it")
+        if not divide:
+            raise SystemExit("--view-owner %s: the rule chooses among the blocks of a DivideTask artefact, and %s is a SingleTask artefact (one "
+                             "net owns every sample); leave the option out" % (args.view_owner, args.c))
+    elif divide:
         raise SystemExit("--view: " + DIVIDE_REFUSAL)
 
 
 def _view(args, opt, region, divide):
     import numpy as np
     import torch
-    from brief_pytorch_amd.framework import NFGR
+    from brief_pytorch_amd.framework import NFGR, decompress_divide_view
     from brief_pytorch_amd.tool import save_img
     if args.view_surface is not None:
         return _surface(args, opt, region)
-    module, side_path, _ = _paths(args.c)
+    module, side_path, blocks_dir = _paths(args.c)
     t0 = time.perf_counter()
+    kw = dict(up=_floats(args.view_up, 3, "--view-up") if args.view_up is not None else None, mode=args.view_mode, region=region,
+              spacing=args.view_spacing, depth_spacing=args.view_depth_spacing,
+              size=[int(x) for x in _floats(args.view_size, 2, "--view-size")] if args.view_size is not None else None,
+              offset=args.view_offset, voxel_size=_floats(args.voxel_size, 3, "--voxel-size") if args.voxel_size is not None else (1, 1, 1),
+              return_hits=True)
     try:
-        img, hits, stats = NFGR.decompress_view(
-            opt, module, side_path, _floats(args.view, 3, "--view"),
-            up=_floats(args.view_up, 3, "--view-up") if args.view_up is not None else None, mode=args.view_mode, region=region,
-            spacing=args.view_spacing, depth_spacing=args.view_depth_spacing,
-            size=[int(x) for x in _floats(args.view_size, 2, "--view-size")] if args.view_size is not None else None,
-            offset=args.view_offset, voxel_size=_floats(args.voxel_size, 3, "--voxel-size") if args.voxel_size is not None else (1, 1, 1),
-            return_hits=True)
+        if divide:                                                # (--view-owner nearest: _view_refusals refused everything else)
+            img, hits, stats = decompress_divide_view(opt, side_path, module, blocks_dir, _floats(args.view, 3, "--view"), **kw)
+        else:
+            img, hits, stats = NFGR.decompress_view(opt, module, side_path, _floats(args.view, 3, "--view"), **kw)
     except ValueError as e:                                       # a refusal (artefact kind, dtype, normalisation, postprocess, geometry, region)
         raise SystemExit("--view: %s" % e)
     torch.cuda.synchronize()
@@ -268,7 +293,8 @@ def _view(args, opt, region, divide):
         np.save(args.o, img)
     else:
         save_img(args.o, img)
-    print("SingleTask view %s (%s) of region %s: image %s, dtype %s, %d of %d rays hit, %d samples evaluated, decoded in %.3f s -> %s" % (
+    print("%s view %s (%s) of region %s: image %s, dtype %s, %d of %d rays hit, %d samples evaluated, decoded in %.3f s -> %s" % (
+        "DivideTask (%d of %d blocks hit, owner %s)" % (stats["blocks_hit"], stats["blocks"], args.view_owner) if divide else "SingleTask",
         args.view, args.view_mode, args.region, tuple(img.shape), img.dtype, stats["rays_hit"], stats["rays"], stats["samples_evaluated"], dt, args.o))
     return 0
 

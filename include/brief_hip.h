@@ -607,6 +607,44 @@ int brief_view_sample_host(const brief_view_desc *view, const int32_t *row, cons
                            uint8_t *inside);
 int brief_view_clip_host(const brief_view_desc *view, int32_t *k0, int32_t *cnt);
 
+/* ---- view decode of a partition (a DivideTask artefact, one net per block): the nearest block owns a sample (csrc/brief_view.h) ----
+ * The view stays the view of the WHOLE volume (view->dims, positions p_a as above).  A block with the inclusive index range
+ * [start_a, start_a + dims_a - 1] owns the half-open cell start_a - 0.5 <= p_a < start_a + dims_a - 0.5 on every axis; a sample is
+ * evaluated for the block iff it is inside the clip box and owned.  The cells of a tiling partition are disjoint and cover
+ * [-0.5, N - 0.5), and both tests read the global float p_a: every sample inside the clip box has exactly one owner.
+ *     local       q_a = fl(p_a - (float)start_a)
+ *     coordinate  q_a < (float)(dims_a / 2) ? fma(step_a, q_a, lo) : fma(-step_a, (float)(dims_a - 1) - q_a, hi),
+ *                 step_a = (hi - lo) / (float)(dims_a - 1): the BLOCK grid's own coordinate at an integer position, bit for bit; up to
+ *                 half a voxel outside the block's grid for q_a in [-0.5, 0) or (dims_a - 1, dims_a - 0.5).  lo / hi: view->lo / hi.
+ * Only the rays of the block's window [row0, row0 + wrows) x [col0, col0 + wcols) are clipped and walked; WINDOW RAY w is the image
+ * ray (row0 + w / wcols, col0 + w % wcols).  k0, cnt and off are indexed by window ray, hits and acc by image ray:
+ *   brief_view_part_clip    k0[w], cnt[w] (wrows * wcols entries): the samples the block evaluates on window ray w;
+ *   (caller)                off = exclusive scan of cnt (int64, wrows * wcols + 1 entries; it may be a slice of one scan over the
+ *                           windows of all blocks: s0 / s1 below are in off's own numbering);
+ *   brief_view_part_coords  coords[s - s0][3], block-local, for the samples s0 <= s < s1 of the list; [r0, r1) are WINDOW rays;
+ *   brief_view_part_fold    brief_view_fold with the exact test (clip box and cell) on every sample; lane 0 of a ray's group does one
+ *                           plain read-modify-write of the image pixel's hits and acc.  No atomics: within a launch a pixel has one
+ *                           owner, and the launches of a view (all blocks) follow each other on one stream.
+ * brief_view_finish is the finish of a partition as well.  Integers throughout: blocks fold in any order to the same bits.
+ * brief_view_part_clip_host / brief_view_part_sample_host evaluate the same header on the host CPU (pos, local, coord: [n][3]; any
+ * output may be NULL; inside: the clip box's closed test; owned: the cell's half-open test).
+ * Limits, besides those of the view entries: every view->dims below 2^23 (the cell bounds are exact floats); start >= 0, dims >= 2,
+ * start + dims <= view->dims; row0, col0 >= 0, wrows, wcols >= 1, the window inside the image. */
+typedef struct {
+    int64_t start[3];                        /* the block's first voxel in the whole volume */
+    int64_t dims[3];                         /* the block's own grid */
+    int32_t row0, col0, wrows, wcols;        /* the window of image rays that can meet the block */
+} brief_view_part;
+int brief_view_part_clip(const brief_view_desc *view, const brief_view_part *part, int32_t *k0, int32_t *cnt, void *stream);
+int brief_view_part_coords(const brief_view_desc *view, const brief_view_part *part, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1,
+                           int64_t r0, int64_t r1, int32_t lanes, float *coords, void *stream);
+int brief_view_part_fold(const brief_view_desc *view, const brief_view_part *part, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1,
+                         int64_t r0, int64_t r1, int32_t lanes, const void *vals, int elem_kind, int32_t channels, int32_t mode, int32_t *hits,
+                         void *acc, void *stream);
+int brief_view_part_clip_host(const brief_view_desc *view, const brief_view_part *part, int32_t *k0, int32_t *cnt);
+int brief_view_part_sample_host(const brief_view_desc *view, const brief_view_part *part, const int32_t *row, const int32_t *col, const int32_t *k,
+                                int64_t n, float *pos, float *local, float *coord, uint8_t *inside, uint8_t *owned);
+
 /* ---- surface view: first-hit depth, sub-sample refinement and shaded normals of an isosurface (csrc/brief_view.inc) ----------------
  * For every ray of a view: the first inside sample at which channel `channel` of the integer decode passes the side test,
  * value >= level (BRIEF_SURFACE_ABOVE) or value <= level (BRIEF_SURFACE_BELOW); a bisection of that crossing; a Lambert shading from
