@@ -134,7 +134,8 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_surface_fold", "brief_surface_bracket", "brief_surface_coords", "brief_surface_step", "brief_surface_shade",
            "brief_view_sample_t_host",
            "brief_view_part_clip", "brief_view_part_coords", "brief_view_part_fold", "brief_view_part_clip_host", "brief_view_part_sample_host",
-           "brief_siren_hess_forward", "brief_siren_hess_forward_box"] \
+           "brief_siren_hess_forward", "brief_siren_hess_forward_box",
+           "brief_view_composite_fold", "brief_view_composite_finish", "brief_view_composite_host"] \
     + ["brief_%s_%s" % (prefix, entry) for prefix, _, _ in FAMILIES for entry in FAMILY_ENTRIES]
 
 
@@ -269,6 +270,9 @@ def lib():
     L.brief_view_part_fold.argtypes = [wp, pp, vp, vp, i64, i64, i64, i64, i32, vp, C.c_int, i32, i32, vp, vp, vp]
     L.brief_view_part_clip_host.argtypes = [wp, pp, vp, vp]
     L.brief_view_part_sample_host.argtypes = [wp, pp, vp, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.brief_view_composite_fold.argtypes = [wp, vp, vp, i64, i64, i64, i64, i32, vp, C.c_int, i32, i32, vp, i32, vp, vp, vp, vp]
+    L.brief_view_composite_finish.argtypes = [wp, C.POINTER(i32), vp, vp, vp, vp, vp]
+    L.brief_view_composite_host.argtypes = [wp, vp, vp, vp, C.c_int, i32, i32, vp, i32, C.POINTER(i32), vp, vp, vp, vp]
     _LIB = L
     return L
 

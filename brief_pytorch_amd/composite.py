@@ -1,0 +1,258 @@
+"""Composite view of a stored artefact: direct volume rendering through a transfer function, front-to-back emission-absorption
+compositing along the rays of an orthographic view (view.make_view).  The march is the view's: clip, scan, the net's own forward entry
+on the compacted sample list chunk by chunk (view._march); each chunk is folded into per-pixel integer state on the device and
+dropped.  The volume is never decoded.
+
+Compositing is order-dependent, so it is taken to the log domain and to integers (csrc/brief_composite.h; DESIGN.md "Composite view"):
+a sample's optical depth tau and premultiplied emission come from a table, the prefix of tau along the ray is an integer sum, the
+transmittance W of that prefix a pure integer function, and a pixel the uint64 sum of W * emission.  The image does not depend on the
+chunking, on the lanes per ray or on the run, bit for bit.
+
+parse_transfer, make_transfer and check_transfer are host arithmetic; composite_host restates the device's fold on the CPU
+(brief_view_composite_host); everything else needs a ROCm GPU (there is no CPU fallback)."""
+import ctypes as C
+import math
+import os
+
+import numpy as np
+
+from . import _lib
+from . import view as view_mod
+
+TAU_SAT = 32 << 16           # BRIEF_COMPOSITE_TAU_SAT: opaque, in units of 2^-16 octaves
+E_MAX = 65280                # BRIEF_COMPOSITE_E_MAX: 256 * 255
+DEFAULT_BITS = {"u8": 8, "u16": 12}
+DIVIDE_REFUSAL = ("a composite view of a DivideTask artefact is refused: every block has its own net and is evaluated in a pass of its "
+                  "own, and a sample's weight is the transmittance of everything in front of it, a prefix that crosses the blocks of a "
+                  "ray; it needs a second pass over the blocks (a follow-up).  Decode the region and render it, or use --view with "
+                  "--view-owner nearest for a projection")
+
+
+def _kind(out_kind):
+    """('u8' | 'u16', bits of the dtype)"""
+    k = {"u8": "u8", "uint8": "u8", "u16": "u16", "uint16": "u16"}.get(str(out_kind))
+    if k is None:
+        raise ValueError("a composite classifies the integer decode only: out_kind must be 'u8' or 'u16' (got %r)" % (out_kind,))
+    return k, 8 if k == "u8" else 16
+
+
+def parse_transfer(text, out_kind=None):
+    """the control points of a transfer function, [(level, r, g, b, a), ...], from `level:r,g,b,a;level:r,g,b,a;...` or from `@file`
+    holding the same, one point per line or separated by `;`.  level: an integer grey level of the integer decode, strictly ascending
+    (with out_kind: inside that dtype's range, else inside uint16's); r, g, b: 0 .. 255; a in [0, 1]: the opacity accumulated over one
+    physical unit of length."""
+    text = str(text)
+    if text.startswith("@"):
+        path = text[1:]
+        if not os.path.isfile(path):
+            raise ValueError("transfer function file %r does not exist" % path)
+        with open(path) as f:
+            text = f.read()
+    top = 65535 if out_kind is None else (1 << _kind(out_kind)[1]) - 1
+    points = []
+    for part in text.replace("\n", ";").split(";"):
+        part = part.strip()
+        if not part:
+            continue
+        try:
+            level, rest = part.split(":")
+            level = int(level.strip())
+            r, g, b, a = (float(x) for x in rest.split(","))
+        except ValueError:
+            raise ValueError("transfer point %r is not of the form level:r,g,b,a (an integer level, three colours 0 .. 255, an opacity 0 .. 1)"
+                             % part) from None
+        if not 0 <= level <= top:
+            raise ValueError("transfer point %r: level %d lies outside the range of the integer decode, 0 .. %d" % (part, level, top))
+        if points and level <= points[-1][0]:
+            raise ValueError("transfer point %r: levels must be strictly ascending (%d follows %d)" % (part, level, points[-1][0]))
+        if not all(0 <= c <= 255 for c in (r, g, b)):
+            raise ValueError("transfer point %r: a colour must lie in 0 .. 255" % part)
+        if not 0 <= a <= 1:
+            raise ValueError("transfer point %r: the opacity must lie in [0, 1]" % part)
+        points.append((level, r, g, b, a))
+    if not points:
+        raise ValueError("a transfer function needs at least one point level:r,g,b,a")
+    return points
+
+
+def check_transfer(tf, out_kind):
+    """a host-visible table as the kernels expect it: (int32 [2^bits, 4] C-contiguous, bits), every entry in range"""
+    _, width = _kind(out_kind)
+    t = np.ascontiguousarray(tf)
+    if t.dtype != np.int32 or t.ndim != 2 or t.shape[1] != 4:
+        raise ValueError("a transfer table is int32 [2^bits, 4] = (tau, eR, eG, eB) (got %s %s)" % (t.dtype, t.shape))
+    bits = int(t.shape[0]).bit_length() - 1
+    if t.shape[0] != 1 << bits or not 1 <= bits <= width:
+        raise ValueError("a transfer table of %d rows is refused: the rows must be 2^bits, bits 1 .. %d for %s data" % (t.shape[0], width, out_kind))
+    if t[:, 0].min() < 0 or t[:, 0].max() > TAU_SAT:
+        raise ValueError("a transfer table's tau must lie in 0 .. TAU_SAT = %d (got %d .. %d)" % (TAU_SAT, t[:, 0].min(), t[:, 0].max()))
+    if t[:, 1:].min() < 0 or t[:, 1:].max() > E_MAX:
+        raise ValueError("a transfer table's emission must lie in 0 .. %d (got %d .. %d)" % (E_MAX, t[:, 1:].min(), t[:, 1:].max()))
+    return t, bits
+
+
+def make_transfer(points, out_kind, depth_spacing, bits=None):
+    """the table int32 [2^bits, 4] = (tau, eR, eG, eB) of the control points [(level, r, g, b, a), ...] (parse_transfer's) for rays
+    sampled every `depth_spacing` physical units.  Entry i stands for the values i * 2^s .. (i + 1) * 2^s - 1, s = bits of the dtype -
+    bits, and is taken at their middle, i * 2^s + (2^s - 1) / 2.  Colour and opacity are interpolated linearly between the points and
+    constant outside them, in float64.  a is the opacity over one physical unit, so over a sample's step the transmittance is
+    (1 - a)^depth_spacing: tau = rint(-log2(1 - a) * depth_spacing * 65536) clamped to TAU_SAT, a = 1 being TAU_SAT.  The opacity
+    correction for the sample spacing happens here; the kernel stays integer.  e_c = rint(256 * colour_c * (1 - 2^(-tau / 65536))),
+    from the already quantised tau.  bits: default 8 for uint8, 12 for uint16."""
+    kind, width = _kind(out_kind)
+    bits = DEFAULT_BITS[kind] if bits is None else int(bits)
+    if not 1 <= bits <= width:
+        raise ValueError("bits = %d is refused: a transfer table of %s data has 2^bits rows, bits 1 .. %d" % (bits, kind, width))
+    depth_spacing = float(depth_spacing)
+    if not (math.isfinite(depth_spacing) and depth_spacing > 0):
+        raise ValueError("depth_spacing must be a positive finite number (got %r)" % (depth_spacing,))
+    pts = [tuple(p) for p in points]
+    if not pts or any(len(p) != 5 for p in pts):
+        raise ValueError("a transfer function needs at least one point (level, r, g, b, a)")
+    p = np.array(pts, np.float64)
+    top = (1 << width) - 1
+    if (p[:, 0] != np.rint(p[:, 0])).any() or (p[:, 0] < 0).any() or (p[:, 0] > top).any() or (np.diff(p[:, 0]) <= 0).any():
+        raise ValueError("the levels of a transfer function must be integers of the integer decode, 0 .. %d, strictly ascending (got %s)"
+                         % (top, [q[0] for q in pts]))
+    if (p[:, 1:4] < 0).any() or (p[:, 1:4] > 255).any() or (p[:, 4] < 0).any() or (p[:, 4] > 1).any() or not np.isfinite(p).all():
+        raise ValueError("a transfer point's colours must lie in 0 .. 255 and its opacity in [0, 1]")
+    shift = width - bits
+    x = np.arange(1 << bits, dtype=np.float64) * (1 << shift) + ((1 << shift) - 1) / 2.0
+    colour = np.stack([np.interp(x, p[:, 0], p[:, 1 + c]) for c in range(3)], 1)
+    a = np.clip(np.interp(x, p[:, 0], p[:, 4]), 0.0, 1.0)
+    with np.errstate(divide="ignore"):
+        octaves = -np.log2(1.0 - a) * depth_spacing              # (a = 1: inf, clamped below)
+    tau = np.rint(np.minimum(octaves * 65536.0, float(TAU_SAT))).astype(np.int64)
+    alpha = -np.expm1(-tau.astype(np.float64) / 65536.0 * math.log(2.0))
+    tf = np.empty((1 << bits, 4), np.int32)
+    tf[:, 0] = tau
+    tf[:, 1:] = np.rint(256.0 * colour * alpha[:, None])
+    return check_transfer(tf, kind)[0]
+
+
+def composite_host(view, k0, off, vals, tf, channel=0, background=(0, 0, 0)):
+    """the composite of given samples on the host CPU (brief_view_composite_host), no GPU call: (image uint8 [rows, cols, 4], hits int32
+    [rows, cols], tau_run int32 [rows, cols], acc uint64 [rows, cols, 3]).  k0 [rays] int32 and off [rays + 1] int64 are the compacted
+    list (off[0] == 0), vals [off[-1], channels] uint8 | uint16 its values, tf a table of check_transfer's form."""
+    vals = np.ascontiguousarray(vals)
+    if vals.dtype not in (np.uint8, np.uint16) or vals.ndim != 2:
+        raise ValueError("vals must be uint8 or uint16 [samples, channels] (got %s %s)" % (vals.dtype, vals.shape))
+    kind = "u8" if vals.dtype == np.uint8 else "u16"
+    tf, bits = check_transfer(tf, kind)
+    rays = view.rows * view.cols
+    k0, off = np.ascontiguousarray(k0, np.int32).ravel(), np.ascontiguousarray(off, np.int64).ravel()
+    if len(k0) != rays or len(off) != rays + 1:
+        raise ValueError("k0 needs one entry per ray and off one more (%d rays; got %d and %d)" % (rays, len(k0), len(off)))
+    if len(vals) != int(off[-1]):
+        raise ValueError("vals holds %d samples, off names %d" % (len(vals), int(off[-1])))
+    hits, tau_run = np.empty(rays, np.int32), np.empty(rays, np.int32)
+    acc, out = np.empty((rays, 3), np.uint64), np.empty((rays, 4), np.uint8)
+    p = (lambda a: a.ctypes.data_as(C.c_void_p))
+    bg = (C.c_int32 * 3)(*[int(b) for b in background])
+    _lib.check(_lib.lib().brief_view_composite_host(C.byref(view), p(k0), p(off), p(vals), _lib.OUT_U8 if kind == "u8" else _lib.OUT_U16,
+                                                    vals.shape[1], int(channel), p(tf), bits, bg, p(hits), p(tau_run), p(acc), p(out)))
+    shape = (view.rows, view.cols)
+    return out.reshape(*shape, 4), hits.reshape(shape), tau_run.reshape(shape), acc.reshape(*shape, 3)
+
+
+def _background(background):
+    try:
+        bg = [int(b) for b in background]
+        whole = all(float(b) == int(b) for b in background)
+    except (TypeError, ValueError):
+        bg, whole = [], False
+    if len(bg) != 3 or not whole or not all(0 <= b <= 255 for b in bg):
+        raise ValueError("background must be three integers r, g, b in 0 .. 255 (got %r)" % (background,))
+    return bg
+
+
+def render_composite(phi, view, tf, lo, hi, out_kind, scale, vrange, channel=0, background=(0, 0, 0), chunk=None):
+    """the composite view of the net `phi` (any net kind and precision its forward entry serves) on the linspace grid view.dims over
+    [lo, hi]: (image uint8 [rows, cols, 4] = R, G, B, A, hits [rows, cols] int32, stats) as device tensors.  Channel `channel` of the
+    integer decode (out_kind 'u8' | 'u16' with scale / vrange: view.render's) is classified by the table `tf` (make_transfer's: a numpy
+    array, checked here, or an int32 device tensor of the same form, taken as it is) and composited front to back along every ray, in
+    ascending k; RGB is already composited over `background` (0 .. 255 per channel), A is the ray's opacity.  A ray without an inside
+    sample shows the background with A = 0.  Samples are evaluated in chunks of at most `chunk` (default mip.DEFAULT_CHUNK) in the
+    list's order; the image does not depend on it.  stats: view.render's keys."""
+    import torch
+    from . import mip
+    kind_name, width = _kind(out_kind)
+    if int(phi.coords_channel) != 3:
+        raise ValueError("a view is defined for 3-D data only (the net takes %d coordinates)" % phi.coords_channel)
+    ch = int(phi.data_channel)
+    if int(channel) != channel or not 0 <= int(channel) < ch:
+        raise ValueError("channel %r does not exist: the net has the channels 0 .. %d" % (channel, ch - 1))
+    bg = (C.c_int32 * 3)(*_background(background))
+    phi._require_gpu()
+    dev = phi.params.device
+    if isinstance(tf, torch.Tensor):
+        bits = int(tf.shape[0]).bit_length() - 1 if tf.dim() == 2 else 0
+        if tf.dtype != torch.int32 or tf.dim() != 2 or tf.shape[1] != 4 or tf.shape[0] != 1 << bits or not 1 <= bits <= width or not tf.is_contiguous():
+            raise ValueError("a transfer table is a contiguous int32 [2^bits, 4], bits 1 .. %d for %s data (got %s %s)"
+                             % (width, kind_name, tf.dtype, tuple(tf.shape)))
+        table = tf.to(dev)
+    else:
+        t, bits = check_transfer(tf, kind_name)
+        table = torch.from_numpy(t).to(dev)
+    chunk = int(chunk or mip.DEFAULT_CHUNK)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    L, st = _lib.lib(), _lib.stream_ptr
+    v = view_mod._with_range(view, lo, hi)
+    rays = v.rows * v.cols
+    kind, dt = (_lib.OUT_U8, torch.uint8) if kind_name == "u8" else (_lib.OUT_U16, torch.uint16)
+    hits = torch.zeros(rays, dtype=torch.int32, device=dev)
+    tau_run = torch.zeros(rays, dtype=torch.int32, device=dev)
+    acc = torch.zeros((rays, 3), dtype=torch.int64, device=dev)         # (uint64 on the device; below 2^50 under a table of make_transfer)
+
+    def fold(k0, off, s0, s1, r0, r1, lanes, vals):
+        _lib.check(L.brief_view_composite_fold(C.byref(v), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(vals), kind, ch, int(channel),
+                                               _lib.ptr(table), bits, _lib.ptr(hits), _lib.ptr(tau_run), _lib.ptr(acc), st()))
+    _, total, rays_hit = view_mod._march(phi, v, kind, dt, scale, vrange, chunk, fold)
+    image = torch.empty((v.rows, v.cols, 4), dtype=torch.uint8, device=dev)
+    _lib.check(L.brief_view_composite_finish(C.byref(v), bg, _lib.ptr(hits), _lib.ptr(tau_run), _lib.ptr(acc), _lib.ptr(image), st()))
+    stats = {"rays": rays, "rays_hit": rays_hit, "samples_inside": int(hits.sum(dtype=torch.int64).item()), "samples_evaluated": total}
+    return image, hits.view(v.rows, v.cols), stats
+
+
+def open_single(opt, module_path, sideinfos):
+    """view.open_single for the composite: a DivideTask artefact is refused in the composite's own words before any net is opened"""
+    from .io import load_yaml
+    if isinstance(sideinfos, str):
+        sideinfos = load_yaml(sideinfos)
+    if "phi_features" not in sideinfos or os.path.isdir(os.path.join(os.path.dirname(str(module_path)), "sideinfos")):
+        raise ValueError(DIVIDE_REFUSAL)
+    return view_mod.open_single(opt, module_path, sideinfos)
+
+
+def decompress_composite(art, direction, transfer, up=None, region=None, centre=None, spacing=1.0, depth_spacing=1.0, size=None, depth=None,
+                         voxel_size=(1, 1, 1), channel=0, background=(0, 0, 0), bits=None, device="cuda", chunk=None, return_hits=False):
+    """the composite view of a stored SingleTask artefact (art: open_single's) as a numpy image uint8 [rows, cols, 4] = R, G, B, A, without
+    decoding the volume.  The geometry arguments are view.make_view's; `region` is the clip box.
+
+    transfer: the transfer function, as text (parse_transfer: 'level:r,g,b,a;...' or '@file') or as a list of points (level, r, g, b,
+    a).  Its levels are grey levels of the artefact's INTEGER DECODE (uint8 / uint16 after the fused de-normalisation), BEFORE
+    Decompress.postprocess, as for the surface view; a is the opacity over one physical unit, corrected for depth_spacing in
+    make_transfer (bits: the table's size, default 8 for uint8, 12 for uint16).  A Decompress.postprocess that changes values is
+    refused: a threshold or a clip would have to act on every sample before its classification, and the samples are never held.
+    Refused by name before any decode: everything view.check_envelope refuses (error-bounded artefacts, 2-D data, dtype,
+    normalisation, an axis of length 1), a non-identity postprocess, a channel that does not exist, a background outside 0 .. 255, a
+    malformed transfer function; DivideTask artefacts by open_single.  return_hits: (image, hits [rows, cols] int32, stats)."""
+    from .misc import preprocess_is_identity
+    view_mod.check_envelope(art, "max")
+    pp = art.postprocess
+    if not preprocess_is_identity(np.zeros(1, np.dtype(art.dtype)), pp.denoise.level, pp.denoise.close, pp.clip):
+        raise ValueError("a composite view with a Decompress.postprocess that changes values is refused: the transfer function classifies "
+                         "the integer decode of every sample, and a threshold or a clip (denoise.level %s, clip %s) does not commute with "
+                         "the compositing; use an identity postprocess and put the threshold into the transfer function"
+                         % (pp.denoise.level, list(pp.clip)))
+    if int(channel) != channel or not 0 <= int(channel) < int(art.cout):
+        raise ValueError("channel %r does not exist: the artefact has the channels 0 .. %d" % (channel, int(art.cout) - 1))
+    _background(background)
+    points = parse_transfer(transfer, art.out_kind) if isinstance(transfer, str) else transfer
+    tf = make_transfer(points, art.out_kind, depth_spacing, bits)
+    view = view_mod.make_view(art.dims, direction, up, centre, spacing, depth_spacing, size, depth, voxel_size, region)
+    image, hits, stats = render_composite(art.load_phi(device), view, tf, art.lo, art.hi, art.out_kind, art.norm_range, art.vrange,
+                                          channel=int(channel), background=background, chunk=chunk)
+    img = image.cpu().numpy()
+    return (img, hits.cpu().numpy(), stats) if return_hits else img

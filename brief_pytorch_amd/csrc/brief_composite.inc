@@ -1,0 +1,208 @@
+// brief_composite.inc — composite view: front-to-back emission-absorption rendering through a transfer table, k_composite_fold and
+// k_composite_finish and their C-ABI entries brief_view_composite_* (part of the single translation unit brief_hip.hip, included at its
+// very end: kernels and host code of a feature that touches no other kernel).  The arithmetic is csrc/brief_composite.h, compiled here
+// for the device and for brief_view_composite_host alike; clip, scan, coordinates and the list layout are the view's (brief_view.inc).
+//
+//   k_composite_fold    k_view_fold's walk: a ray belongs to a group of G = 2^lg adjacent lanes, and in every PASS the group touches G
+//                       consecutive samples of the ray-major list.  Per pass a lane loads its sample's value, looks (tau, eR, eG, eB) up,
+//                       the group takes an inclusive scan of tau over its lanes (lg shuffles of width G), adds the ray's running carry
+//                       to get the saturated exclusive prefix P_i, and adds W(P_i) * e_c to three uint64 sums of its own; the carry
+//                       advances by the pass's total.  After the passes the sums are butterflied over the group and lane 0 does one
+//                       plain read-modify-write of the pixel's state: tau_run[r] (the saturated running optical depth, which is also the
+//                       carry-in of the ray's next chunk), acc[r][3] and hits[r].
+//   k_composite_finish  the RGBA image from that state (brief_composite_pixel).
+// No atomics: within a launch a pixel has one owner.  The chunks of a view follow the list's order on one stream, so the earlier part
+// of a ray is always folded first and tau_run[r] is the prefix of everything before the chunk.  Every sum is an integer sum, and
+// the prefix a sample gets depends on its place along the ray alone: the image does not depend on G, on the chunking or on the run.
+//
+// The table is read through the cache with plain 16-byte loads, whatever its size (4 KiB for a uint8 table, 64 KiB at the default
+// b = 12 of uint16, 1 MiB at b = 16).  A copy of a small table in LDS, gathered there, was measured against this and bought nothing
+// (profiles/r20_composite.md: 1.58 against 1.59 ms behind a 4x22 net, inside the spread), so there is one path.
+#include "brief_composite.h"
+
+struct CompositeTable { int32_t channel, shift; };      // index = value[channel] >> shift: below 2^tf_bits for every value of the dtype
+struct CompositeBg { int32_t c[3]; };
+
+__device__ __forceinline__ unsigned long long composite_shfl_xor(unsigned long long x, int o)
+{
+    return (unsigned long long)__shfl_xor((long long)x, o);
+}
+
+// hits: int32 [rays], tau_run: int32 [rays], acc: uint64 [rays][3], all caller-initialised to 0
+template <typename T>
+__global__ __launch_bounds__(256) void k_composite_fold(brief_view_desc v, ViewChunk ch, const int32_t *__restrict__ k0, const int64_t *__restrict__ off,
+                                                        const T *__restrict__ vals, int C, CompositeTable tb, const int4 *__restrict__ tf,
+                                                        int32_t *__restrict__ hits, int32_t *__restrict__ tau_run,
+                                                        unsigned long long *__restrict__ acc)
+{
+    const int G = 1 << ch.lg, sub = threadIdx.x & (G - 1);
+    const int64_t groups = ((int64_t)gridDim.x * blockDim.x) >> ch.lg, nr = ch.r1 - ch.r0;
+    const int64_t iters = (nr + groups - 1) / groups;               // the same for every lane: the butterfly below needs the whole group
+    int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> ch.lg;
+    for (int64_t it = 0; it < iters; ++it, g += groups) {
+        const ViewRay q = view_ray(v, ch, off, g);
+        const int32_t kb = k0[q.r];
+        uint32_t carry = (uint32_t)tau_run[q.r];                     // (read by the whole group before its lane 0 writes it, below)
+        int n = 0;
+        unsigned long long m[3] = {0, 0, 0};
+        for (int64_t sb = q.lo; sb < q.hi; sb += G) {                // a pass; q.lo and q.hi are the group's: its lanes stay together
+            const int64_t s = sb + sub;
+            int4 e = make_int4(0, 0, 0, 0);
+            if (s < q.hi) {
+                const int32_t k = kb + (int32_t)(s - q.a);
+                if (brief_view_inside(v, brief_view_at(v, 0, q.base[0], k), brief_view_at(v, 1, q.base[1], k), brief_view_at(v, 2, q.base[2], k))) {
+                    ++n;
+                    e = tf[(int)vals[(s - ch.s0) * C + tb.channel] >> tb.shift];
+                }
+            }
+            uint32_t incl = (uint32_t)e.x;                           // at most G * TAU_SAT <= 2^27: no overflow before the saturation
+            for (int o = 1; o < G; o <<= 1) {
+                const uint32_t y = (uint32_t)__shfl_up((int)incl, o, G);
+                if (sub >= o) incl += y;
+            }
+            const unsigned long long w = brief_composite_w(brief_composite_add(carry, incl - (uint32_t)e.x));
+            m[0] += w * (unsigned long long)(uint32_t)e.y;
+            m[1] += w * (unsigned long long)(uint32_t)e.z;
+            m[2] += w * (unsigned long long)(uint32_t)e.w;
+            carry = brief_composite_add(carry, (uint32_t)__shfl((int)incl, G - 1, G));
+        }
+        for (int o = G >> 1; o >= 1; o >>= 1) {                      // (G is the launch's: every group of the wave takes the same steps)
+            n += __shfl_xor(n, o);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) m[c] += composite_shfl_xor(m[c], o);
+        }
+        if (sub == 0 && n > 0) {                                     // the pixel's owner
+            hits[q.r] += n;
+            tau_run[q.r] = (int32_t)carry;
+            unsigned long long *d = acc + q.r * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) d[c] += m[c];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_composite_finish(int64_t rays, CompositeBg bg, const int32_t *__restrict__ tau_run,
+                                                          const unsigned long long *__restrict__ acc, uchar4 *__restrict__ out)
+{
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rays; r += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t a[3] = {acc[r * 3], acc[r * 3 + 1], acc[r * 3 + 2]};
+        uint8_t px[4];
+        brief_composite_pixel((uint32_t)tau_run[r], a, bg.c, px);
+        out[r] = make_uchar4(px[0], px[1], px[2], px[3]);
+    }
+}
+
+// ---- host side
+static int check_composite_table(int elem_kind, int32_t channels, int32_t channel, const void *tf, int32_t tf_bits, CompositeTable *tb)
+{
+    if (elem_kind != BRIEF_OUT_U8 && elem_kind != BRIEF_OUT_U16) return fail(BRIEF_ERR_INVALID, "composite: elem_kind must be BRIEF_OUT_U8 (1) or BRIEF_OUT_U16 (2)");
+    if (channels < 1 || channels > 4) return fail(BRIEF_ERR_INVALID, "composite: channels must be 1..4");
+    if (channel < 0 || channel >= channels) return fail(BRIEF_ERR_INVALID, "composite: channel must be 0 .. channels - 1");
+    if (!tf) return fail(BRIEF_ERR_INVALID, "composite: null transfer table");
+    if ((uintptr_t)tf & 15) return fail(BRIEF_ERR_INVALID, "composite: the transfer table must be 16-byte aligned (an entry is read as one int4)");
+    const int bits = elem_kind == BRIEF_OUT_U8 ? 8 : 16;
+    if (tf_bits < 1 || tf_bits > bits) return fail(BRIEF_ERR_INVALID, "composite: tf_bits must be 1 .. 8 for uint8 and 1 .. 16 for uint16");
+    tb->channel = channel; tb->shift = bits - tf_bits;
+    return 0;
+}
+
+static int check_composite_bg(const int32_t *background, CompositeBg *bg)
+{
+    if (!background) return fail(BRIEF_ERR_INVALID, "composite: null background");
+    for (int c = 0; c < 3; ++c) {
+        if (background[c] < 0 || background[c] > 255) return fail(BRIEF_ERR_INVALID, "composite: background must be 0 .. 255 per channel");
+        bg->c[c] = background[c];
+    }
+    return 0;
+}
+
+extern "C" {
+
+int brief_view_composite_fold(const brief_view_desc *view, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1, int64_t r0, int64_t r1,
+                              int32_t lanes, const void *vals, int elem_kind, int32_t channels, int32_t channel, const int32_t *tf, int32_t tf_bits,
+                              int32_t *hits, int32_t *tau_run, uint64_t *acc, void *stream)
+{
+    ViewChunk ch;
+    CompositeTable tb;
+    if (int rc = check_view_chunk(view, k0, off, s0, s1, r0, r1, lanes, &ch)) return rc;
+    if (!vals || !hits || !tau_run || !acc) return fail(BRIEF_ERR_INVALID, "composite: null buffer");
+    if (int rc = check_composite_table(elem_kind, channels, channel, tf, tf_bits, &tb)) return rc;
+    const dim3 grid(view_blocks((r1 - r0) << ch.lg)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define COMPOSITE_FOLD(T) hipLaunchKernelGGL((k_composite_fold<T>), grid, block, 0, st, *view, ch, k0, off, (const T *)vals, (int)channels, tb, \
+                                             (const int4 *)tf, hits, tau_run, (unsigned long long *)acc)
+    if (elem_kind == BRIEF_OUT_U8) COMPOSITE_FOLD(uint8_t); else COMPOSITE_FOLD(uint16_t);
+#undef COMPOSITE_FOLD
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_view_composite_finish(const brief_view_desc *view, const int32_t *background, const int32_t *hits, const int32_t *tau_run, const uint64_t *acc,
+                                uint8_t *out, void *stream)
+{
+    CompositeBg bg;
+    if (int rc = check_view(view)) return rc;
+    if (!hits || !tau_run || !acc || !out) return fail(BRIEF_ERR_INVALID, "composite: null buffer");
+    if ((uintptr_t)out & 3) return fail(BRIEF_ERR_INVALID, "composite: the image must be 4-byte aligned (a pixel is written as one uchar4)");
+    if (int rc = check_composite_bg(background, &bg)) return rc;
+    const int64_t rays = (int64_t)view->rows * view->cols;
+    if (rays > kViewMaxRays) return fail(BRIEF_ERR_INVALID, "view: more than 2^40 rays");
+    hipLaunchKernelGGL(k_composite_finish, dim3(view_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rays, bg, tau_run,
+                       (const unsigned long long *)acc, (uchar4 *)out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the same fold and finish on the host CPU, sample after sample: no GPU call.  Every buffer is host memory; vals holds the WHOLE list.
+int brief_view_composite_host(const brief_view_desc *view, const int32_t *k0, const int64_t *off, const void *vals, int elem_kind, int32_t channels,
+                              int32_t channel, const int32_t *tf, int32_t tf_bits, const int32_t *background, int32_t *hits, int32_t *tau_run,
+                              uint64_t *acc, uint8_t *out)
+{
+    CompositeTable tb;
+    CompositeBg bg;
+    if (int rc = check_view(view)) return rc;
+    if (!k0 || !off || !vals || !out) return fail(BRIEF_ERR_INVALID, "composite: null buffer (hits, tau_run and acc alone may be NULL)");
+    if (int rc = check_composite_table(elem_kind, channels, channel, tf, tf_bits, &tb)) return rc;
+    if (int rc = check_composite_bg(background, &bg)) return rc;
+    for (int32_t i = 0; i < (int32_t)1 << tf_bits; ++i) {
+        const int32_t *e = tf + 4 * (int64_t)i;
+        if (e[0] < 0 || e[0] > BRIEF_COMPOSITE_TAU_SAT) return fail(BRIEF_ERR_INVALID, "composite: a table entry's tau lies outside 0 .. TAU_SAT (32 * 65536)");
+        for (int c = 1; c < 4; ++c)
+            if (e[c] < 0 || e[c] > BRIEF_COMPOSITE_E_MAX) return fail(BRIEF_ERR_INVALID, "composite: a table entry's emission lies outside 0 .. 65280");
+    }
+    const int64_t rays = (int64_t)view->rows * view->cols;
+    if (off[0] != 0) return fail(BRIEF_ERR_INVALID, "composite: off[0] must be 0 (vals holds the whole list)");
+    for (int64_t r = 0; r < rays; ++r) {
+        const int64_t cnt = off[r + 1] - off[r];
+        if (cnt < 0 || k0[r] < 0 || cnt > (int64_t)view->depth - k0[r])
+            return fail(BRIEF_ERR_INVALID, "composite: off must not decrease, and a ray's samples k0 .. k0 + cnt - 1 must lie inside 0 .. depth - 1");
+    }
+    for (int64_t r = 0; r < rays; ++r) {
+        const int32_t row = (int32_t)(r / view->cols), col = (int32_t)(r - (int64_t)row * view->cols);
+        float base[3];
+        for (int a = 0; a < 3; ++a) base[a] = brief_view_base(*view, a, row, col);
+        uint32_t run = 0;
+        uint64_t sum[3] = {0, 0, 0};
+        int32_t n = 0;
+        for (int64_t s = off[r]; s < off[r + 1]; ++s) {
+            const int32_t k = k0[r] + (int32_t)(s - off[r]);
+            if (!brief_view_inside(*view, brief_view_at(*view, 0, base[0], k), brief_view_at(*view, 1, base[1], k), brief_view_at(*view, 2, base[2], k)))
+                continue;
+            ++n;
+            const int64_t at = s * channels + channel;
+            const int value = elem_kind == BRIEF_OUT_U8 ? (int)((const uint8_t *)vals)[at] : (int)((const uint16_t *)vals)[at];
+            const int32_t *e = tf + 4 * (int64_t)(value >> tb.shift);
+            const uint64_t w = brief_composite_w(run);
+            for (int c = 0; c < 3; ++c) sum[c] += w * (uint64_t)e[1 + c];
+            run = brief_composite_add(run, (uint32_t)e[0]);
+        }
+        if (hits) hits[r] = n;
+        if (tau_run) tau_run[r] = (int32_t)run;
+        if (acc)
+            for (int c = 0; c < 3; ++c) acc[r * 3 + c] = sum[c];
+        brief_composite_pixel(run, sum, bg.c, out + r * 4);
+    }
+    return 0;
+}
+
+}   // extern "C"

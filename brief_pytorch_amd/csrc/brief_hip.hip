@@ -41,6 +41,7 @@
 //   brief_quant.inc    k_quant_minmax / k_quant_fold / k_quant_apply / k_quant_decode: the 2..16-bit weight quantiser of the quantised artefact.
 //   brief_jac.inc      k_jac_fwd / k_jac_repack: value and analytic Jacobian of an fp32 SIREN with respect to the coordinates (host: brief_jac_host.inc).
 //   brief_view.inc     k_view_clip / k_view_coords / k_view_fold / k_view_finish: oblique slices and projections along any direction (geometry: brief_view.h).
+//   brief_composite.inc  k_composite_fold / k_composite_finish: emission-absorption rendering of a view through a transfer table, in integers (arithmetic: brief_composite.h).
 //   brief_hess.inc     k_hess_fwd: value, Jacobian and analytic Hessian of an fp32 SIREN with respect to the coordinates (second-order forward mode; host entries in the same file).
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -1777,3 +1778,4 @@ int brief_quant_decode(const uint16_t *codes, const brief_quant_span *tensors, i
 #include "brief_jac_host.inc"         // spatial-gradient decode: brief_siren_jac_* (named last: its kernels are the last ones instantiated)
 #include "brief_view.inc"             // orthographic view decode: kernels and entries of their own, behind everything else (the kernels above keep their order)
 #include "brief_hess.inc"             // Hessian decode: k_hess_fwd and brief_siren_hess_forward / _forward_box, behind the view kernels (the kernels above keep their order)
+#include "brief_composite.inc"        // composite view: k_composite_fold / k_composite_finish and brief_view_composite_*, behind everything else (the kernels above keep their order)

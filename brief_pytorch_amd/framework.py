@@ -300,6 +300,15 @@ class NFGR:
         from . import view
         return view.decompress_surface(view.open_single(opt, module_path, sideinfos), direction, level, **kwargs)
 
+    @staticmethod
+    def decompress_composite(opt, module_path, sideinfos, direction, transfer, **kwargs):
+        """the composite view of a stored SingleTask artefact as a numpy image uint8 [rows, cols, 4] = R, G, B, A: direct volume rendering
+        along `direction` through the transfer function `transfer` ('level:r,g,b,a;...', '@file' or a list of points; levels are grey
+        levels BEFORE Decompress.postprocess), front-to-back emission-absorption compositing in integers, so the image does not depend
+        on chunking or run.  The volume is never decoded.  composite.decompress_composite has the arguments and the envelope."""
+        from . import composite
+        return composite.decompress_composite(composite.open_single(opt, module_path, sideinfos), direction, transfer, **kwargs)
+
     # ---- spatial-gradient decode: the analytic Jacobian of the stored net in grey levels per voxel (brief_pytorch_amd/gradient.py)
     @staticmethod
     def decompress_gradient(opt, module_path, sideinfos, region=None, step=1, shape=None, device="cuda"):

@@ -55,6 +55,16 @@ integer decode, before `Decompress.postprocess`.  `.png` / `.tif` hold the shade
 float32 [rows, cols, 5] = depth, normal (z, y, x), shade, with NaN depth where no ray hits.  Artefacts other than an fp32 SIREN up to
 1024 features have no analytic normal: `.npy` then holds the depth alone, [rows, cols], and an image output is refused by name (the
 view options that shape the geometry apply; not with `--view-mode` or `--view-offset`).
+
+    python decompress.py -p <run yaml> -c <.../compressed> --region :,:,: --view dz,dy,dx --view-composite 'L:r,g,b,a;L:r,g,b,a;...'|@file
+        [--view-composite-channel C] [--view-background r,g,b] [--view-composite-bits B] -o out.png|out.npy
+
+`--view-composite SPEC` renders the view through a TRANSFER FUNCTION instead: every sample of a ray is classified by channel C of the
+integer decode (control points `level:r,g,b,a`, levels strictly ascending and before `Decompress.postprocess`, colours 0 .. 255, `a` the
+opacity over one voxel of depth; linear between the points, constant outside) and composited front to back over `--view-background`,
+in integers: the image does not depend on the chunking or the run.  `.png` holds R,G,B, `.npy` uint8 [rows, cols, 4] = R,G,B,A
+(SingleTask artefacts with an identity postprocess; the view options that shape the geometry apply; not with `--view-mode`,
+`--view-offset`, `--view-surface...`, `--view-owner`, `--mip`, `--gradient`, `--hessian`, `--shape` or `--step`).
 """
 import argparse
 import os
@@ -98,9 +108,16 @@ def main(argv=None):
     ap.add_argument("--view-refine", type=int, default=None, metavar="N", help="rounds of bisection of the hit, 0 .. 16 (default 8)")
     ap.add_argument("--view-channel", type=int, default=None, metavar="C", help="the channel the level is tested on (default 0)")
     ap.add_argument("--view-light", default=None, metavar="lz,ly,lx", help="the physical direction the light travels (default: the view direction)")
+    ap.add_argument("--view-composite", default=None, metavar="SPEC",
+                    help="render the view through a transfer function, level:r,g,b,a;level:r,g,b,a;... or @file: front-to-back emission-absorption compositing")
+    ap.add_argument("--view-composite-channel", type=int, default=None, metavar="C", help="the channel the transfer function classifies (default 0)")
+    ap.add_argument("--view-background", default=None, metavar="r,g,b", help="the colour behind the composite, 0 .. 255 each (default 0,0,0)")
+    ap.add_argument("--view-composite-bits", type=int, default=None, metavar="B", help="the transfer table has 2^B rows (default 8 for uint8, 12 for uint16)")
     ap.add_argument("--voxel-size", default=None, metavar="sz,sy,sx", help="physical extent of a voxel per axis (default 1,1,1)")
     ap.add_argument("-o", required=True, help="output file (.tif / .tiff / .npy / .png / .jpg)")
     args = ap.parse_args(argv)
+    if any(v is not None for v in (args.view_composite, args.view_composite_channel, args.view_background, args.view_composite_bits)):
+        _composite_refusals(args)     # every refusal by name, before the GPU path is imported
     if args.hessian is not None:
         # every refusal by name, before the GPU path is imported
         if args.hessian not in ("components", "laplacian", "eigenvalues", "vesselness"):
@@ -273,6 +290,8 @@ def _view(args, opt, region, divide):
     from brief_pytorch_amd.tool import save_img
     if args.view_surface is not None:
         return _surface(args, opt, region)
+    if args.view_composite is not None:
+        return _composite(args, opt, region)
     module, side_path, blocks_dir = _paths(args.c)
     t0 = time.perf_counter()
     kw = dict(up=_floats(args.view_up, 3, "--view-up") if args.view_up is not None else None, mode=args.view_mode, region=region,
@@ -338,6 +357,77 @@ def _surface(args, opt, region):
           "%d samples evaluated, %d refinement points, decoded in %.3f s -> %s" % (
               args.view, args.view_surface, args.view_surface_side or "above", args.region, "image" if not npy else "array", tuple(data.shape),
               data.dtype, stats["rays_surface"], stats["rays"], stats["rays_cut"], stats["samples_evaluated"], stats["refine_points"], dt, args.o))
+    return 0
+
+
+def _composite_refusals(args):
+    if args.view_composite is None:
+        raise SystemExit("--view-composite-channel / --view-background / --view-composite-bits describe a composite: give its transfer function "
+                         "with --view-composite SPEC")
+    if args.view is None:
+        raise SystemExit("--view-composite renders a --view through a transfer function: give the view's direction with --view dz,dy,dx")
+    for flag, on in (("--view-mode %s" % args.view_mode, args.view_mode != "max"), ("--view-offset", args.view_offset is not None),
+                     ("--view-surface", args.view_surface is not None), ("--view-surface-side", args.view_surface_side is not None),
+                     ("--view-refine", args.view_refine is not None), ("--view-channel", args.view_channel is not None),
+                     ("--view-light", args.view_light is not None), ("--view-owner", args.view_owner is not None), ("--mip", args.mip),
+                     ("--gradient", args.gradient is not None), ("--hessian", args.hessian is not None), ("--shape", args.shape is not None),
+                     ("--step %d" % args.step, args.step != 1)):
+        if on:
+            raise SystemExit("--view-composite with %s: a composite is a view of its own (every sample of a ray, classified by the transfer "
+                             "function and composited front to back; its channel is --view-composite-channel); ask for one of them" % flag)
+    ext = os.path.splitext(args.o)[1].lower()
+    if ext not in (".png", ".npy"):
+        raise SystemExit("--view-composite writes an RGB image as .png or the RGBA array as .npy (got %s): the .tif writer holds one channel "
+                         "per page, and no other format is supported" % (ext or "no extension"))
+    from brief_pytorch_amd import composite
+    try:
+        composite.parse_transfer(args.view_composite)
+        if args.view_background is not None:
+            composite._background(_floats(args.view_background, 3, "--view-background"))
+    except ValueError as e:
+        raise SystemExit("--view-composite: %s" % e)
+    if args.view_composite_channel is not None and args.view_composite_channel < 0:
+        raise SystemExit("--view-composite-channel %d: a channel is 0 or above" % args.view_composite_channel)
+    if args.view_composite_bits is not None and not 1 <= args.view_composite_bits <= 16:
+        raise SystemExit("--view-composite-bits %d: the transfer table has 2^B rows, B 1 .. 8 for uint8 and 1 .. 16 for uint16" % args.view_composite_bits)
+    if os.path.isdir(_paths(args.c)[2]):
+        raise SystemExit("--view-composite: " + composite.DIVIDE_REFUSAL)
+
+
+def _write_rgb_png(path, rgb):
+    """uint8 [rows, cols, 3] = R, G, B into a PNG whose bytes are R, G, B: tool.write_png takes cv2's B, G, R (and read_png hands it back)"""
+    from brief_pytorch_amd.tool import write_png
+    write_png(path, rgb[..., ::-1])
+
+
+def _composite(args, opt, region):
+    import numpy as np
+    import torch
+    from brief_pytorch_amd.framework import NFGR
+    module, side_path, _ = _paths(args.c)
+    t0 = time.perf_counter()
+    try:
+        img, hits, stats = NFGR.decompress_composite(
+            opt, module, side_path, _floats(args.view, 3, "--view"), args.view_composite,
+            up=_floats(args.view_up, 3, "--view-up") if args.view_up is not None else None, region=region,
+            spacing=args.view_spacing, depth_spacing=args.view_depth_spacing,
+            size=[int(x) for x in _floats(args.view_size, 2, "--view-size")] if args.view_size is not None else None,
+            voxel_size=_floats(args.voxel_size, 3, "--voxel-size") if args.voxel_size is not None else (1, 1, 1),
+            channel=args.view_composite_channel or 0,
+            background=_floats(args.view_background, 3, "--view-background") if args.view_background is not None else (0, 0, 0),
+            bits=args.view_composite_bits, return_hits=True)
+    except ValueError as e:                                       # a refusal (artefact kind, dtype, normalisation, postprocess, transfer, geometry)
+        raise SystemExit("--view-composite: %s" % e)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    if os.path.splitext(args.o)[1].lower() == ".npy":
+        data = img
+        np.save(args.o, data)
+    else:
+        data = np.ascontiguousarray(img[..., :3])
+        _write_rgb_png(args.o, data)
+    print("SingleTask composite view %s of region %s: image %s, dtype %s, %d of %d rays hit, %d samples evaluated, decoded in %.3f s -> %s" % (
+        args.view, args.region, tuple(data.shape), data.dtype, stats["rays_hit"], stats["rays"], stats["samples_evaluated"], dt, args.o))
     return 0
 
 

@@ -685,6 +685,39 @@ int brief_surface_shade(const brief_view_desc *view, const float *t, const float
 int brief_view_sample_t_host(const brief_view_desc *view, const int32_t *row, const int32_t *col, const float *t, int64_t n, float *pos, float *coord,
                              uint8_t *inside);
 
+/* ---- composite view: front-to-back emission-absorption rendering through a transfer table (csrc/brief_composite.inc, .h) ------------
+ * Clip, scan and the march's coordinates are brief_view_clip / (caller) / brief_view_coords.  Channel `channel` of the integer decode is
+ * classified by the table tf, int32 [2^tf_bits][4] = (tau, eR, eG, eB), at the index value >> (bits of the dtype - tf_bits):
+ *     tau   the sample's optical depth in units of 2^-16 octaves (the sample multiplies the transmittance by 2^(-tau / 65536)),
+ *           0 .. TAU_SAT = 32 * 65536, TAU_SAT being opaque;
+ *     e_c   the premultiplied emission round(256 * colour_c * (1 - 2^(-tau / 65536))), 0 .. 65280.
+ * Over the inside samples of a ray in ascending k, all in integers: P_i = min(sum of the tau before sample i, TAU_SAT);
+ * acc_c = sum of W(P_i) * e_c(i) (uint64), W the transmittance in Q0.32 from two 256-entry constant tables, W(0) = 2^32, W(TAU_SAT) = 0;
+ *   brief_view_composite_fold    brief_view_fold's arguments and walk; per pass a scan of tau over the lanes of a ray's group plus the
+ *                                ray's running carry gives P_i; lane 0 does one plain read-modify-write of the pixel's state: hits[r]
+ *                                (int32), tau_run[r] (int32: the saturated running optical depth, the carry-in of the ray's next chunk)
+ *                                and acc[r][3] (uint64), all caller-initialised to 0.  No atomics; the chunks of a view follow the
+ *                                list's order on one stream, so the earlier part of a ray is folded first;
+ *   brief_view_composite_finish  out[r][4] (uint8) = R, G, B, A: out_c = min(255, (acc_c + bg_c * 256 * W(P_total) + 2^39) >> 40), RGB already
+ *                                composited over background[3] (a HOST pointer, 0 .. 255 each), A = min(255, ((2^32 - W(P_total)) * 255
+ *                                + 2^31) >> 32).
+ * Sums of integers, and a prefix that depends on a sample's place along its ray alone: the image is exact and independent of chunking,
+ * `lanes` and the run.  Every device entry only enqueues on `stream`; tf is device memory there.
+ * brief_view_composite_host is the same fold and finish on the host CPU, without any GPU call: every buffer is host memory, off[0] is 0 and
+ * vals [off[rays]][channels] holds the whole list; hits, tau_run and acc may be NULL.
+ * Limits (BRIEF_ERR_INVALID with a message naming the limit, before any launch): those of the view entries; no null buffer; elem_kind
+ * BRIEF_OUT_U8 | BRIEF_OUT_U16; channels 1 .. 4; channel 0 .. channels - 1; tf_bits 1 .. 8 (uint8) or 1 .. 16 (uint16); tf 16-byte and out
+ * 4-byte aligned; background 0 .. 255.  The table's entries are checked where it is host-visible (brief_view_composite_host: tau 0 ..
+ * TAU_SAT, e_c 0 .. 65280; composite.make_transfer); the kernel reads them as they are. */
+int brief_view_composite_fold(const brief_view_desc *view, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1, int64_t r0, int64_t r1,
+                              int32_t lanes, const void *vals, int elem_kind, int32_t channels, int32_t channel, const int32_t *tf, int32_t tf_bits,
+                              int32_t *hits, int32_t *tau_run, uint64_t *acc, void *stream);
+int brief_view_composite_finish(const brief_view_desc *view, const int32_t *background, const int32_t *hits, const int32_t *tau_run, const uint64_t *acc,
+                                uint8_t *out, void *stream);
+int brief_view_composite_host(const brief_view_desc *view, const int32_t *k0, const int64_t *off, const void *vals, int elem_kind, int32_t channels,
+                              int32_t channel, const int32_t *tf, int32_t tf_bits, const int32_t *background, int32_t *hits, int32_t *tau_run,
+                              uint64_t *acc, uint8_t *out);
+
 /* ---- Hessian decode of an fp32 SIREN (csrc/brief_hess.inc) ------------------------------------------------------------------------
  * value[n][cout] and jac[n][cout][cin] as brief_siren_jac_forward gives them, and hess[n][cout][nh] = d2 phi_c / d x_a d x_b (x_n), the
  * analytic second derivatives with respect to the coordinates in coordinate units; with output_act, of the activated output.  nh = 6 in
