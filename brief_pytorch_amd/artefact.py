@@ -141,6 +141,16 @@ def open_artefact(opt, module_path, sideinfos, *, default_precision=None, defaul
     return Artefact(copy.deepcopy(cf), sideinfos, module_path, default_precision, default_name)
 
 
+def view_dims(dims, shape):
+    """the grid a decode evaluates: the fitted `dims`, or with `shape` the resampled view of that spatial shape (one length >= 1 per axis)"""
+    if shape is None:
+        return dims
+    shape = [int(v) for v in shape]
+    if len(shape) != len(dims) or any(v < 1 for v in shape):
+        raise ValueError("shape %s does not fit the %d spatial axes of the artefact" % (shape, len(dims)))
+    return shape
+
+
 def check_envelope(art, *, no_error_bound=None, need_3d=None, need_integer=None, need_minmaxany=None, local_postprocess=False, min_axis=None):
     """What a decode mode supports, refused on options and side info before any decode, in this order.  A condition is checked where
     its argument is given; the argument is the mode's own wording of the refusal (a % template), so each mode keeps its text.

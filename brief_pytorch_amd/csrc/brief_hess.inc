@@ -1,9 +1,11 @@
 // brief_hess.inc — Hessian decode of an fp32 SIREN: k_hess_fwd<MTW, BOX> and its host entries brief_siren_hess_forward / _forward_box
 // (part of the single translation unit brief_hip.hip, included last, behind brief_view.inc, so that its kernels are the last ones named).
-// Only new kernels: no kernel, device function or argument struct of another file is changed or shared.  The tile helpers
-// hess_box_coords, hess_chain and hess_write_image are the one text of brief_tile.inc compiled under the hess_ prefix (TILE_CHAIN_PACKED
-// form, as brief_jac.inc has them under jac_); hess_bias_col (one parameter more) is this file's own, the included hess_bias, hess_stash
-// and hess_frag are unused.  The weights are the Jacobian kernel's packed fragment copy (k_jac_repack, JacLayout): there is no second repack.
+// No kernel or device function of another file is changed.  The tile helpers hess_box_coords, hess_chain, hess_bias_col, hess_fetch and
+// hess_write_image are the one text of brief_tile.inc compiled under the hess_ prefix (TILE_CHAIN_PACKED form, as brief_jac.inc has them
+// under jac_); the included hess_bias, hess_stash and hess_frag are unused.  HessArgs is brief_jac.inc's JacArgs and one pointer; the host
+// entries are the driver of brief_jac_host.inc over HessDecode.  The weights are the Jacobian kernel's packed fragment copy (k_jac_repack,
+// JacLayout): there is no second repack.  The two kernels stay two texts: their column layouts, the layer-0 block, the sine rule and the
+// head differ in every line that is not a helper call (profiles/r21_derivative_decode.md).
 //
 // Forward mode of second order: the value, its cin tangents and its cin (cin + 1) / 2 distinct second derivatives travel together,
 //   z_0 = W_0 x + b_0,      d_a z_0 = W_0[:, a],       d_ab z_0 = 0
@@ -26,18 +28,8 @@
 // computed once per thread, no LDS round trip.  The LDS image of a layer stays [32 nt rows][32 columns] (128 KB at 1024 features)
 // plus the tile's coordinates, as in k_jac_fwd.
 
-struct HessArgs {
-    brief_siren_desc d;
-    JacLayout lay;
-    const float *pk;
-    const float *coords;
-    const int64_t *idx;
-    int64_t offset, n;
-    GridArgs grid;
-    BoxArgs box;
-    float *value;             // [n][cout] or NULL
-    float *jac;               // [n][cout][cin] or NULL
-    float *hess;              // [n][cout][nh]
+struct HessArgs : JacArgs {
+    float *hess;              // [n][cout][nh]; the base's jac may be NULL here
 };
 
 #define TILE_CHAIN_PACKED
@@ -48,18 +40,6 @@ struct HessArgs {
 __device__ __forceinline__ float hess_lane(int addr, float v)
 {
     return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v)));
-}
-
-// the bias in the value column, zero in every other column
-template <int MTW>
-__device__ __forceinline__ void hess_bias_col(f32x16 (&acc)[MTW], const float *__restrict__ b, int nt, int wv, int hi, bool value_col)
-{
-#pragma unroll
-    for (int t = 0; t < MTW; ++t) {
-        const int mt = wv + 4 * t;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = mt < nt && value_col ? b[32 * mt + ROWMAP(r, hi)] : 0.f;
-    }
 }
 
 // One tile of SPT samples per workgroup iteration (persistent grid over the tiles), 4 waves; wave wv owns feature tiles wv, wv + 4,
@@ -90,23 +70,7 @@ __global__ __launch_bounds__(256) void k_hess_fwd(const HessArgs a)
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t col0 = tile * spt;
         // ---- sample selection: the sources of the family decode kernels
-        if (tid < spt) {
-            float x0 = 0.f, x1 = 0.f, x2 = 0.f;
-            const int64_t n = col0 + tid;
-            if (n < a.n) {
-                const int64_t j = a.idx ? a.idx[n] : n + a.offset;
-                if (a.coords) {
-                    x0 = a.coords[j * cin];
-                    x1 = a.coords[j * cin + 1];
-                    if (cin == 3) x2 = a.coords[j * cin + 2];
-                } else if (BOX) {
-                    hess_box_coords(a.grid, a.box, cin, j, x0, x1, x2);
-                } else {
-                    grid_coords(a.grid, cin, j, x0, x1, x2);
-                }
-            }
-            *reinterpret_cast<float4 *>(xsh + 4 * tid) = make_float4(x0, x1, x2, 0.f);
-        }
+        if (tid < spt) *reinterpret_cast<float4 *>(xsh + 4 * tid) = hess_fetch<BOX>(a, cin, col0 + tid);
         __syncthreads();
         const float4 x = *reinterpret_cast<const float4 *>(xsh + 4 * sj);
         // ---- sine layers 0 .. L-2: layer 0 on the VALU (K = cin), the others as MFMA chains
@@ -185,71 +149,42 @@ __global__ __launch_bounds__(256) void k_hess_fwd(const HessArgs a)
     }
 }
 
-// ---- host side: every entry only enqueues on `stream`; nothing is allocated and the host never waits.  The checks, their order and the
-// sample sources are those of brief_siren_jac_forward* (brief_jac_host.inc); `packed` is brief_siren_jac_repack's buffer.
+// ---- host side: the driver of brief_jac_host.inc (its checks, their order and the sample sources) over this decode's traits; `packed`
+// is brief_siren_jac_repack's buffer.
 
-static const char *kHessTooWide = "spatial hessian: features must be 1..1024";
-
-static int hess_check(const brief_siren_desc *d)
-{
-    if (!d) return fail(BRIEF_ERR_INVALID, "null desc");
-    if (d->precision != BRIEF_PREC_F32) return fail(BRIEF_ERR_INVALID, "spatial hessian: precision must be BRIEF_PREC_F32");
-    if (d->cin != 2 && d->cin != 3) return fail(BRIEF_ERR_INVALID, "spatial hessian: coords_channel must be 2 or 3");
-    if (d->cout < 1 || d->cout > 4) return fail(BRIEF_ERR_INVALID, "spatial hessian: data_channel must be 1..4");
-    if (d->layers < 2) return fail(BRIEF_ERR_INVALID, "spatial hessian: layers must be >= 2");
-    if (d->features < 1 || d->features > 1024) return fail(BRIEF_ERR_INVALID, kHessTooWide);
-    return 0;
-}
+static void deriv_set_hess(HessArgs &a, float *hess) { a.hess = hess; }
 
 template <bool BOX>
 struct HessFwd { template <int M> static auto fn() { return k_hess_fwd<M, BOX>; } };
 
-static void hess_args(HessArgs &a, const brief_siren_desc *d, const float *packed, int64_t n, float *value, float *jac, float *hess)
-{
-    memset(&a, 0, sizeof(a));
-    a.d = *d; a.lay = jac_layout(*d); a.pk = packed;
-    a.n = n; a.value = value; a.jac = jac; a.hess = hess;
-}
-
-// the persistent grid over tiles of 3 (cin == 3) or 5 (cin == 2) samples: family_grid counts tiles of 32
-template <bool BOX>
-static int hess_launch(const HessArgs &a, hipStream_t st)
-{
-    const int lds = jac_lds_bytes(a.lay);
-    const int64_t spt = a.d.cin == 3 ? 3 : 5;
-    return launch_fwd_mtw<HessFwd<BOX> >((a.lay.nt + 3) / 4, a, family_grid(lds, 32 * ((a.n + spt - 1) / spt)), lds, st, kHessTooWide);
-}
+struct HessDecode {
+    typedef HessArgs Args;
+    static constexpr const char *label = "spatial hessian", *too_wide = "spatial hessian: features must be 1..1024",
+                                *null_buffer = "spatial hessian: null buffer (packed and hess are required)";
+    static float *required(float *, float *hess) { return hess; }
+    // the persistent grid over tiles of 3 (cin == 3) or 5 (cin == 2) samples: family_grid counts tiles of 32
+    template <bool BOX>
+    static int launch(const Args &a, hipStream_t st)
+    {
+        const int lds = jac_lds_bytes(a.lay);
+        const int64_t spt = a.d.cin == 3 ? 3 : 5;
+        return launch_fwd_mtw<HessFwd<BOX> >((a.lay.nt + 3) / 4, a, family_grid(lds, 32 * ((a.n + spt - 1) / spt)), lds, st, too_wide);
+    }
+};
 
 extern "C" {
 
 int brief_siren_hess_forward(const brief_siren_desc *d, const float *packed, const brief_grid_desc *grid, const brief_batch_desc *batch,
                              float *value, float *jac, float *hess, void *stream)
 {
-    if (int rc = hess_check(d)) return rc;
-    if (int rc = check_batch(d->cin, grid, batch, false)) return rc;
-    if (!packed || !hess) return fail(BRIEF_ERR_INVALID, "spatial hessian: null buffer (packed and hess are required)");
-    HessArgs a;
-    hess_args(a, d, packed, batch->n, value, jac, hess);
-    a.coords = batch->coords; a.idx = batch->idx; a.offset = batch->offset;
-    fill_grid(a.grid, grid);
-    return hess_launch<false>(a, (hipStream_t)stream);
+    return deriv_forward<HessDecode>(d, packed, grid, batch, value, jac, hess, stream);
 }
 
 int brief_siren_hess_forward_box(const brief_siren_desc *d, const float *packed, const brief_grid_box *box, int64_t offset, int64_t n,
                                  float *value, float *jac, float *hess, void *stream)
 {
-    if (int rc = hess_check(d)) return rc;
-    int64_t voxels = 0;
-    if (int rc = check_box(d->cin, box, &voxels)) return rc;
-    if (n < 1) return fail(BRIEF_ERR_INVALID, "empty batch");
-    if (offset < 0 || offset > voxels - n) return fail(BRIEF_ERR_INVALID, "offset + n exceeds the box's voxel count");
-    if (!packed || !hess) return fail(BRIEF_ERR_INVALID, "spatial hessian: null buffer (packed and hess are required)");
-    HessArgs a;
-    hess_args(a, d, packed, n, value, jac, hess);
-    a.offset = offset;
-    fill_grid(a.grid, &box->grid);
-    fill_box(a.box, box);
-    return hess_launch<true>(a, (hipStream_t)stream);
+    return deriv_forward_box<HessDecode>(d, packed, box, offset, n, value, jac, hess, stream);
 }
 
 }   // extern "C"
+

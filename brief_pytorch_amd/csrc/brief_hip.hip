@@ -20,7 +20,7 @@
 // (brief_device.inc shared definitions, brief_fused.inc k_fused, brief_lean.inc k_lean, brief_small.inc k_small, brief_wgrad.inc k_wgrad,
 //  brief_x3.inc split precision, brief_reduce.inc optimizer + k_reduce, brief_bf16.inc the bf16 path, brief_aux.inc repack / metrics / deblocking).
 // The families with kernels of their own (brief_ffn.inc, brief_nerf.inc, brief_mfn.inc, brief_taper.inc) share ONE host driver and keep their
-// C-ABI entries in brief_family_host.inc, included at the end of this file.  Their tile helpers, and brief_jac.inc's, are the one text of
+// C-ABI entries in brief_family_host.inc, included at the end of this file.  Their tile helpers, brief_jac.inc's and brief_hess.inc's, are the one text of
 // brief_tile.inc, which each of those files includes under its own name prefix (not listed below: brief_hip.hip does not include it).
 //
 //   k_fused<NT,TRAIN>  coords -> layer0 -> hidden layers -> head -> loss -> dgrad chain.
@@ -42,7 +42,7 @@
 //   brief_jac.inc      k_jac_fwd / k_jac_repack: value and analytic Jacobian of an fp32 SIREN with respect to the coordinates (host: brief_jac_host.inc).
 //   brief_view.inc     k_view_clip / k_view_coords / k_view_fold / k_view_finish: oblique slices and projections along any direction (geometry: brief_view.h).
 //   brief_composite.inc  k_composite_fold / k_composite_finish: emission-absorption rendering of a view through a transfer table, in integers (arithmetic: brief_composite.h).
-//   brief_hess.inc     k_hess_fwd: value, Jacobian and analytic Hessian of an fp32 SIREN with respect to the coordinates (second-order forward mode; host entries in the same file).
+//   brief_hess.inc     k_hess_fwd: value, Jacobian and analytic Hessian of an fp32 SIREN with respect to the coordinates (second-order forward mode; host entries in the same file, over the driver of brief_jac_host.inc).
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
@@ -1775,7 +1775,7 @@ int brief_quant_decode(const uint16_t *codes, const brief_quant_span *tensors, i
 }   // extern "C"
 
 #include "brief_family_host.inc"      // FFN, NeRF, MFN, tapered SIRENs: one host driver, four traits structs and their C-ABI entries
-#include "brief_jac_host.inc"         // spatial-gradient decode: brief_siren_jac_* (named last: its kernels are the last ones instantiated)
+#include "brief_jac_host.inc"         // the derivative decodes' host driver and the spatial-gradient entries brief_siren_jac_* (named last: its kernels are the last ones instantiated)
 #include "brief_view.inc"             // orthographic view decode: kernels and entries of their own, behind everything else (the kernels above keep their order)
 #include "brief_hess.inc"             // Hessian decode: k_hess_fwd and brief_siren_hess_forward / _forward_box, behind the view kernels (the kernels above keep their order)
 #include "brief_composite.inc"        // composite view: k_composite_fold / k_composite_finish and brief_view_composite_*, behind everything else (the kernels above keep their order)

@@ -1,9 +1,10 @@
 // brief_jac.inc — spatial-gradient decode of an fp32 SIREN: k_jac_fwd<MTW, BOX>, k_jac_repack (part of the single translation unit
 // brief_hip.hip, included behind brief_quant.inc so that its kernels are named last; the host entries are brief_jac_host.inc).
-// Only new kernels: no kernel, device function or argument struct of another file is changed or shared.  The tile helpers jac_box_coords,
-// jac_chain and jac_write_image are the one text of brief_tile.inc compiled under the jac_ prefix (TILE_CHAIN_PACKED form; not functions
-// shared with the families: that changes the code of 88 of the 330 kernels, see the note in brief_nerf.inc).  jac_bias (one parameter
-// more) and the frag lambda of k_jac_repack (it captures ks) are this file's own; the included jac_bias, jac_stash and jac_frag are unused.
+// No kernel or device function of another file is changed.  The tile helpers jac_box_coords, jac_chain, jac_bias_col, jac_fetch and
+// jac_write_image are the one text of brief_tile.inc compiled under the jac_ prefix (TILE_CHAIN_PACKED form; not functions shared with the
+// families: that changes the code of 88 of the 330 kernels, see the note in brief_nerf.inc); the Hessian decode (brief_hess.inc) compiles
+// the same text under hess_, and its HessArgs derives from this file's JacArgs.  The frag lambda of k_jac_repack (it captures ks) is this
+// file's own; the included jac_bias, jac_stash and jac_frag are unused.
 //
 // Forward mode: the value and its cin tangents travel through the layers together,
 //   z_0 = W_0 x + b_0,            dz_0/dx_a = W_0[:, a]
@@ -68,18 +69,6 @@ __device__ __forceinline__ float jac_quad0(float v)
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x00, 0xf, 0xf, false));
 }
 
-// the bias in the value column (q == 0), zero in the tangent columns
-template <int MTW>
-__device__ __forceinline__ void jac_bias(f32x16 (&acc)[MTW], const float *__restrict__ b, int nt, int wv, int hi, bool value_col)
-{
-#pragma unroll
-    for (int t = 0; t < MTW; ++t) {
-        const int mt = wv + 4 * t;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = mt < nt && value_col ? b[32 * mt + ROWMAP(r, hi)] : 0.f;
-    }
-}
-
 // One tile of 8 samples x 4 quantities per workgroup iteration (persistent grid over the tiles), 4 waves; wave wv owns feature tiles
 // wv, wv + 4, ... of every layer.  Samples past n in the last tile compute on zeros and store nothing.
 template <int MTW, bool BOX>
@@ -96,23 +85,7 @@ __global__ __launch_bounds__(256) void k_jac_fwd(const JacArgs a)
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t col0 = tile * 8;
         // ---- sample selection: the sources of the family decode kernels
-        if (tid < 8) {
-            float x0 = 0.f, x1 = 0.f, x2 = 0.f;
-            const int64_t n = col0 + tid;
-            if (n < a.n) {
-                const int64_t j = a.idx ? a.idx[n] : n + a.offset;
-                if (a.coords) {
-                    x0 = a.coords[j * cin];
-                    x1 = a.coords[j * cin + 1];
-                    if (cin == 3) x2 = a.coords[j * cin + 2];
-                } else if (BOX) {
-                    jac_box_coords(a.grid, a.box, cin, j, x0, x1, x2);
-                } else {
-                    grid_coords(a.grid, cin, j, x0, x1, x2);
-                }
-            }
-            *reinterpret_cast<float4 *>(xsh + 4 * tid) = make_float4(x0, x1, x2, 0.f);
-        }
+        if (tid < 8) *reinterpret_cast<float4 *>(xsh + 4 * tid) = jac_fetch<BOX>(a, cin, col0 + tid);
         __syncthreads();
         const float4 x = *reinterpret_cast<const float4 *>(xsh + 4 * sj);
         // ---- sine layers 0 .. L-2: layer 0 on the VALU (K = cin), the others as MFMA chains
@@ -136,7 +109,7 @@ __global__ __launch_bounds__(256) void k_jac_fwd(const JacArgs a)
                 }
             } else {
                 const float *pl = a.pk + a.lay.hid + (int64_t)(l - 1) * a.lay.hid_stride;
-                jac_bias(acc, pl + (int64_t)nt * ks * 256, nt, wv, hi, q == 0);
+                jac_bias_col(acc, pl + (int64_t)nt * ks * 256, nt, wv, hi, q == 0);
                 jac_chain(acc, pl, ks, nt, Xh, wv, lane);
             }
             // column 0 holds the phase in revolutions, columns 1 .. 3 its derivatives: h = sin_rev(f), dh = 2 pi cos_rev(f) dz
@@ -154,7 +127,7 @@ __global__ __launch_bounds__(256) void k_jac_fwd(const JacArgs a)
         // ---- head (one 32-row tile: wave 0), rows 0..cout-1 are in registers 0..3 of lanes 0..31
         f32x16 hacc[1];
         const float *ph = a.pk + a.lay.head;
-        jac_bias(hacc, ph + (int64_t)ks * 256, 1, wv, hi, q == 0);
+        jac_bias_col(hacc, ph + (int64_t)ks * 256, 1, wv, hi, q == 0);
         if (wv == 0) jac_chain(hacc, ph, ks, 1, Xh, wv, lane);
         float yo[4];
 #pragma unroll

@@ -80,7 +80,7 @@ struct NerfArgs {
 // ---- the tile helpers nerf_box_coords, nerf_chain, nerf_bias, nerf_write_image, nerf_stash and nerf_frag: the one text of brief_tile.inc,
 // compiled here under the nerf_ prefix.  One text, not one set of functions: with the NeRF, MFN and taper kernels calling the ffn_*
 // helpers, 88 of the 330 kernels compiled to other code, 24 k_ffn_fwd instantiations whose source did not change among them.  No
-// family keeps a copy; only brief_jac.inc has a bias (jac_bias, one parameter more) and a frag lambda of its own.
+// family keeps a copy; only brief_jac.inc has a frag lambda of its own.
 #define TILE_(name) nerf_##name
 #include "brief_tile.inc"
 

@@ -1,16 +1,18 @@
-// brief_tile.inc — the tile helpers of the family kernels (FFN, NeRF, MFN, tapered SIREN, the Jacobian decode): ONE text, compiled once
-// per family.  A family file sets its prefix and includes this file where its helpers stand:
+// brief_tile.inc — the tile helpers of the family kernels (FFN, NeRF, MFN, tapered SIREN, the Jacobian decode, the Hessian decode): ONE
+// text, compiled once per family.  A family file sets its prefix and includes this file where its helpers stand:
 //     #define TILE_(name) nerf_##name
 //     #include "brief_tile.inc"
-// and gets nerf_box_coords, nerf_chain, nerf_bias, nerf_write_image, nerf_stash and nerf_frag, functions of its own.  They are NOT one
-// set of functions called by every family: with the NeRF, MFN and taper kernels calling the ffn_* helpers, 88 of the 330 kernels
-// compiled to other code, k_ffn_fwd instantiations whose source had not changed among them (profiles/r12_family_driver.md, third row).
-// Included under a prefix, every family's kernels see the tokens they saw when each file carried a copy, and compile to the same
-// code (profiles/r18_tile_helpers.md).  Nothing here is instantiated or emitted for a family that does not call it.
+// and gets nerf_box_coords, nerf_chain, nerf_bias, nerf_bias_col, nerf_fetch, nerf_write_image, nerf_stash and nerf_frag, functions of
+// its own.  They are NOT one set of functions called by every family: with the NeRF, MFN and taper kernels calling the ffn_* helpers, 88
+// of the 330 kernels compiled to other code, k_ffn_fwd instantiations whose source had not changed among them
+// (profiles/r12_family_driver.md, third row).  Included under a prefix, every family's kernels see the tokens they saw when each file
+// carried a copy, and compile to the same code (profiles/r18_tile_helpers.md, profiles/r21_derivative_decode.md).  Nothing here is
+// instantiated or emitted for a family that does not call it: bias_col and fetch are called by the two derivative decodes (brief_jac.inc,
+// brief_hess.inc) only, bias, stash and frag by the four network families only.
 //
-// TILE_CHAIN_PACKED (set by brief_taper.inc and brief_jac.inc, whose fragment rows are exactly ksteps steps long): the chain takes no
-// row stride KS and uses ksteps for both.  It is a second text, not a forwarder to the KS form: a forwarder, and equally the count
-// passed twice, compiled k_taper_fwd and k_jac_fwd to other code.
+// TILE_CHAIN_PACKED (set by brief_taper.inc, brief_jac.inc and brief_hess.inc, whose fragment rows are exactly ksteps steps long): the
+// chain takes no row stride KS and uses ksteps for both.  It is a second text, not a forwarder to the KS form: a forwarder, and equally
+// the count passed twice, compiled k_taper_fwd and k_jac_fwd to other code.
 // Both macros are undefined again at the end of this file.
 
 #ifndef TILE_
@@ -121,6 +123,39 @@ __device__ __forceinline__ void TILE_(bias)(f32x16 (&acc)[MTW], const float *__r
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = mt < nt ? b[32 * mt + ROWMAP(r, hi)] : 0.f;
     }
+}
+
+// the bias in the value column of a derivative decode (value_col), zero in the tangent and second-derivative columns
+template <int MTW>
+__device__ __forceinline__ void TILE_(bias_col)(f32x16 (&acc)[MTW], const float *__restrict__ b, int nt, int wv, int hi, bool value_col)
+{
+#pragma unroll
+    for (int t = 0; t < MTW; ++t) {
+        const int mt = wv + 4 * t;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = mt < nt && value_col ? b[32 * mt + ROWMAP(r, hi)] : 0.f;
+    }
+}
+
+// sample n of a decode batch -> its coordinates (x0, x1, x2, 0), zeros past the end of the batch: the sources of the family decode
+// kernels (coords, else idx or n + offset into the box or the grid); Args: JacArgs or a struct derived from it
+template <bool BOX, class Args>
+__device__ __forceinline__ float4 TILE_(fetch)(const Args &a, int cin, int64_t n)
+{
+    float x0 = 0.f, x1 = 0.f, x2 = 0.f;
+    if (n < a.n) {
+        const int64_t j = a.idx ? a.idx[n] : n + a.offset;
+        if (a.coords) {
+            x0 = a.coords[j * cin];
+            x1 = a.coords[j * cin + 1];
+            if (cin == 3) x2 = a.coords[j * cin + 2];
+        } else if (BOX) {
+            TILE_(box_coords)(a.grid, a.box, cin, j, x0, x1, x2);
+        } else {
+            grid_coords(a.grid, cin, j, x0, x1, x2);
+        }
+    }
+    return make_float4(x0, x1, x2, 0.f);
 }
 
 template <int MTW>

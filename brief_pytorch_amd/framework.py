@@ -21,7 +21,7 @@ import torch
 from . import _lib, config, corrections, quantize
 from . import region as region_mod
 from .artefact import _coords_range, _load_corrections, _region_postprocess_check, check_error_bound      # noqa: F401 (re-exported: tests and bench.py import them from here)
-from .artefact import block_paths, divide_blocks, meeting, open_artefact
+from .artefact import block_paths, divide_blocks, meeting, open_artefact, view_dims
 from .fit import Fitter
 from .io import get_folder_size, get_type_max, invnormalize_data, minmaxany_range, normalize_data, normalize_data_device, save_yaml, load_yaml
 from .metrics import cal_ssim, eval_performance, gpu_eval_u16, gpu_ssim_u16, psnr_from_sse
@@ -231,11 +231,7 @@ class NFGR:
             raise ValueError("a resampled view (shape) of an error-bounded artefact is refused: its corrections (error_bound %s) exist on the "
                              "fitted grid %s only" % (art.side["error_bound"], dims))
         corr = art.corrections()
-        if shape is not None:
-            shape = [int(v) for v in shape]
-            if len(shape) != len(dims) or any(v < 1 for v in shape):
-                raise ValueError("shape %s does not fit the %d spatial axes of the artefact" % (shape, len(dims)))
-            dims = shape
+        dims = view_dims(dims, shape)
         start, stop, stp = region_mod.normalize_region(dims, region, step)
         phi = art.load_phi(device)
         if art.integer:

@@ -4,14 +4,12 @@ region semantics: a region equals the slice of the whole, results do not depend 
 call gives the same bits.  (DESIGN.md "Spatial-gradient decode".)
 
 voxel_scale, refusal and supported are host arithmetic; everything else needs a ROCm GPU (there is no CPU fallback)."""
-import numpy as np
+import functools
 
-from . import artefact, config
-from . import region as region_mod
+from . import derivative
+from .derivative import MAX_FEATURES, NETS, PRECISIONS      # noqa: F401 (the envelope is the two derivative decodes')
 
-MAX_FEATURES = 1024
-NETS = ("SIREN",)                  # the net classes brief_siren_jac_* evaluate
-PRECISIONS = ("fp32", "f32")
+NOUN = derivative.Noun("spatial gradients", "gradient", "spatial-gradient decode")
 
 
 def voxel_scale(dims, lo, hi, norm_range, vmin, vmax):
@@ -21,21 +19,12 @@ def voxel_scale(dims, lo, hi, norm_range, vmin, vmax):
     invnormalize_data('minmaxany_a_b') of the net's output ((y - a) / (b - a) * (vmax - vmin) + vmin, norm_range = (a, b)), per step
     of one voxel of the linspace grid `dims` over [lo, hi] that is being evaluated.  With a stride it is still per voxel of that grid;
     with a resampled view (shape) `dims` is the resampled grid, so it is per voxel of that one."""
-    a, b = (np.float64(v) for v in norm_range)
-    grey = (np.float64(vmax) - np.float64(vmin)) / (b - a)
-    out = np.zeros(len(dims), dtype=np.float64)
-    for ax, n in enumerate(dims):
-        if int(n) > 1:
-            out[ax] = (np.float64(hi) - np.float64(lo)) / np.float64(int(n) - 1) * grey
-    return out
+    return derivative.steps(dims, lo, hi) * derivative.grey(norm_range, vmin, vmax)
 
 
 def refusal(phi_name, precision, features):
     """None where spatial gradients exist, else the refusal text (pure: no GPU, no library)"""
-    if str(phi_name) not in NETS or str(precision) not in PRECISIONS or not 1 <= int(features) <= MAX_FEATURES:
-        return "spatial gradients exist for fp32 SIREN up to %d features (this net is %s, %s, %d features)" % (
-            MAX_FEATURES, phi_name, precision, int(features))
-    return None
+    return derivative.refusal(NOUN, phi_name, precision, features)
 
 
 def supported(phi_name, precision, features):
@@ -45,11 +34,7 @@ def supported(phi_name, precision, features):
 
 def check_artefact(art):
     """what decompress_gradient supports, checked on the opened artefact before any decode"""
-    why = refusal(art.phi_name, art.precision, art.phi_features)
-    if why is not None:
-        raise ValueError(why)
-    artefact.check_envelope(art, need_minmaxany="the spatial-gradient decode supports the 'minmaxany_a_b' normalisations only (their inverse "
-                                                "is affine in the net's output), not Normalize.name=%s")
+    derivative.check_artefact(art, NOUN)
 
 
 def _block_gradient(art, dims, start, stop, step, device, chunk=None):
@@ -63,16 +48,7 @@ def _block_gradient(art, dims, start, stop, step, device, chunk=None):
 
 def decompress_gradient_device(opt, module_path, sideinfos, region=None, step=1, shape=None, device="cuda", chunk=None):
     """decompress_gradient's result as a device tensor (what the magnitude of decompress.py is taken of)"""
-    art = artefact.open_artefact(opt, module_path, sideinfos)
-    check_artefact(art)
-    dims = art.dims
-    if shape is not None:
-        shape = [int(v) for v in shape]
-        if len(shape) != len(dims) or any(v < 1 for v in shape):
-            raise ValueError("shape %s does not fit the %d spatial axes of the artefact" % (shape, len(dims)))
-        dims = shape
-    start, stop, stp = region_mod.normalize_region(dims, region if region is not None else (slice(None),) * len(dims), step)
-    return _block_gradient(art, dims, start, stop, stp, device, chunk)
+    return derivative.single(opt, module_path, sideinfos, region, step, shape, device, functools.partial(_block_gradient, chunk=chunk), NOUN)
 
 
 def decompress_gradient(opt, module_path, sideinfos, region=None, step=1, shape=None, device="cuda", chunk=None):
@@ -91,26 +67,8 @@ def decompress_gradient(opt, module_path, sideinfos, region=None, step=1, shape=
 
 def decompress_divide_gradient_device(opt, orig_sideinfos, module_dir, sideinfos_dir, region=None, step=1, device="cuda", chunk=None):
     """decompress_divide_gradient's result as a device tensor"""
-    import torch
-    if isinstance(opt, str):
-        opt = config.load(opt)
-    data_shape, blocks = artefact.divide_blocks(orig_sideinfos, module_dir, sideinfos_dir)
-    dims, cout = data_shape[:-1], data_shape[-1]
-    start, stop, stp = region_mod.normalize_region(dims, region if region is not None else (slice(None),) * len(dims), step)
-    ext = region_mod.extents(start, stop, stp)
-    # every refusal before any decode
-    arts = {b.name: artefact.open_artefact(opt, b.module_path, b.side) for b in blocks}
-    for art in arts.values():
-        check_artefact(art)
-    pair = artefact.first_overlap(blocks, "dhw" if len(dims) == 3 else "hw")
-    if pair is not None:
-        raise ValueError("the blocks %s and %s overlap: merge_divided_data adds overlapping blocks and clips the sum, which has "
-                         "no single net's gradient; the spatial-gradient decode needs a partition without overlap" % (pair[0].name, pair[1].name))
-    out = torch.zeros((*ext, cout, len(dims)), dtype=torch.float32, device=device)
-    for b, o_lo, o_hi, l_start, l_stop in artefact.meeting(blocks, start, stp, ext):
-        art = arts[b.name]
-        out[tuple(slice(lo, hi) for lo, hi in zip(o_lo, o_hi))] = _block_gradient(art, art.dims, l_start, l_stop, stp, device, chunk)
-    return out
+    return derivative.divide(opt, orig_sideinfos, module_dir, sideinfos_dir, region, step, device, functools.partial(_block_gradient, chunk=chunk),
+                             lambda nd: nd, NOUN)
 
 
 def decompress_divide_gradient(opt, orig_sideinfos, module_dir, sideinfos_dir, region=None, step=1, device="cuda", chunk=None):

@@ -8,16 +8,15 @@ Component order of the last axis (the upper triangle, row by row): (00, 01, 02, 
 
 voxel_scale, refusal, supported, and laplacian / eigenvalues / vesselness on CPU tensors are host arithmetic; everything else needs a ROCm
 GPU (there is no CPU fallback)."""
+import functools
 import math
 
 import numpy as np
 
-from . import artefact, config
-from . import region as region_mod
+from . import derivative
+from .derivative import MAX_FEATURES, NETS, PRECISIONS      # noqa: F401 (the envelope is the two derivative decodes')
 
-MAX_FEATURES = 1024
-NETS = ("SIREN",)                  # the net classes brief_siren_hess_* evaluate
-PRECISIONS = ("fp32", "f32")
+NOUN = derivative.Noun("spatial Hessians", "Hessian", "Hessian decode")
 MODES = ("components", "laplacian", "eigenvalues", "vesselness")
 PAIRS = {2: ((0, 0), (0, 1), (1, 1)), 3: ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))}      # axes of component h
 DERIVED_CHUNK = 1 << 22            # rows of the result a derived map is computed on at a time (its float64 temporaries)
@@ -38,21 +37,14 @@ def voxel_scale(dims, lo, hi, norm_range, vmin, vmax):
     of the unclipped, untruncated invnormalize_data('minmaxany_a_b') of the net's output (affine: (y - lo_n) / (hi_n - lo_n) * (vmax -
     vmin) + vmin, norm_range = (lo_n, hi_n)), per step of one voxel of the linspace grid `dims` over [lo, hi] along each of the two
     axes.  With a stride it is still per voxel of that grid; with a resampled view (shape) `dims` is the resampled grid."""
-    a, b = (np.float64(v) for v in norm_range)
-    grey = (np.float64(vmax) - np.float64(vmin)) / (b - a)
-    step = np.zeros(len(dims), dtype=np.float64)
-    for ax, n in enumerate(dims):
-        if int(n) > 1:
-            step[ax] = (np.float64(hi) - np.float64(lo)) / np.float64(int(n) - 1)
+    step = derivative.steps(dims, lo, hi)
+    grey = derivative.grey(norm_range, vmin, vmax)
     return np.array([step[i] * step[j] * grey for i, j in PAIRS[len(dims)]], dtype=np.float64)
 
 
 def refusal(phi_name, precision, features):
     """None where spatial Hessians exist, else the refusal text (pure: no GPU, no library)"""
-    if str(phi_name) not in NETS or str(precision) not in PRECISIONS or not 1 <= int(features) <= MAX_FEATURES:
-        return "spatial Hessians exist for fp32 SIREN up to %d features (this net is %s, %s, %d features)" % (
-            MAX_FEATURES, phi_name, precision, int(features))
-    return None
+    return derivative.refusal(NOUN, phi_name, precision, features)
 
 
 def supported(phi_name, precision, features):
@@ -62,11 +54,7 @@ def supported(phi_name, precision, features):
 
 def check_artefact(art):
     """what decompress_hessian supports, checked on the opened artefact before any decode"""
-    why = refusal(art.phi_name, art.precision, art.phi_features)
-    if why is not None:
-        raise ValueError(why)
-    artefact.check_envelope(art, need_minmaxany="the Hessian decode supports the 'minmaxany_a_b' normalisations only (their inverse "
-                                                "is affine in the net's output), not Normalize.name=%s")
+    derivative.check_artefact(art, NOUN)
 
 
 def check_mode(mode):
@@ -193,7 +181,7 @@ def derive(h, mode, chunk=DERIVED_CHUNK, **kw):
     return out.reshape(*h.shape[:-1], *out.shape[1:])
 
 
-# ---- artefact walks (gradient.py's)
+# ---- artefact walks (derivative.py's)
 
 def _block_hessian(art, dims, start, stop, step, device, chunk=None):
     """the scaled components [*extent, cout, nh] (device, float32) of one stored net over the box start:stop:step of the grid `dims`"""
@@ -207,16 +195,8 @@ def _block_hessian(art, dims, start, stop, step, device, chunk=None):
 def decompress_hessian_device(opt, module_path, sideinfos, region=None, step=1, shape=None, mode="components", device="cuda", chunk=None, **kw):
     """decompress_hessian's result as a device tensor"""
     check_mode(mode)
-    art = artefact.open_artefact(opt, module_path, sideinfos)
-    check_artefact(art)
-    dims = art.dims
-    if shape is not None:
-        shape = [int(v) for v in shape]
-        if len(shape) != len(dims) or any(v < 1 for v in shape):
-            raise ValueError("shape %s does not fit the %d spatial axes of the artefact" % (shape, len(dims)))
-        dims = shape
-    start, stop, stp = region_mod.normalize_region(dims, region if region is not None else (slice(None),) * len(dims), step)
-    return derive(_block_hessian(art, dims, start, stop, stp, device, chunk), mode, **kw)
+    h = derivative.single(opt, module_path, sideinfos, region, step, shape, device, functools.partial(_block_hessian, chunk=chunk), NOUN)
+    return derive(h, mode, **kw)
 
 
 def decompress_hessian(opt, module_path, sideinfos, region=None, step=1, shape=None, mode="components", device="cuda", chunk=None, **kw):
@@ -240,27 +220,10 @@ def decompress_hessian(opt, module_path, sideinfos, region=None, step=1, shape=N
 def decompress_divide_hessian_device(opt, orig_sideinfos, module_dir, sideinfos_dir, region=None, step=1, mode="components", device="cuda",
                                      chunk=None, **kw):
     """decompress_divide_hessian's result as a device tensor"""
-    import torch
     check_mode(mode)
-    if isinstance(opt, str):
-        opt = config.load(opt)
-    data_shape, blocks = artefact.divide_blocks(orig_sideinfos, module_dir, sideinfos_dir)
-    dims, cout = data_shape[:-1], data_shape[-1]
-    start, stop, stp = region_mod.normalize_region(dims, region if region is not None else (slice(None),) * len(dims), step)
-    ext = region_mod.extents(start, stop, stp)
-    # every refusal before any decode
-    arts = {b.name: artefact.open_artefact(opt, b.module_path, b.side) for b in blocks}
-    for art in arts.values():
-        check_artefact(art)
-    pair = artefact.first_overlap(blocks, "dhw" if len(dims) == 3 else "hw")
-    if pair is not None:
-        raise ValueError("the blocks %s and %s overlap: merge_divided_data adds overlapping blocks and clips the sum, which has "
-                         "no single net's Hessian; the Hessian decode needs a partition without overlap" % (pair[0].name, pair[1].name))
-    out = torch.zeros((*ext, cout, len(PAIRS[len(dims)])), dtype=torch.float32, device=device)
-    for b, o_lo, o_hi, l_start, l_stop in artefact.meeting(blocks, start, stp, ext):
-        art = arts[b.name]
-        out[tuple(slice(lo, hi) for lo, hi in zip(o_lo, o_hi))] = _block_hessian(art, art.dims, l_start, l_stop, stp, device, chunk)
-    return derive(out, mode, **kw)
+    h = derivative.divide(opt, orig_sideinfos, module_dir, sideinfos_dir, region, step, device, functools.partial(_block_hessian, chunk=chunk),
+                          lambda nd: len(PAIRS[nd]), NOUN)
+    return derive(h, mode, **kw)
 
 
 def decompress_divide_hessian(opt, orig_sideinfos, module_dir, sideinfos_dir, region=None, step=1, mode="components", device="cuda",

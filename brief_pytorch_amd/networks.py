@@ -15,7 +15,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import _lib, gradient, quantize, region
+from . import _lib, gradient, hessian, quantize, region
 
 __all__ = ["SIREN", "FFN", "NeRF", "MFNFourier", "MFNGabor", "SIREN_Pyramid", "SIRENFT", "SIRENPS", "init_phi", "ALLPHI", "ALL_CALC_PHI_FEATURES", "ALL_CALC_PHI_PARAM_COUNT",
            "ALL_CHECK_PARAM_COUNT", "get_nnmodule_param_count"]
@@ -350,6 +350,20 @@ class SIREN:
         (default BOX_CHUNK) through brief_siren_forward_box's offset / n."""
         self._require_gpu()
         self.sync_packed()
+        box, ext, total = self._box_plan(dims, start, stop, step, lo, hi)
+        kind = {"f32": _lib.OUT_F32, "u8": _lib.OUT_U8, "u16": _lib.OUT_U16}[out_kind]
+        dt = {"f32": torch.float32, "u8": torch.uint8, "u16": torch.uint16}[out_kind]
+        if out is None:
+            out = torch.empty((*ext, self.data_channel), dtype=dt, device=self.params.device)
+        elif out.dtype != dt or out.numel() != total * self.data_channel or not out.is_contiguous():
+            raise ValueError("out must be a contiguous %s tensor of %d elements" % (dt, total * self.data_channel))
+        flat = out.view(total, self.data_channel)
+        self._box_chunks(total, chunk, lambda off, cnt: self._abi_forward_box(box, off, cnt, flat[off:off + cnt], kind, scale, vrange))
+        return out
+
+    def _box_plan(self, dims, start, stop, step, lo, hi):
+        """(GridBox, extents, voxel count) of the box start:stop:step of the linspace grid `dims` over [lo, hi]: decode_box's region
+        semantics, for the three box decoders"""
         nd = len(dims)
         per = (lambda v: [v] * nd if v is None or np.isscalar(v) else list(v))
         b, e = per(start), per(stop)
@@ -357,34 +371,30 @@ class SIREN:
             raise ValueError("start / stop need one entry per axis of dims")
         b0, e0, st = region.normalize_region(dims, tuple(slice(x, y) for x, y in zip(b, e)), step)
         ext = region.extents(b0, e0, st)
-        total = int(np.prod(ext))
-        kind = {"f32": _lib.OUT_F32, "u8": _lib.OUT_U8, "u16": _lib.OUT_U16}[out_kind]
-        dt = {"f32": torch.float32, "u8": torch.uint8, "u16": torch.uint16}[out_kind]
-        if out is None:
-            out = torch.empty((*ext, self.data_channel), dtype=dt, device=self.params.device)
-        elif out.dtype != dt or out.numel() != total * self.data_channel or not out.is_contiguous():
-            raise ValueError("out must be a contiguous %s tensor of %d elements" % (dt, total * self.data_channel))
         box = _lib.GridBox()
         box.grid = self._grid(dims, lo, hi)
         for a in range(nd):
             box.start[a], box.step[a], box.extent[a] = b0[a], st[a], ext[a]
+        return box, ext, int(np.prod(ext))
+
+    def _box_chunks(self, total, chunk, call):
+        """call(offset, count) -> status over the box's `total` voxels in runs of at most `chunk` (default BOX_CHUNK)"""
         chunk = int(chunk or self.BOX_CHUNK)
         if chunk < 1:
             raise ValueError("chunk must be >= 1")
-        flat = out.view(total, self.data_channel)
         for off in range(0, total, chunk):
-            cnt = min(chunk, total - off)
-            _lib.check(self._abi_forward_box(box, off, cnt, flat[off:off + cnt], kind, scale, vrange))
-        return out
+            _lib.check(call(off, min(chunk, total - off)))
 
-    # ---- spatial gradients: value and analytic Jacobian with respect to the coordinates (csrc/brief_jac.inc)
-    def _sync_jac(self):
+    # ---- spatial gradients and Hessians: value, analytic Jacobian and analytic second derivatives with respect to the coordinates
+    # (csrc/brief_jac.inc, csrc/brief_hess.inc; one host driver, csrc/brief_jac_host.inc)
+    def _sync_jac(self, decode=gradient):
         """the Jacobian kernel's own fragment buffer, a second derived copy of self.params: allocated on first use, and written anew
         at the head of EVERY gradient call (one launch over the net's size).  A stale copy is the bug this is built against: the
         parameters change under load_state_dict / load_model (.data), torch optimizers, to() and the in-kernel updates of a fit,
-        and a flag would have to follow every one of those writers; a copy that is never reused cannot be stale."""
+        and a flag would have to follow every one of those writers; a copy that is never reused cannot be stale.
+        decode: the module (gradient, hessian) in whose words a net outside the envelope is refused."""
         self._require_gpu()
-        why = gradient.refusal(getattr(type(self), "kind", "SIREN"), self.precision, self.features)
+        why = decode.refusal(getattr(type(self), "kind", "SIREN"), self.precision, self.features)
         if why is not None:
             raise _lib.BriefError(why)
         L = _lib.lib()
@@ -401,53 +411,49 @@ class SIREN:
         """(value [n, cout], jac [n, cout, cin]) at arbitrary device coordinates [n, cin]: the net's output and its analytic Jacobian
         d phi_c / d x_a in coordinate units (with output_act, of the activated output); float32, from brief_siren_jac_forward.
         value is None with want_value=False.  fp32 SIREN up to 1024 features only (BriefError otherwise)."""
-        pk = self._sync_jac()
+        return self._derivatives_at(coords, want_value, True, False)[:2]
+
+    def _derivative_outputs(self, lead, want_value, want_jac, want_hess):
+        """the float32 results [*lead, cout], [*lead, cout, cin] and [*lead, cout, nh] of a derivative decode, None where not wanted"""
         cin, cout = self.coords_channel, self.data_channel
-        c = coords.to(self.params.device, torch.float32).reshape(-1, cin).contiguous()
+        new = (lambda want, *tail: torch.empty((*lead, cout, *tail), dtype=torch.float32, device=self.params.device) if want else None)
+        return new(want_value), new(want_jac, cin), new(want_hess, cin * (cin + 1) // 2)
+
+    def _derivatives_at(self, coords, want_value, want_jac, want_hess):
+        """(value, jac, hess) at the coordinates [n, cin], None where not wanted: spatial_gradient's and spatial_hessian's body.  With
+        want_hess the Hessian kernel runs (brief_siren_hess_forward), else the Jacobian kernel (brief_siren_jac_forward)."""
+        pk = self._sync_jac(hessian if want_hess else gradient)
+        c = coords.to(self.params.device, torch.float32).reshape(-1, self.coords_channel).contiguous()
         n = c.shape[0]
-        value = torch.empty((n, cout), dtype=torch.float32, device=c.device) if want_value else None
-        jac = torch.empty((n, cout, cin), dtype=torch.float32, device=c.device)
+        outs = self._derivative_outputs((n,), want_value, want_jac, want_hess)
         if n:
             b = _lib.BatchDesc(c.data_ptr(), None, None, None, 0, n, 0, 0, 0)
-            _lib.check(_lib.lib().brief_siren_jac_forward(C.byref(self.desc), _lib.ptr(pk), None, C.byref(b), _lib.ptr(value), _lib.ptr(jac),
-                                                          _lib.stream_ptr()))
-        return value, jac
+            entry = _lib.lib().brief_siren_hess_forward if want_hess else _lib.lib().brief_siren_jac_forward
+            _lib.check(entry(C.byref(self.desc), _lib.ptr(pk), None, C.byref(b), *[_lib.ptr(t) for t in outs[:3 if want_hess else 2]],
+                             _lib.stream_ptr()))
+        return outs
+
+    def _derivatives_box(self, dims, start, stop, step, lo, hi, chunk, want_value, want_jac, want_hess):
+        """(value, jac, hess) over a box of the grid `dims`, None where not wanted: decode_gradient_box's and decode_hessian_box's body
+        (decode_box's plan and chunk loop around brief_siren_hess_forward_box with want_hess, else brief_siren_jac_forward_box)"""
+        pk = self._sync_jac(hessian if want_hess else gradient)
+        box, ext, total = self._box_plan(dims, start, stop, step, lo, hi)
+        outs = self._derivative_outputs(ext, want_value, want_jac, want_hess)
+        flat = [None if t is None else t.view(total, *t.shape[len(ext):]) for t in outs[:3 if want_hess else 2]]
+        entry = _lib.lib().brief_siren_hess_forward_box if want_hess else _lib.lib().brief_siren_jac_forward_box
+        self._box_chunks(total, chunk, lambda off, cnt: entry(C.byref(self.desc), _lib.ptr(pk), C.byref(box), off, cnt,
+                                                             *[_lib.ptr(None if t is None else t[off:off + cnt]) for t in flat],
+                                                             _lib.stream_ptr()))
+        return outs
 
     def decode_gradient_box(self, dims, start=None, stop=None, step=1, lo=-1.0, hi=1.0, chunk=None, want_value=True):
         """(jac [*extent, cout, cin], value [*extent, cout] | None) over the box start:stop:step of the linspace grid `dims`, with
         decode_box's region semantics, coordinates (bit for bit) and chunk loop: a box equals the slice of the whole grid's result,
         and neither `chunk` nor a repeat of the call changes a bit.  Coordinate units: per unit of [lo, hi] (gradient.voxel_scale
         converts to grey levels per voxel step)."""
-        pk = self._sync_jac()
-        nd = len(dims)
-        per = (lambda v: [v] * nd if v is None or np.isscalar(v) else list(v))
-        b, e = per(start), per(stop)
-        if len(b) != nd or len(e) != nd:
-            raise ValueError("start / stop need one entry per axis of dims")
-        b0, e0, st = region.normalize_region(dims, tuple(slice(x, y) for x, y in zip(b, e)), step)
-        ext = region.extents(b0, e0, st)
-        total = int(np.prod(ext))
-        cin, cout = self.coords_channel, self.data_channel
-        dev = self.params.device
-        jac = torch.empty((*ext, cout, cin), dtype=torch.float32, device=dev)
-        value = torch.empty((*ext, cout), dtype=torch.float32, device=dev) if want_value else None
-        box = _lib.GridBox()
-        box.grid = self._grid(dims, lo, hi)
-        for a in range(nd):
-            box.start[a], box.step[a], box.extent[a] = b0[a], st[a], ext[a]
-        chunk = int(chunk or self.BOX_CHUNK)
-        if chunk < 1:
-            raise ValueError("chunk must be >= 1")
-        fj = jac.view(total, cout, cin)
-        fv = value.view(total, cout) if want_value else None
-        for off in range(0, total, chunk):
-            cnt = min(chunk, total - off)
-            _lib.check(_lib.lib().brief_siren_jac_forward_box(C.byref(self.desc), _lib.ptr(pk), C.byref(box), off, cnt,
-                                                              _lib.ptr(fv[off:off + cnt]) if want_value else None, _lib.ptr(fj[off:off + cnt]),
-                                                              _lib.stream_ptr()))
+        value, jac, _ = self._derivatives_box(dims, start, stop, step, lo, hi, chunk, want_value, True, False)
         return jac, value
 
-    # ---- spatial Hessians: value, Jacobian and analytic second derivatives with respect to the coordinates (csrc/brief_hess.inc)
     def spatial_hessian(self, coords, want_value=True, want_jac=True):
         """(value [n, cout], jac [n, cout, cin], hess [n, cout, nh]) at arbitrary device coordinates [n, cin]: the net's output, its
         analytic Jacobian and its analytic Hessian d2 phi_c / d x_a d x_b in coordinate units (with output_act, of the activated
@@ -455,28 +461,7 @@ class SIREN:
         order (00, 01, 11) for cin = 2 (hessian.full() expands to the symmetric matrix).  value / jac are None with want_value /
         want_jac False.  fp32 SIREN up to 1024 features only (BriefError otherwise).  The kernel reads the Jacobian decode's
         fragment copy (_sync_jac), written anew at the head of every call."""
-        pk = self._sync_hess()
-        cin, cout = self.coords_channel, self.data_channel
-        nh = cin * (cin + 1) // 2
-        c = coords.to(self.params.device, torch.float32).reshape(-1, cin).contiguous()
-        n = c.shape[0]
-        value = torch.empty((n, cout), dtype=torch.float32, device=c.device) if want_value else None
-        jac = torch.empty((n, cout, cin), dtype=torch.float32, device=c.device) if want_jac else None
-        hess = torch.empty((n, cout, nh), dtype=torch.float32, device=c.device)
-        if n:
-            b = _lib.BatchDesc(c.data_ptr(), None, None, None, 0, n, 0, 0, 0)
-            _lib.check(_lib.lib().brief_siren_hess_forward(C.byref(self.desc), _lib.ptr(pk), None, C.byref(b), _lib.ptr(value), _lib.ptr(jac),
-                                                           _lib.ptr(hess), _lib.stream_ptr()))
-        return value, jac, hess
-
-    def _sync_hess(self):
-        """_sync_jac behind the Hessian decode's own refusal text"""
-        from . import hessian
-        self._require_gpu()
-        why = hessian.refusal(getattr(type(self), "kind", "SIREN"), self.precision, self.features)
-        if why is not None:
-            raise _lib.BriefError(why)
-        return self._sync_jac()
+        return self._derivatives_at(coords, want_value, want_jac, True)
 
     def decode_hessian_box(self, dims, start=None, stop=None, step=1, lo=-1.0, hi=1.0, chunk=None, want_value=False, want_jac=False):
         """hess [*extent, cout, nh] over the box start:stop:step of the linspace grid `dims`, with decode_box's region semantics,
@@ -484,37 +469,7 @@ class SIREN:
         of the call changes a bit.  Coordinate units: per unit of [lo, hi] squared (hessian.voxel_scale converts to grey levels per
         voxel step squared).  With want_value or want_jac the result is (hess, value [*extent, cout] | None, jac [*extent, cout, cin]
         | None)."""
-        pk = self._sync_hess()
-        nd = len(dims)
-        per = (lambda v: [v] * nd if v is None or np.isscalar(v) else list(v))
-        b, e = per(start), per(stop)
-        if len(b) != nd or len(e) != nd:
-            raise ValueError("start / stop need one entry per axis of dims")
-        b0, e0, st = region.normalize_region(dims, tuple(slice(x, y) for x, y in zip(b, e)), step)
-        ext = region.extents(b0, e0, st)
-        total = int(np.prod(ext))
-        cin, cout = self.coords_channel, self.data_channel
-        nh = cin * (cin + 1) // 2
-        dev = self.params.device
-        hess = torch.empty((*ext, cout, nh), dtype=torch.float32, device=dev)
-        value = torch.empty((*ext, cout), dtype=torch.float32, device=dev) if want_value else None
-        jac = torch.empty((*ext, cout, cin), dtype=torch.float32, device=dev) if want_jac else None
-        box = _lib.GridBox()
-        box.grid = self._grid(dims, lo, hi)
-        for a in range(nd):
-            box.start[a], box.step[a], box.extent[a] = b0[a], st[a], ext[a]
-        chunk = int(chunk or self.BOX_CHUNK)
-        if chunk < 1:
-            raise ValueError("chunk must be >= 1")
-        fh = hess.view(total, cout, nh)
-        fv = value.view(total, cout) if want_value else None
-        fj = jac.view(total, cout, cin) if want_jac else None
-        for off in range(0, total, chunk):
-            cnt = min(chunk, total - off)
-            _lib.check(_lib.lib().brief_siren_hess_forward_box(C.byref(self.desc), _lib.ptr(pk), C.byref(box), off, cnt,
-                                                               _lib.ptr(fv[off:off + cnt]) if want_value else None,
-                                                               _lib.ptr(fj[off:off + cnt]) if want_jac else None,
-                                                               _lib.ptr(fh[off:off + cnt]), _lib.stream_ptr()))
+        value, jac, hess = self._derivatives_box(dims, start, stop, step, lo, hi, chunk, want_value, want_jac, True)
         return (hess, value, jac) if want_value or want_jac else hess
 
     def train_step(self, n, targets, idx=None, coords=None, weights=None, grid=None, offset=0,

@@ -119,18 +119,10 @@ def main(argv=None):
     if any(v is not None for v in (args.view_composite, args.view_composite_channel, args.view_background, args.view_composite_bits)):
         _composite_refusals(args)     # every refusal by name, before the GPU path is imported
     if args.hessian is not None:
-        # every refusal by name, before the GPU path is imported
-        if args.hessian not in ("components", "laplacian", "eigenvalues", "vesselness"):
-            raise SystemExit("--hessian %s: unknown mode (components, laplacian, eigenvalues or vesselness)" % args.hessian)
-        for flag, on in (("--mip", args.mip), ("--gradient", args.gradient is not None), ("--view-surface", args.view_surface is not None),
-                         ("--view", args.view is not None)):
-            if on:
-                raise SystemExit("--hessian with %s: each writes a result of its own; ask for one of them" % flag)
-        if os.path.splitext(args.o)[1].lower() != ".npy":
-            raise SystemExit("--hessian writes float32 arrays as .npy only (got %s): Hessian output in image formats is not supported"
-                             % (os.path.splitext(args.o)[1] or "no extension"))
-        if args.shape and os.path.isdir(_paths(args.c)[2]):
-            raise SystemExit("--hessian --shape: resampling is not defined for a DivideTask artefact (every block has its own linspace grid)")
+        why = "each writes a result of its own; ask for one of them"
+        _derivative_refusals(args, "--hessian", args.hessian, ("components", "laplacian", "eigenvalues", "vesselness"), "Hessian",
+                             (("--mip", args.mip, why), ("--gradient", args.gradient is not None, why),
+                              ("--view-surface", args.view_surface is not None, why), ("--view", args.view is not None, why)))
     if args.view is not None:
         _view_refusals(args)          # every refusal by name, before the GPU path is imported
     elif args.view_owner is not None:
@@ -144,16 +136,8 @@ def main(argv=None):
         raise SystemExit("--view-up / --view-mode / --view-spacing / --view-depth-spacing / --view-size / --view-offset / --voxel-size "
                          "describe a --view: give its direction with --view dz,dy,dx")
     if args.gradient is not None:
-        # every refusal by name, before the GPU path is imported
-        if args.gradient not in ("components", "magnitude"):
-            raise SystemExit("--gradient %s: unknown mode (components or magnitude)" % args.gradient)
-        if args.mip:
-            raise SystemExit("--gradient with --mip: a projection of a gradient is not defined here; ask for one of them")
-        if os.path.splitext(args.o)[1].lower() != ".npy":
-            raise SystemExit("--gradient writes float32 arrays as .npy only (got %s): gradient output in image formats is not supported"
-                             % (os.path.splitext(args.o)[1] or "no extension"))
-        if args.shape and os.path.isdir(_paths(args.c)[2]):
-            raise SystemExit("--gradient --shape: resampling is not defined for a DivideTask artefact (every block has its own linspace grid)")
+        _derivative_refusals(args, "--gradient", args.gradient, ("components", "magnitude"), "gradient",
+                             (("--mip", args.mip, "a projection of a gradient is not defined here; ask for one of them"),))
     if args.mip and args.shape:
         from brief_pytorch_amd.mip import SHAPE_REFUSAL
         raise SystemExit("--mip --shape: " + SHAPE_REFUSAL)
@@ -174,9 +158,16 @@ def main(argv=None):
     if args.mip:
         return _mip(args, opt, region, divide)
     if args.gradient is not None:
-        return _gradient(args, opt, region, shape, divide)
+        from brief_pytorch_amd import gradient
+        return _derivative(args, opt, region, shape, divide, "--gradient", args.gradient, "spatial gradient (%s, grey levels per voxel)",
+                           gradient.decompress_gradient_device, gradient.decompress_divide_gradient_device,
+                           gradient.magnitude if args.gradient == "magnitude" else None)
     if args.hessian is not None:
-        return _hessian(args, opt, region, shape, divide)
+        import functools
+        from brief_pytorch_amd import hessian
+        return _derivative(args, opt, region, shape, divide, "--hessian", args.hessian, "Hessian (%s, grey levels per voxel squared)",
+                           functools.partial(hessian.decompress_hessian_device, mode=args.hessian),
+                           functools.partial(hessian.decompress_divide_hessian_device, mode=args.hessian))
     t0 = time.perf_counter()
     if divide:
         if shape is not None:
@@ -431,49 +422,41 @@ def _composite(args, opt, region):
     return 0
 
 
-def _gradient(args, opt, region, shape, divide):
+def _derivative_refusals(args, flag, mode, modes, noun, clashes):
+    """every refusal of --gradient / --hessian by name, before the GPU path is imported; clashes: (other flag, given, why not both)"""
+    if mode not in modes:
+        raise SystemExit("%s %s: unknown mode (%s or %s)" % (flag, mode, ", ".join(modes[:-1]), modes[-1]))
+    for other, on, why in clashes:
+        if on:
+            raise SystemExit("%s with %s: %s" % (flag, other, why))
+    if os.path.splitext(args.o)[1].lower() != ".npy":
+        raise SystemExit("%s writes float32 arrays as .npy only (got %s): %s output in image formats is not supported"
+                         % (flag, os.path.splitext(args.o)[1] or "no extension", noun))
+    if args.shape and os.path.isdir(_paths(args.c)[2]):
+        raise SystemExit("%s --shape: resampling is not defined for a DivideTask artefact (every block has its own linspace grid)" % flag)
+
+
+def _derivative(args, opt, region, shape, divide, flag, mode, what, single, divided, finish=None):
+    """--gradient / --hessian: single / divided are the decode's *_device functions, finish a map of the result on the device"""
     import numpy as np
     import torch
-    from brief_pytorch_amd import gradient
     module, side_path, blocks_dir = _paths(args.c)
     t0 = time.perf_counter()
     try:
         if divide:
-            g = gradient.decompress_divide_gradient_device(opt, side_path, module, blocks_dir, region, args.step)
+            r = divided(opt, side_path, module, blocks_dir, region, args.step)
         else:
-            g = gradient.decompress_gradient_device(opt, module, side_path, region, args.step, shape=shape)
+            r = single(opt, module, side_path, region, args.step, shape=shape)
     except ValueError as e:                                       # a refusal (net class, precision, width, normalisation, overlap, region)
-        raise SystemExit("--gradient: %s" % e)
-    if args.gradient == "magnitude":
-        g = gradient.magnitude(g)                                 # on the device
-    data = g.cpu().numpy()
+        raise SystemExit("%s: %s" % (flag, e))
+    if finish is not None:
+        r = finish(r)                                             # on the device
+    data = r.cpu().numpy()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     np.save(args.o, data)
-    print("%s region %s: spatial gradient (%s, grey levels per voxel), shape %s, dtype %s, decoded in %.3f s -> %s" % (
-        "DivideTask" if divide else "SingleTask", args.region, args.gradient, tuple(data.shape), data.dtype, dt, args.o))
-    return 0
-
-
-def _hessian(args, opt, region, shape, divide):
-    import numpy as np
-    import torch
-    from brief_pytorch_amd import hessian
-    module, side_path, blocks_dir = _paths(args.c)
-    t0 = time.perf_counter()
-    try:
-        if divide:
-            h = hessian.decompress_divide_hessian_device(opt, side_path, module, blocks_dir, region, args.step, mode=args.hessian)
-        else:
-            h = hessian.decompress_hessian_device(opt, module, side_path, region, args.step, shape=shape, mode=args.hessian)
-    except ValueError as e:                                       # a refusal (net class, precision, width, normalisation, overlap, region)
-        raise SystemExit("--hessian: %s" % e)
-    data = h.cpu().numpy()
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    np.save(args.o, data)
-    print("%s region %s: Hessian (%s, grey levels per voxel squared), shape %s, dtype %s, decoded in %.3f s -> %s" % (
-        "DivideTask" if divide else "SingleTask", args.region, args.hessian, tuple(data.shape), data.dtype, dt, args.o))
+    print("%s region %s: %s, shape %s, dtype %s, decoded in %.3f s -> %s" % (
+        "DivideTask" if divide else "SingleTask", args.region, what % mode, tuple(data.shape), data.dtype, dt, args.o))
     return 0
 
 
