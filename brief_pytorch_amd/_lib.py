@@ -97,6 +97,10 @@ class ViewPart(C.Structure):        # brief_view_part
     _fields_ = [("start", C.c_int64 * 3), ("dims", C.c_int64 * 3), ("row0", C.c_int32), ("col0", C.c_int32), ("wrows", C.c_int32), ("wcols", C.c_int32)]
 
 
+class CompositeWindow(C.Structure):  # brief_composite_window
+    _fields_ = [("base", C.c_int64), ("row0", C.c_int32), ("col0", C.c_int32), ("wrows", C.c_int32), ("wcols", C.c_int32)]
+
+
 VIEW_MODE = {"max": 0, "min": 1, "mean": 2, "slice": 3}      # BRIEF_VIEW_MAX .. BRIEF_VIEW_SLICE
 SURFACE_SIDE = {"above": 0, "below": 1}                      # BRIEF_SURFACE_ABOVE, BRIEF_SURFACE_BELOW
 
@@ -135,7 +139,9 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_view_sample_t_host",
            "brief_view_part_clip", "brief_view_part_coords", "brief_view_part_fold", "brief_view_part_clip_host", "brief_view_part_sample_host",
            "brief_siren_hess_forward", "brief_siren_hess_forward_box",
-           "brief_view_composite_fold", "brief_view_composite_finish", "brief_view_composite_host"] \
+           "brief_view_composite_fold", "brief_view_composite_finish", "brief_view_composite_host",
+           "brief_view_composite_part_fold", "brief_view_composite_part_carry", "brief_view_composite_part_gather",
+           "brief_view_composite_part_fold_host", "brief_view_composite_part_carry_host", "brief_view_composite_part_gather_host"] \
     + ["brief_%s_%s" % (prefix, entry) for prefix, _, _ in FAMILIES for entry in FAMILY_ENTRIES]
 
 
@@ -273,6 +279,12 @@ def lib():
     L.brief_view_composite_fold.argtypes = [wp, vp, vp, i64, i64, i64, i64, i32, vp, C.c_int, i32, i32, vp, i32, vp, vp, vp, vp]
     L.brief_view_composite_finish.argtypes = [wp, C.POINTER(i32), vp, vp, vp, vp, vp]
     L.brief_view_composite_host.argtypes = [wp, vp, vp, vp, C.c_int, i32, i32, vp, i32, C.POINTER(i32), vp, vp, vp, vp]
+    L.brief_view_composite_part_fold.argtypes = [wp, pp, vp, vp, i64, i64, i64, i64, i32, vp, C.c_int, i32, i32, vp, i32, vp, vp, vp, vp]
+    L.brief_view_composite_part_carry.argtypes = [wp, vp, i32, i64, vp, vp, vp, vp, vp, vp]
+    L.brief_view_composite_part_gather.argtypes = [wp, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.brief_view_composite_part_fold_host.argtypes = [wp, pp, vp, vp, vp, C.c_int, i32, i32, vp, i32, vp, vp, vp]
+    L.brief_view_composite_part_carry_host.argtypes = [wp, vp, i32, i64, vp, vp, vp, vp, vp]
+    L.brief_view_composite_part_gather_host.argtypes = [wp, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
     _LIB = L
     return L
 

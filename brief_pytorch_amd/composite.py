@@ -8,8 +8,14 @@ a sample's optical depth tau and premultiplied emission come from a table, the p
 transmittance W of that prefix a pure integer function, and a pixel the uint64 sum of W * emission.  The image does not depend on the
 chunking, on the lanes per ray or on the run, bit for bit.
 
-parse_transfer, make_transfer and check_transfer are host arithmetic; composite_host restates the device's fold on the CPU
-(brief_view_composite_host); everything else needs a ROCm GPU (there is no CPU fallback)."""
+The composite of a DivideTask artefact (render_composite_partition, decompress_divide_composite) is the same image over the whole
+volume with one net per block, the nearest block owning a sample: the blocks are marched in separate passes, so the optical depth in
+front of a block's part of a ray is carried across the blocks, and only the parts behind something partly opaque are marched a
+second time (DESIGN.md "Composite view of a partition").
+
+parse_transfer, make_transfer and check_transfer are host arithmetic; composite_host, part_fold_host, part_carry_host and
+part_gather_host restate the device's folds on the CPU (brief_view_composite_host, brief_view_composite_part_*_host); everything else
+needs a ROCm GPU (there is no CPU fallback)."""
 import ctypes as C
 import math
 import os
@@ -25,7 +31,8 @@ DEFAULT_BITS = {"u8": 8, "u16": 12}
 DIVIDE_REFUSAL = ("a composite view of a DivideTask artefact is refused: every block has its own net and is evaluated in a pass of its "
                   "own, and a sample's weight is the transmittance of everything in front of it, a prefix that crosses the blocks of a "
                   "ray; it needs a second pass over the blocks (a follow-up).  Decode the region and render it, or use --view with "
-                  "--view-owner nearest for a projection")
+                  "--view-owner nearest for a projection.  That second pass exists where the ownership rule is named: --view-composite with "
+                  "--view-owner nearest (decompress_divide_composite) renders the composite of the partition")
 
 
 def _kind(out_kind):
@@ -166,6 +173,20 @@ def _background(background):
     return bg
 
 
+def _device_table(tf, kind_name, width, dev):
+    """(the table on the device, its bits): a numpy array is checked (check_transfer), an int32 device tensor of the same form is taken
+    as it is"""
+    import torch
+    if isinstance(tf, torch.Tensor):
+        bits = int(tf.shape[0]).bit_length() - 1 if tf.dim() == 2 else 0
+        if tf.dtype != torch.int32 or tf.dim() != 2 or tf.shape[1] != 4 or tf.shape[0] != 1 << bits or not 1 <= bits <= width or not tf.is_contiguous():
+            raise ValueError("a transfer table is a contiguous int32 [2^bits, 4], bits 1 .. %d for %s data (got %s %s)"
+                             % (width, kind_name, tf.dtype, tuple(tf.shape)))
+        return tf.to(dev), bits
+    t, bits = check_transfer(tf, kind_name)
+    return torch.from_numpy(t).to(dev), bits
+
+
 def render_composite(phi, view, tf, lo, hi, out_kind, scale, vrange, channel=0, background=(0, 0, 0), chunk=None):
     """the composite view of the net `phi` (any net kind and precision its forward entry serves) on the linspace grid view.dims over
     [lo, hi]: (image uint8 [rows, cols, 4] = R, G, B, A, hits [rows, cols] int32, stats) as device tensors.  Channel `channel` of the
@@ -185,15 +206,7 @@ def render_composite(phi, view, tf, lo, hi, out_kind, scale, vrange, channel=0, 
     bg = (C.c_int32 * 3)(*_background(background))
     phi._require_gpu()
     dev = phi.params.device
-    if isinstance(tf, torch.Tensor):
-        bits = int(tf.shape[0]).bit_length() - 1 if tf.dim() == 2 else 0
-        if tf.dtype != torch.int32 or tf.dim() != 2 or tf.shape[1] != 4 or tf.shape[0] != 1 << bits or not 1 <= bits <= width or not tf.is_contiguous():
-            raise ValueError("a transfer table is a contiguous int32 [2^bits, 4], bits 1 .. %d for %s data (got %s %s)"
-                             % (width, kind_name, tf.dtype, tuple(tf.shape)))
-        table = tf.to(dev)
-    else:
-        t, bits = check_transfer(tf, kind_name)
-        table = torch.from_numpy(t).to(dev)
+    table, bits = _device_table(tf, kind_name, width, dev)
     chunk = int(chunk or mip.DEFAULT_CHUNK)
     if chunk < 1:
         raise ValueError("chunk must be >= 1")
@@ -213,6 +226,144 @@ def render_composite(phi, view, tf, lo, hi, out_kind, scale, vrange, channel=0, 
     _lib.check(L.brief_view_composite_finish(C.byref(v), bg, _lib.ptr(hits), _lib.ptr(tau_run), _lib.ptr(acc), _lib.ptr(image), st()))
     stats = {"rays": rays, "rays_hit": rays_hit, "samples_inside": int(hits.sum(dtype=torch.int64).item()), "samples_evaluated": total}
     return image, hits.view(v.rows, v.cols), stats
+
+
+# ---- the composite of a partition: the prefix is carried across blocks (csrc/brief_composite.h "the composite of a PARTITION") --------
+def windows_table(pts):
+    """(the table of brief_composite_window of the block descriptors `pts` (view.make_part's) as a ctypes array, window_rays): block b's
+    slice of the block-major window-ray arrays starts at base[b]; an empty window is 0 x 0"""
+    wins = (_lib.CompositeWindow * len(pts))()
+    at = 0
+    for w, pt in zip(wins, pts):
+        n = int(pt.wrows) * int(pt.wcols)
+        w.base = at
+        w.row0, w.col0, w.wrows, w.wcols = (pt.row0, pt.col0, pt.wrows, pt.wcols) if n else (0, 0, 0, 0)
+        at += n
+    return wins, at
+
+
+_hp = (lambda a: a.ctypes.data_as(C.c_void_p))
+
+
+def part_fold_host(view, part, k0, off, vals, tf, hits_w, tau_w, acc_w, channel=0):
+    """k_composite_part_fold on the host CPU (brief_view_composite_part_fold_host), no GPU call: folds the block's whole list (k0 [wrays]
+    int32, off [wrays + 1] int64 in any numbering, vals [off[-1] - off[0], channels] uint8 | uint16) into the window rays' state
+    hits_w int32 [wrays] (or None), tau_w int32 [wrays] (carry-in, then carry-out) and acc_w uint64 [wrays, 3], IN PLACE"""
+    vals = np.ascontiguousarray(vals)
+    if vals.dtype not in (np.uint8, np.uint16) or vals.ndim != 2:
+        raise ValueError("vals must be uint8 or uint16 [samples, channels] (got %s %s)" % (vals.dtype, vals.shape))
+    kind = "u8" if vals.dtype == np.uint8 else "u16"
+    tf, bits = check_transfer(tf, kind)
+    wrays = int(part.wrows) * int(part.wcols)
+    k0, off = np.ascontiguousarray(k0, np.int32).ravel(), np.ascontiguousarray(off, np.int64).ravel()
+    if len(k0) != wrays or len(off) != wrays + 1:
+        raise ValueError("k0 needs one entry per window ray and off one more (%d window rays; got %d and %d)" % (wrays, len(k0), len(off)))
+    if len(vals) != int(off[-1] - off[0]):
+        raise ValueError("vals holds %d samples, off names %d" % (len(vals), int(off[-1] - off[0])))
+    for a, dt, n in ((hits_w, np.int32, wrays), (tau_w, np.int32, wrays), (acc_w, np.uint64, wrays * 3)):
+        if a is not None and (a.dtype != dt or a.size != n or not a.flags.c_contiguous):
+            raise ValueError("the state of a block is hits_w int32 [wrays], tau_w int32 [wrays], acc_w uint64 [wrays, 3], C-contiguous")
+    if wrays:
+        _lib.check(_lib.lib().brief_view_composite_part_fold_host(
+            C.byref(view), C.byref(part), _hp(k0), _hp(off), _hp(vals), _lib.OUT_U8 if kind == "u8" else _lib.OUT_U16, vals.shape[1], int(channel),
+            _hp(tf), bits, _hp(hits_w) if hits_w is not None else None, _hp(tau_w), _hp(acc_w)))
+
+
+def part_carry_host(view, wins, window_rays, k0, cnt, tau_w):
+    """(carry, cnt2) int32 [window_rays] on the host CPU (brief_view_composite_part_carry_host): per segment the saturated sum of the
+    totals tau_w of the same pixel's segments with a smaller k0, and cnt where 0 < carry < TAU_SAT, else 0"""
+    k0, cnt, tau_w = (np.ascontiguousarray(a, np.int32).ravel() for a in (k0, cnt, tau_w))
+    if not len(k0) == len(cnt) == len(tau_w) == window_rays:
+        raise ValueError("k0, cnt and tau_w need one entry per window ray (%d)" % window_rays)
+    carry, cnt2 = np.zeros(window_rays, np.int32), np.zeros(window_rays, np.int32)
+    _lib.check(_lib.lib().brief_view_composite_part_carry_host(C.byref(view), wins, len(wins), window_rays, _hp(k0), _hp(cnt), _hp(tau_w),
+                                                               _hp(carry), _hp(cnt2)))
+    return carry, cnt2
+
+
+def part_gather_host(view, wins, window_rays, hits_w, tau_w, acc_w, carry, acc_w2):
+    """(hits int32 [rows, cols], tau_run int32 [rows, cols], acc uint64 [rows, cols, 3]) of the image from the window rays' state on the
+    host CPU (brief_view_composite_part_gather_host)"""
+    hits_w, tau_w, carry = (np.ascontiguousarray(a, np.int32).ravel() for a in (hits_w, tau_w, carry))
+    acc_w, acc_w2 = (np.ascontiguousarray(a, np.uint64).ravel() for a in (acc_w, acc_w2))
+    if not len(hits_w) == len(tau_w) == len(carry) == window_rays or not len(acc_w) == len(acc_w2) == 3 * window_rays:
+        raise ValueError("the window rays' state needs one entry per window ray (%d), acc_w and acc_w2 three" % window_rays)
+    rays = view.rows * view.cols
+    hits, tau_run, acc = np.zeros(rays, np.int32), np.zeros(rays, np.int32), np.zeros((rays, 3), np.uint64)
+    _lib.check(_lib.lib().brief_view_composite_part_gather_host(C.byref(view), wins, len(wins), window_rays, _hp(hits_w), _hp(tau_w), _hp(acc_w),
+                                                                _hp(carry), _hp(acc_w2), _hp(hits), _hp(tau_run), _hp(acc)))
+    shape = (view.rows, view.cols)
+    return hits.reshape(shape), tau_run.reshape(shape), acc.reshape(*shape, 3)
+
+
+def render_composite_partition(parts, view, tf, out_kind, channel=0, background=(0, 0, 0), chunk=None):
+    """render_composite for a PARTITION of the grid view.dims: parts is view.render_partition's list of blocks (phi, start, dims, lo, hi,
+    scale, vrange), and the nearest block owns a sample, exactly as there.  Returns (image uint8 [rows, cols, 4] = R, G, B, A, hits
+    [rows, cols] int32, stats) as device tensors: the composite of every pixel's owned samples in ascending k, whichever block owns
+    them, bit for bit what render_composite's fold gives on that list.  A sample in a gap no block covers contributes nothing; a ray
+    that meets no block shows the background with A = 0.
+
+    The blocks are evaluated in separate passes, in no depth order, and a sample's weight is the transmittance of everything in front
+    of it.  Per pixel and block the owned samples are one interval of k, a SEGMENT.  PASS A marches all blocks (view._march_partition)
+    and folds every segment on its own, under carry-in 0, into per-window-ray state: its total T and its colour sums.  The CARRY
+    kernel gives every segment C = min(sum of T over the pixel's segments with a smaller k0, TAU_SAT).  C == 0 (nothing, or only
+    transparent segments, in front): pass A's sums are final.  C == TAU_SAT: the segment is hidden.  PASS B marches only the other
+    segments again, with carry-in C.  The GATHER kernel sums a pixel's segments, and the finish is render_composite's.  All sums are
+    integer sums and the saturation commutes with them, so the order of the blocks, the chunking and the run change no bit.  Memory:
+    one chunk, the per-window-ray state and the image; nothing grows with the samples.
+    stats: view.render_partition's keys, samples_evaluated counting both passes, plus samples_second_pass and segments (non-empty
+    intervals over all pixels and blocks)."""
+    import torch
+    kind_name, width = _kind(out_kind)
+    parts, ch, chunk, pts, vs = view_mod._plan_partition(parts, view, chunk, "render_composite_partition")
+    if int(channel) != channel or not 0 <= int(channel) < ch:
+        raise ValueError("channel %r does not exist: the nets have the channels 0 .. %d" % (channel, ch - 1))
+    channel = int(channel)
+    bg = (C.c_int32 * 3)(*_background(background))
+    dev = parts[0][0].params.device
+    table, bits = _device_table(tf, kind_name, width, dev)
+    L, stream, at_ray = _lib.lib(), _lib.stream_ptr(), view_mod._at_ray
+    rays = view.rows * view.cols
+    kind, dt = (_lib.OUT_U8, torch.uint8) if kind_name == "u8" else (_lib.OUT_U16, torch.uint16)
+    wins, window_rays = windows_table(pts)
+    hits = torch.zeros(rays, dtype=torch.int32, device=dev)
+    tau_run = torch.zeros(rays, dtype=torch.int32, device=dev)
+    acc = torch.zeros((rays, 3), dtype=torch.int64, device=dev)         # (uint64 on the device)
+    p_table = _lib.ptr(table)
+    evaluated = second = blocks_hit = segments = 0
+    if window_rays > 0:
+        hits_w = torch.zeros(window_rays, dtype=torch.int32, device=dev)
+        tau_w = torch.zeros(window_rays, dtype=torch.int32, device=dev)
+        acc_w = torch.zeros((window_rays, 3), dtype=torch.int64, device=dev)
+
+        def fold_into(h, t, a):
+            def fold(i, v, pt, base, k0_b, off_b, s0, s1, r0, r1, lanes, p_vals):
+                _lib.check(L.brief_view_composite_part_fold(v, pt, k0_b, off_b, s0, s1, r0, r1, lanes, p_vals, kind, ch, channel, p_table, bits,
+                                                            at_ray(h, base) if h is not None else None, at_ray(t, base), at_ray(a, base), stream))
+            return fold
+        first = view_mod._march_partition(parts, vs, pts, kind, dt, chunk, fold_into(hits_w, tau_w, acc_w))
+        evaluated, blocks_hit, segments = first["evaluated"], first["blocks_hit"], first["segments"]
+        if evaluated > 0:
+            k0, cnt = first["k0"], first["cnt"]
+            d_wins = torch.frombuffer(bytearray(bytes(wins)), dtype=torch.uint8).to(dev)
+            carry = torch.empty(window_rays, dtype=torch.int32, device=dev)
+            cnt2 = torch.empty(window_rays, dtype=torch.int32, device=dev)
+            v0 = C.byref(vs[0])
+            _lib.check(L.brief_view_composite_part_carry(v0, _lib.ptr(d_wins), len(pts), window_rays, _lib.ptr(k0), _lib.ptr(cnt), _lib.ptr(tau_w),
+                                                         _lib.ptr(carry), _lib.ptr(cnt2), stream))
+            tau_w2 = carry.clone()
+            acc_w2 = torch.zeros((window_rays, 3), dtype=torch.int64, device=dev)
+            second = view_mod._march_partition(parts, vs, pts, kind, dt, chunk, fold_into(None, tau_w2, acc_w2), clipped=(k0, cnt),
+                                               counts=cnt2)["evaluated"]
+            _lib.check(L.brief_view_composite_part_gather(v0, _lib.ptr(d_wins), len(pts), window_rays, _lib.ptr(hits_w), _lib.ptr(tau_w),
+                                                          _lib.ptr(acc_w), _lib.ptr(carry), _lib.ptr(acc_w2), _lib.ptr(hits), _lib.ptr(tau_run),
+                                                          _lib.ptr(acc), stream))
+    image = torch.empty((view.rows, view.cols, 4), dtype=torch.uint8, device=dev)
+    _lib.check(L.brief_view_composite_finish(C.byref(vs[0]), bg, _lib.ptr(hits), _lib.ptr(tau_run), _lib.ptr(acc), _lib.ptr(image), stream))
+    rays_hit, inside = torch.stack([(hits > 0).sum(), hits.sum(dtype=torch.int64)]).cpu().tolist()      # (a ray's range is exact: hit <=> hits > 0)
+    stats = {"rays": rays, "rays_hit": rays_hit, "samples_inside": inside, "samples_evaluated": evaluated + second, "blocks": len(parts),
+             "blocks_hit": blocks_hit, "rays_clipped": window_rays, "samples_second_pass": second, "segments": segments}
+    return image, hits.view(view.rows, view.cols), stats
 
 
 def open_single(opt, module_path, sideinfos):
@@ -238,14 +389,8 @@ def decompress_composite(art, direction, transfer, up=None, region=None, centre=
     Refused by name before any decode: everything view.check_envelope refuses (error-bounded artefacts, 2-D data, dtype,
     normalisation, an axis of length 1), a non-identity postprocess, a channel that does not exist, a background outside 0 .. 255, a
     malformed transfer function; DivideTask artefacts by open_single.  return_hits: (image, hits [rows, cols] int32, stats)."""
-    from .misc import preprocess_is_identity
     view_mod.check_envelope(art, "max")
-    pp = art.postprocess
-    if not preprocess_is_identity(np.zeros(1, np.dtype(art.dtype)), pp.denoise.level, pp.denoise.close, pp.clip):
-        raise ValueError("a composite view with a Decompress.postprocess that changes values is refused: the transfer function classifies "
-                         "the integer decode of every sample, and a threshold or a clip (denoise.level %s, clip %s) does not commute with "
-                         "the compositing; use an identity postprocess and put the threshold into the transfer function"
-                         % (pp.denoise.level, list(pp.clip)))
+    _check_postprocess(art)
     if int(channel) != channel or not 0 <= int(channel) < int(art.cout):
         raise ValueError("channel %r does not exist: the artefact has the channels 0 .. %d" % (channel, int(art.cout) - 1))
     _background(background)
@@ -254,5 +399,58 @@ def decompress_composite(art, direction, transfer, up=None, region=None, centre=
     view = view_mod.make_view(art.dims, direction, up, centre, spacing, depth_spacing, size, depth, voxel_size, region)
     image, hits, stats = render_composite(art.load_phi(device), view, tf, art.lo, art.hi, art.out_kind, art.norm_range, art.vrange,
                                           channel=int(channel), background=background, chunk=chunk)
+    img = image.cpu().numpy()
+    return (img, hits.cpu().numpy(), stats) if return_hits else img
+
+
+def _check_postprocess(art):
+    from .misc import preprocess_is_identity
+    pp = art.postprocess
+    if not preprocess_is_identity(np.zeros(1, np.dtype(art.dtype)), pp.denoise.level, pp.denoise.close, pp.clip):
+        raise ValueError("a composite view with a Decompress.postprocess that changes values is refused: the transfer function classifies "
+                         "the integer decode of every sample, and a threshold or a clip (denoise.level %s, clip %s) does not commute with "
+                         "the compositing; use an identity postprocess and put the threshold into the transfer function"
+                         % (pp.denoise.level, list(pp.clip)))
+
+
+def decompress_divide_composite(opt, orig_sideinfos, module_dir, sideinfos_dir, direction, transfer, up=None, region=None, centre=None, spacing=1.0,
+                                depth_spacing=1.0, size=None, depth=None, voxel_size=(1, 1, 1), channel=0, background=(0, 0, 0), bits=None,
+                                device="cuda", chunk=None, return_hits=False):
+    """decompress_composite for a stored DivideTask artefact (orig_sideinfos: the job's side info, dict or path; module_dir /
+    sideinfos_dir: the blocks' trees), without decoding the volume or any block: the view is a view of the WHOLE volume, `region` and
+    `centre` index it, the nearest block owns a sample (view.decompress_divide_view's rule; nothing is blended across a face), and the
+    prefix of a ray's optical depth is carried across the blocks (render_composite_partition).  transfer, channel, background and bits
+    are decompress_composite's.  Refused by name before any net is opened: per block everything view.check_envelope refuses
+    (error-bounded blocks, dtype, normalisation, an axis of length 1), a Decompress.postprocess that changes values, blocks of
+    different dtypes or channel counts, overlapping blocks, 2-D data, an axis of 2^23 or more, a channel that does not exist, a
+    background outside 0 .. 255, a malformed transfer function.  return_hits: (image, hits [rows, cols] int32, stats)."""
+    from . import artefact, config
+    if isinstance(opt, str):
+        opt = config.load(opt)
+    data_shape, blocks = artefact.divide_blocks(orig_sideinfos, module_dir, sideinfos_dir, one_dtype="the composite view")
+    if len(data_shape) != 4:
+        raise ValueError(view_mod.ENVELOPE["need_3d"] % (len(data_shape) - 1, data_shape))
+    arts = [artefact.open_artefact(opt, b.module_path, b.side) for b in blocks]
+    for art in arts:
+        view_mod.check_envelope(art, "max")
+        _check_postprocess(art)
+    pair = artefact.first_overlap(blocks, "dhw")
+    if pair is not None:
+        raise ValueError("the blocks %s and %s overlap: merge_divided_data adds overlapping blocks, and a sample of a view has one owner; "
+                         "decode the region and render it" % (pair[0].name, pair[1].name))
+    starts = [[b.ranges[a][0] for a in "dhw"] for b in blocks]
+    for b, art in zip(blocks, arts):
+        if art.cout != data_shape[-1] or art.dims != [b.ranges[a][1] - b.ranges[a][0] + 1 for a in "dhw"]:
+            raise ValueError("the block %s holds data of shape %s: not its index range of a volume with %d channels" % (b.name, art.data_shape, data_shape[-1]))
+    if int(channel) != channel or not 0 <= int(channel) < int(data_shape[-1]):
+        raise ValueError("channel %r does not exist: the artefact has the channels 0 .. %d" % (channel, int(data_shape[-1]) - 1))
+    _background(background)
+    out_kind = arts[0].out_kind
+    points = parse_transfer(transfer, out_kind) if isinstance(transfer, str) else transfer
+    tf = make_transfer(points, out_kind, depth_spacing, bits)
+    view = view_mod.make_view(data_shape[:-1], direction, up, centre, spacing, depth_spacing, size, depth, voxel_size, region)
+    view_mod.make_part(view, starts[0], arts[0].dims, "image")    # (the 2^23 rule, before any net is opened)
+    parts = [(art.load_phi(device), s, art.dims, art.lo, art.hi, art.norm_range, art.vrange) for art, s in zip(arts, starts)]
+    image, hits, stats = render_composite_partition(parts, view, tf, out_kind, channel=int(channel), background=background, chunk=chunk)
     img = image.cpu().numpy()
     return (img, hits.cpu().numpy(), stats) if return_hits else img

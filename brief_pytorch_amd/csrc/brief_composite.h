@@ -127,3 +127,76 @@ BRIEF_HD void brief_composite_pixel(uint32_t tau_total, const uint64_t acc[3], c
     const uint64_t a = ((((uint64_t)1 << 32) - w) * 255u + ((uint64_t)1 << 31)) >> 32;
     out[3] = (uint8_t)(a < 255u ? a : 255u);
 }
+
+// ---- the composite of a PARTITION (one net per block, view.render_partition's ownership): carry the prefix across blocks.
+// Per pixel and block the owned samples form one interval of k (brief_view_part_ray_range), a SEGMENT; the segments of a pixel are
+// disjoint, so their k0 order them front to back.  A block's window rays carry the state of its segments: hits_w, tau_w (the
+// segment's saturated total T after the first pass) and acc_w[3] (its colour sums under carry-in 0).  The weight of a sample is
+// W(min(C + L, TAU_SAT)), L the optical depth in front of it inside its own segment and C = min(sum of T over the segments in front,
+// TAU_SAT); the saturation commutes with the sum, so a segment folds on its own once C is known.  C == 0: the first pass is already
+// final.  C == TAU_SAT: the segment contributes nothing.  Otherwise it is folded a second time with carry-in C.
+// The window rays of all blocks lie in one block-major array; brief_composite_window (include/brief_hip.h) names a block's slice of it.
+// The functions below trust the table: bases 0 and then each the end of the slice before, windows inside the image.  The host entries
+// check it entry by entry before they call them; a device table cannot be read before a launch, and a malformed one is undefined behaviour.
+
+// the window ray of pixel (row, col) in the block's slice, or -1 where the window does not hold the pixel
+BRIEF_HD int64_t brief_composite_window_ray(const brief_composite_window &b, int32_t row, int32_t col)
+{
+    const int32_t wr = row - b.row0, wc = col - b.col0;
+    if (wr < 0 || wc < 0 || wr >= b.wrows || wc >= b.wcols) return -1;
+    return b.base + (int64_t)wr * b.wcols + wc;
+}
+
+// the block whose slice holds window ray w, 0 <= w < window_rays: the last one whose base is <= w (an empty window holds no ray)
+BRIEF_HD int32_t brief_composite_window_of(const brief_composite_window *wins, int32_t blocks, int64_t w)
+{
+    int32_t lo = 0, hi = blocks - 1;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi + 1) >> 1;
+        if (wins[mid].base <= w) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// C and the second pass's count of window ray w: C = min(sum of tau_w over the segments of the same pixel with a smaller k0, TAU_SAT)
+BRIEF_HD void brief_composite_carry(const brief_composite_window *wins, int32_t blocks, const int32_t *k0, const int32_t *cnt,
+                                    const int32_t *tau_w, int64_t w, int32_t &carry, int32_t &cnt2)
+{
+    carry = 0;
+    cnt2 = 0;
+    const int32_t n = cnt[w];
+    if (n <= 0) return;
+    const brief_composite_window &own = wins[brief_composite_window_of(wins, blocks, w)];
+    const int64_t i = w - own.base;
+    const int32_t wr = (int32_t)(i / own.wcols);
+    const int32_t row = own.row0 + wr, col = own.col0 + (int32_t)(i - (int64_t)wr * own.wcols), kb = k0[w];
+    uint64_t sum = 0;                                            // at most blocks * TAU_SAT < 2^52
+    for (int32_t b = 0; b < blocks; ++b) {
+        const int64_t x = brief_composite_window_ray(wins[b], row, col);
+        if (x < 0 || x == w) continue;
+        if (cnt[x] > 0 && k0[x] < kb) sum += (uint64_t)(uint32_t)tau_w[x];
+    }
+    carry = (int32_t)(sum < (uint64_t)BRIEF_COMPOSITE_TAU_SAT ? sum : (uint64_t)BRIEF_COMPOSITE_TAU_SAT);
+    cnt2 = carry > 0 && carry < BRIEF_COMPOSITE_TAU_SAT ? n : 0;
+}
+
+// the state of pixel (row, col) from its segments: the first pass's sums where C == 0, the second pass's where 0 < C < TAU_SAT
+BRIEF_HD void brief_composite_gather(const brief_composite_window *wins, int32_t blocks, int32_t row, int32_t col,
+                                     const int32_t *hits_w, const int32_t *tau_w, const uint64_t *acc_w, const int32_t *carry, const uint64_t *acc_w2,
+                                     int32_t &hits, uint32_t &tau_run, uint64_t acc[3])
+{
+    uint64_t t = 0;
+    hits = 0;
+    acc[0] = acc[1] = acc[2] = 0;
+    for (int32_t b = 0; b < blocks; ++b) {
+        const int64_t x = brief_composite_window_ray(wins[b], row, col);
+        if (x < 0) continue;
+        hits += hits_w[x];
+        t += (uint64_t)(uint32_t)tau_w[x];
+        const int32_t c = carry[x];
+        const uint64_t *a = c == 0 ? acc_w + x * 3 : (c < BRIEF_COMPOSITE_TAU_SAT ? acc_w2 + x * 3 : (const uint64_t *)0);
+        if (a)
+            for (int j = 0; j < 3; ++j) acc[j] += a[j];
+    }
+    tau_run = (uint32_t)(t < (uint64_t)BRIEF_COMPOSITE_TAU_SAT ? t : (uint64_t)BRIEF_COMPOSITE_TAU_SAT);
+}

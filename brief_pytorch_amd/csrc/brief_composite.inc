@@ -206,3 +206,251 @@ int brief_view_composite_host(const brief_view_desc *view, const int32_t *k0, co
 }
 
 }   // extern "C"
+
+// ---- composite view of a partition: the prefix is carried across blocks (csrc/brief_composite.h "the composite of a PARTITION";
+// composite.render_composite_partition; DESIGN.md "Composite view of a partition").
+//   k_composite_part_fold    k_composite_fold on one block's list: view_part_ray's walk and k_view_part_fold's exact test (clip box and
+//                            cell).  Its state is indexed by WINDOW ray within the block's slice: hits_w, tau_w (carry-in and carry-out)
+//                            and acc_w[3].  Pass A runs it on zeroed state, pass B over the second-pass counts with tau_w preloaded with C.
+//   k_composite_part_carry   one thread per window ray of all blocks: C and cnt2 (brief_composite_carry), a loop over the table of windows.
+//   k_composite_part_gather  one thread per pixel: the pixel's hits, tau_run and acc from its segments (brief_composite_gather).
+// No atomics: a window ray has one owner in a launch, and the chunks of a block follow each other on one stream.
+template <typename T>
+__global__ __launch_bounds__(256) void k_composite_part_fold(brief_view_desc v, brief_view_part pt, ViewChunk ch, const int32_t *__restrict__ k0,
+                                                             const int64_t *__restrict__ off, const T *__restrict__ vals, int C, CompositeTable tb,
+                                                             const int4 *__restrict__ tf, int32_t *__restrict__ hits_w, int32_t *__restrict__ tau_w,
+                                                             unsigned long long *__restrict__ acc_w)
+{
+    const int G = 1 << ch.lg, sub = threadIdx.x & (G - 1);
+    const int64_t groups = ((int64_t)gridDim.x * blockDim.x) >> ch.lg, nr = ch.r1 - ch.r0;
+    const int64_t iters = (nr + groups - 1) / groups;               // the same for every lane: the butterfly below needs the whole group
+    int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> ch.lg;
+    for (int64_t it = 0; it < iters; ++it, g += groups) {
+        const ViewRay q = view_part_ray(v, pt, ch, off, g).q;
+        const int32_t kb = k0[q.r];
+        uint32_t carry = (uint32_t)tau_w[q.r];                       // (read by the whole group before its lane 0 writes it, below)
+        int n = 0;
+        unsigned long long m[3] = {0, 0, 0};
+        for (int64_t sb = q.lo; sb < q.hi; sb += G) {                // a pass; q.lo and q.hi are the group's: its lanes stay together
+            const int64_t s = sb + sub;
+            int4 e = make_int4(0, 0, 0, 0);
+            if (s < q.hi) {
+                const int32_t k = kb + (int32_t)(s - q.a);
+                const float p0 = brief_view_at(v, 0, q.base[0], k), p1 = brief_view_at(v, 1, q.base[1], k), p2 = brief_view_at(v, 2, q.base[2], k);
+                if (brief_view_inside(v, p0, p1, p2) && brief_view_part_owned(pt, p0, p1, p2)) {
+                    ++n;
+                    e = tf[(int)vals[(s - ch.s0) * C + tb.channel] >> tb.shift];
+                }
+            }
+            uint32_t incl = (uint32_t)e.x;                           // at most G * TAU_SAT <= 2^27: no overflow before the saturation
+            for (int o = 1; o < G; o <<= 1) {
+                const uint32_t y = (uint32_t)__shfl_up((int)incl, o, G);
+                if (sub >= o) incl += y;
+            }
+            const unsigned long long w = brief_composite_w(brief_composite_add(carry, incl - (uint32_t)e.x));
+            m[0] += w * (unsigned long long)(uint32_t)e.y;
+            m[1] += w * (unsigned long long)(uint32_t)e.z;
+            m[2] += w * (unsigned long long)(uint32_t)e.w;
+            carry = brief_composite_add(carry, (uint32_t)__shfl((int)incl, G - 1, G));
+        }
+        for (int o = G >> 1; o >= 1; o >>= 1) {                      // (G is the launch's: every group of the wave takes the same steps)
+            n += __shfl_xor(n, o);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) m[c] += composite_shfl_xor(m[c], o);
+        }
+        if (sub == 0 && n > 0) {                                     // the window ray's owner
+            if (hits_w) hits_w[q.r] += n;
+            tau_w[q.r] = (int32_t)carry;
+            unsigned long long *d = acc_w + q.r * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) d[c] += m[c];
+        }
+    }
+}
+
+struct CompositeWins { const brief_composite_window *wins; int32_t blocks; int64_t window_rays; };
+
+__global__ __launch_bounds__(256) void k_composite_part_carry(CompositeWins t, const int32_t *__restrict__ k0, const int32_t *__restrict__ cnt,
+                                                              const int32_t *__restrict__ tau_w, int32_t *__restrict__ carry, int32_t *__restrict__ cnt2)
+{
+    for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < t.window_rays; w += (int64_t)gridDim.x * blockDim.x) {
+        int32_t c, n;
+        brief_composite_carry(t.wins, t.blocks, k0, cnt, tau_w, w, c, n);
+        carry[w] = c;
+        cnt2[w] = n;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_composite_part_gather(int32_t cols, int64_t rays, CompositeWins t, const int32_t *__restrict__ hits_w,
+                                                               const int32_t *__restrict__ tau_w, const unsigned long long *__restrict__ acc_w,
+                                                               const int32_t *__restrict__ carry, const unsigned long long *__restrict__ acc_w2,
+                                                               int32_t *__restrict__ hits, int32_t *__restrict__ tau_run,
+                                                               unsigned long long *__restrict__ acc)
+{
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rays; r += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t row = (int32_t)(r / cols), col = (int32_t)(r - (int64_t)row * cols);
+        int32_t n;
+        uint32_t run;
+        uint64_t a[3];
+        brief_composite_gather(t.wins, t.blocks, row, col, hits_w, tau_w, (const uint64_t *)acc_w, carry, (const uint64_t *)acc_w2, n, run, a);
+        hits[r] = n;
+        tau_run[r] = (int32_t)run;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[r * 3 + c] = a[c];
+    }
+}
+
+// ---- host side of the partition entries
+static const int64_t kCompositeMaxWindowRays = (int64_t)1 << 46;      // 2^40 rays of up to 2^6 blocks each and more: far above any memory
+
+static int check_composite_wins(const brief_view_desc *view, const void *wins, int32_t blocks, int64_t window_rays, int64_t *rays)
+{
+    if (int rc = check_view(view)) return rc;
+    *rays = (int64_t)view->rows * view->cols;
+    if (*rays > kViewMaxRays) return fail(BRIEF_ERR_INVALID, "view: more than 2^40 rays");
+    if (!wins) return fail(BRIEF_ERR_INVALID, "composite: null table of windows");
+    if (blocks < 1) return fail(BRIEF_ERR_INVALID, "composite: blocks must be >= 1");
+    if (window_rays < 1 || window_rays > kCompositeMaxWindowRays) return fail(BRIEF_ERR_INVALID, "composite: window_rays must be 1 .. 2^46");
+    return 0;
+}
+
+// the table itself, where it is host memory
+static int check_composite_wins_host(const brief_view_desc *view, const brief_composite_window *wins, int32_t blocks, int64_t window_rays)
+{
+    int64_t at = 0;
+    for (int32_t b = 0; b < blocks; ++b) {
+        const brief_composite_window &w = wins[b];
+        if (w.base != at) return fail(BRIEF_ERR_INVALID, "composite: the windows' bases must be 0 and then each the end of the slice before");
+        if (w.wrows < 0 || w.wcols < 0 || (w.wrows == 0) != (w.wcols == 0))
+            return fail(BRIEF_ERR_INVALID, "composite: a window must be at least 1 x 1, or 0 x 0 where the block meets no ray");
+        if (w.wrows > 0 && (w.row0 < 0 || w.col0 < 0 || w.row0 > view->rows - w.wrows || w.col0 > view->cols - w.wcols))
+            return fail(BRIEF_ERR_INVALID, "composite: a block's window must lie inside the image rows x cols");
+        at += (int64_t)w.wrows * w.wcols;
+    }
+    if (at != window_rays) return fail(BRIEF_ERR_INVALID, "composite: the windows must hold window_rays rays together");
+    return 0;
+}
+
+extern "C" {
+
+int brief_view_composite_part_fold(const brief_view_desc *view, const brief_view_part *part, const int32_t *k0, const int64_t *off, int64_t s0,
+                                   int64_t s1, int64_t r0, int64_t r1, int32_t lanes, const void *vals, int elem_kind, int32_t channels,
+                                   int32_t channel, const int32_t *tf, int32_t tf_bits, int32_t *hits_w, int32_t *tau_w, uint64_t *acc_w,
+                                   void *stream)
+{
+    ViewChunk ch;
+    CompositeTable tb;
+    if (int rc = check_view_part_chunk(view, part, k0, off, s0, s1, r0, r1, lanes, &ch)) return rc;
+    if (!vals || !tau_w || !acc_w) return fail(BRIEF_ERR_INVALID, "composite: null buffer (hits_w alone may be NULL)");
+    if (int rc = check_composite_table(elem_kind, channels, channel, tf, tf_bits, &tb)) return rc;
+    const dim3 grid(view_blocks((r1 - r0) << ch.lg)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define COMPOSITE_PART_FOLD(T) hipLaunchKernelGGL((k_composite_part_fold<T>), grid, block, 0, st, *view, *part, ch, k0, off, (const T *)vals, \
+                                                  (int)channels, tb, (const int4 *)tf, hits_w, tau_w, (unsigned long long *)acc_w)
+    if (elem_kind == BRIEF_OUT_U8) COMPOSITE_PART_FOLD(uint8_t); else COMPOSITE_PART_FOLD(uint16_t);
+#undef COMPOSITE_PART_FOLD
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_view_composite_part_carry(const brief_view_desc *view, const brief_composite_window *wins, int32_t blocks, int64_t window_rays,
+                                    const int32_t *k0, const int32_t *cnt, const int32_t *tau_w, int32_t *carry, int32_t *cnt2, void *stream)
+{
+    int64_t rays;
+    if (int rc = check_composite_wins(view, wins, blocks, window_rays, &rays)) return rc;
+    if (!k0 || !cnt || !tau_w || !carry || !cnt2) return fail(BRIEF_ERR_INVALID, "composite: null buffer");
+    const CompositeWins t = {wins, blocks, window_rays};
+    hipLaunchKernelGGL(k_composite_part_carry, dim3(view_blocks(window_rays)), dim3(256), 0, (hipStream_t)stream, t, k0, cnt, tau_w, carry, cnt2);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_view_composite_part_gather(const brief_view_desc *view, const brief_composite_window *wins, int32_t blocks, int64_t window_rays,
+                                     const int32_t *hits_w, const int32_t *tau_w, const uint64_t *acc_w, const int32_t *carry,
+                                     const uint64_t *acc_w2, int32_t *hits, int32_t *tau_run, uint64_t *acc, void *stream)
+{
+    int64_t rays;
+    if (int rc = check_composite_wins(view, wins, blocks, window_rays, &rays)) return rc;
+    if (!hits_w || !tau_w || !acc_w || !carry || !acc_w2 || !hits || !tau_run || !acc) return fail(BRIEF_ERR_INVALID, "composite: null buffer");
+    const CompositeWins t = {wins, blocks, window_rays};
+    hipLaunchKernelGGL(k_composite_part_gather, dim3(view_blocks(rays)), dim3(256), 0, (hipStream_t)stream, view->cols, rays, t, hits_w, tau_w,
+                       (const unsigned long long *)acc_w, carry, (const unsigned long long *)acc_w2, hits, tau_run, (unsigned long long *)acc);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the same fold on the host CPU, sample after sample: no GPU call.  Every buffer is host memory; off has wrows * wcols + 1 entries in
+// any numbering (a slice of one scan over all blocks), vals holds the block's WHOLE list, sample s at s - off[0].
+int brief_view_composite_part_fold_host(const brief_view_desc *view, const brief_view_part *part, const int32_t *k0, const int64_t *off,
+                                        const void *vals, int elem_kind, int32_t channels, int32_t channel, const int32_t *tf, int32_t tf_bits,
+                                        int32_t *hits_w, int32_t *tau_w, uint64_t *acc_w)
+{
+    CompositeTable tb;
+    if (int rc = check_view_part(view, part)) return rc;
+    if (!k0 || !off || !vals || !tau_w || !acc_w) return fail(BRIEF_ERR_INVALID, "composite: null buffer (hits_w alone may be NULL)");
+    if (int rc = check_composite_table(elem_kind, channels, channel, tf, tf_bits, &tb)) return rc;
+    const int64_t wrays = (int64_t)part->wrows * part->wcols;
+    for (int64_t r = 0; r < wrays; ++r) {
+        const int64_t cnt = off[r + 1] - off[r];
+        if (cnt < 0 || k0[r] < 0 || cnt > (int64_t)view->depth - k0[r])
+            return fail(BRIEF_ERR_INVALID, "composite: off must not decrease, and a ray's samples k0 .. k0 + cnt - 1 must lie inside 0 .. depth - 1");
+        if (tau_w[r] < 0 || tau_w[r] > BRIEF_COMPOSITE_TAU_SAT) return fail(BRIEF_ERR_INVALID, "composite: a carry-in tau_w lies outside 0 .. TAU_SAT (32 * 65536)");
+    }
+    for (int64_t r = 0; r < wrays; ++r) {
+        const int32_t wr = (int32_t)(r / part->wcols);
+        const int32_t row = part->row0 + wr, col = part->col0 + (int32_t)(r - (int64_t)wr * part->wcols);
+        float base[3];
+        for (int a = 0; a < 3; ++a) base[a] = brief_view_base(*view, a, row, col);
+        uint32_t run = (uint32_t)tau_w[r];
+        uint64_t sum[3] = {0, 0, 0};
+        int32_t n = 0;
+        for (int64_t s = off[r]; s < off[r + 1]; ++s) {
+            const int32_t k = k0[r] + (int32_t)(s - off[r]);
+            const float p0 = brief_view_at(*view, 0, base[0], k), p1 = brief_view_at(*view, 1, base[1], k), p2 = brief_view_at(*view, 2, base[2], k);
+            if (!(brief_view_inside(*view, p0, p1, p2) && brief_view_part_owned(*part, p0, p1, p2))) continue;
+            ++n;
+            const int64_t at = (s - off[0]) * channels + channel;
+            const int value = elem_kind == BRIEF_OUT_U8 ? (int)((const uint8_t *)vals)[at] : (int)((const uint16_t *)vals)[at];
+            const int32_t *e = tf + 4 * (int64_t)(value >> tb.shift);
+            const uint64_t w = brief_composite_w(run);
+            for (int c = 0; c < 3; ++c) sum[c] += w * (uint64_t)(uint32_t)e[1 + c];
+            run = brief_composite_add(run, (uint32_t)e[0]);
+        }
+        if (n > 0) {
+            if (hits_w) hits_w[r] += n;
+            tau_w[r] = (int32_t)run;
+            for (int c = 0; c < 3; ++c) acc_w[r * 3 + c] += sum[c];
+        }
+    }
+    return 0;
+}
+
+int brief_view_composite_part_carry_host(const brief_view_desc *view, const brief_composite_window *wins, int32_t blocks, int64_t window_rays,
+                                         const int32_t *k0, const int32_t *cnt, const int32_t *tau_w, int32_t *carry, int32_t *cnt2)
+{
+    int64_t rays;
+    if (int rc = check_composite_wins(view, wins, blocks, window_rays, &rays)) return rc;
+    if (!k0 || !cnt || !tau_w || !carry || !cnt2) return fail(BRIEF_ERR_INVALID, "composite: null buffer");
+    if (int rc = check_composite_wins_host(view, wins, blocks, window_rays)) return rc;
+    for (int64_t w = 0; w < window_rays; ++w) brief_composite_carry(wins, blocks, k0, cnt, tau_w, w, carry[w], cnt2[w]);
+    return 0;
+}
+
+int brief_view_composite_part_gather_host(const brief_view_desc *view, const brief_composite_window *wins, int32_t blocks, int64_t window_rays,
+                                          const int32_t *hits_w, const int32_t *tau_w, const uint64_t *acc_w, const int32_t *carry,
+                                          const uint64_t *acc_w2, int32_t *hits, int32_t *tau_run, uint64_t *acc)
+{
+    int64_t rays;
+    if (int rc = check_composite_wins(view, wins, blocks, window_rays, &rays)) return rc;
+    if (!hits_w || !tau_w || !acc_w || !carry || !acc_w2 || !hits || !tau_run || !acc) return fail(BRIEF_ERR_INVALID, "composite: null buffer");
+    if (int rc = check_composite_wins_host(view, wins, blocks, window_rays)) return rc;
+    for (int64_t r = 0; r < rays; ++r) {
+        const int32_t row = (int32_t)(r / view->cols), col = (int32_t)(r - (int64_t)row * view->cols);
+        uint32_t run;
+        brief_composite_gather(wins, blocks, row, col, hits_w, tau_w, acc_w, carry, acc_w2, hits[r], run, acc + r * 3);
+        tau_run[r] = (int32_t)run;
+    }
+    return 0;
+}
+
+}   // extern "C"

@@ -305,6 +305,13 @@ class NFGR:
         from . import composite
         return composite.decompress_composite(composite.open_single(opt, module_path, sideinfos), direction, transfer, **kwargs)
 
+    def decompress_divide_composite(self, orig_sideinfos_path, module_save_dir, sideinfos_save_dir, direction, transfer, opt=None, **kwargs):
+        """the same for a stored DivideTask artefact: the composite of the whole volume in which the nearest block owns a sample and
+        the prefix of a ray is carried across the blocks (composite.decompress_divide_composite)"""
+        from . import composite
+        return composite.decompress_divide_composite(opt if opt is not None else _wrap(self.opt), orig_sideinfos_path, module_save_dir,
+                                                     sideinfos_save_dir, direction, transfer, **{"device": self.device, **kwargs})
+
     # ---- spatial-gradient decode: the analytic Jacobian of the stored net in grey levels per voxel (brief_pytorch_amd/gradient.py)
     @staticmethod
     def decompress_gradient(opt, module_path, sideinfos, region=None, step=1, shape=None, device="cuda"):
@@ -1054,6 +1061,13 @@ def decompress_divide_view(opt, orig_sideinfos, module_dir, sideinfos_dir, direc
     """an orthographic view of a stored DivideTask artefact, the nearest block owning a sample (view.decompress_divide_view); opt: the whole option tree"""
     from . import view
     return view.decompress_divide_view(opt, orig_sideinfos, module_dir, sideinfos_dir, direction, **kwargs)
+
+
+def decompress_divide_composite(opt, orig_sideinfos, module_dir, sideinfos_dir, direction, transfer, **kwargs):
+    """the composite view of a stored DivideTask artefact, the nearest block owning a sample and the prefix carried across the blocks
+    (composite.decompress_divide_composite); opt: the whole option tree"""
+    from . import composite
+    return composite.decompress_divide_composite(opt, orig_sideinfos, module_dir, sideinfos_dir, direction, transfer, **kwargs)
 
 
 def decompress_divide_gradient(opt, orig_sideinfos, module_dir, sideinfos_dir, region=None, step=1, device="cuda"):

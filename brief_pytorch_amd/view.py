@@ -8,7 +8,8 @@ The surface view (render_surface, decompress_surface) folds the same march to th
 crosses a level, refines that hit by bisection and shades it with the net's analytic normal (DESIGN.md "Surface view").
 
 A view of a DivideTask artefact (render_partition, decompress_divide_view) is the same lattice over the whole volume with one net per
-block: the nearest block owns a sample (DESIGN.md "View decode of a partition").
+block: the nearest block owns a sample (DESIGN.md "View decode of a partition").  Its march, _march_partition, also serves the composite
+of a partition (composite.render_composite_partition).
 
 make_view, part_window and make_part are host arithmetic; brief_view_sample_host / brief_view_sample_t_host / brief_view_clip_host and
 brief_view_part_clip_host / brief_view_part_sample_host restate the device's geometry on the CPU; everything else needs a ROCm GPU
@@ -349,30 +350,18 @@ def part_sample_host(view, part, row, col, k):
     return pos, local, coord, inside.astype(bool), owned.astype(bool)
 
 
-def render_partition(parts, view, mode, out_kind, chunk=None):
-    """render for a PARTITION of the grid view.dims: parts is a list of blocks (phi, start, dims, lo, hi, scale, vrange), one net per
-    block on its own linspace grid `dims` over [lo, hi] whose first voxel is `start` in the whole volume, with its own integer
-    epilogue (scale, vrange).  The nearest block owns a sample: a block evaluates exactly the samples inside the clip box whose
-    global position lies in its half-open cell start - 0.5 <= p < start + dims - 0.5, on block-local coordinates (up to half a voxel
-    outside its own grid).  Blocks must not overlap; a sample in a gap no block covers is neither evaluated nor folded.  Returns
-    render's (image, hits, stats); every fold is an integer fold, so the order of the blocks and the chunking change no bit.
+def _at_ray(t, base):
+    """a block's slice of a window-ray array: the pointer to entry `base` of the tensor t"""
+    return C.c_void_p(t.data_ptr() + t.element_size() * t.stride(0) * base)
 
-    All blocks are clipped first, each over its own WINDOW of rays (part_window), into one block-major array; one scan and one read of
-    the per-block totals follow, then block by block the net's own forward entry on chunks of the block's span (a chunk never spans
-    two blocks) and the fold.  A block whose window or total is empty launches nothing after the clip.  The nets may be of different
-    kinds; their channel count must agree.  Memory: one chunk, the window arrays and the accumulators (and the nets themselves).
-    stats: render's keys over the whole image, plus blocks, blocks_hit (blocks that own a sample) and rays_clipped (the windows' sum)."""
-    import torch
+
+def _plan_partition(parts, view, chunk, who):
+    """the checks every view of a partition shares, before any GPU call: (parts, channels, chunk, block descriptors, per-block view
+    descriptors with the block's lo / hi)"""
     from . import mip
-    if mode not in MODES:
-        raise ValueError("view mode %r is not one of %s" % (mode, " | ".join(MODES)))
-    if out_kind not in ("u8", "u16"):
-        raise ValueError("render_partition folds the integer decode only: out_kind must be 'u8' or 'u16' (got %r)" % (out_kind,))
-    if mode == "slice" and view.depth != 1:
-        raise ValueError("mode 'slice' needs a view of one plane (depth 1); this one has %d samples per ray" % view.depth)
     parts = list(parts)
     if not parts:
-        raise ValueError("render_partition needs at least one block")
+        raise ValueError("%s needs at least one block" % who)
     ch = int(parts[0][0].data_channel)
     for phi, *_ in parts:
         if int(phi.coords_channel) != 3:
@@ -392,8 +381,97 @@ def render_partition(parts, view, mode, out_kind, chunk=None):
     pts = [make_part(view, s, n, w) for s, n, w in zip(first.tolist(), size.tolist(), _windows(view, first, size).tolist())]
     for phi, *_ in parts:
         phi._require_gpu()
-    L, stream = _lib.lib(), _lib.stream_ptr()
     vs = [_with_range(view, lo, hi) for _, _, _, lo, hi, _, _ in parts]
+    return parts, ch, chunk, pts, vs
+
+
+def _march_partition(parts, vs, pts, kind, dt, chunk, fold, clipped=None, counts=None):
+    """the part every view of a partition shares, as _march is for the single-net views.  All blocks are clipped, each over its own
+    window, into one block-major array (or `clipped` = (k0, cnt) of an earlier march is taken as it is); ONE scan of the counts (and of
+    the hit flags, for the lanes per ray) and ONE read of the per-block totals follow; then block by block and chunk by chunk the
+    block-local coordinates, the net's own forward entry with the block's integer epilogue, and
+    fold(i, v, pt, base, k0_b, off_b, s0, s1, r0, r1, lanes, p_vals): block i's descriptors, the base of its slice of the window-ray
+    arrays, its slices of k0 and off, the chunk [s0, s1) in off's numbering and its window rays [r0, r1) within the slice.
+    counts: int32 [window_rays], taken instead of the clip's counts (each either the clip's own or 0): the march of a later pass over
+    a subset of the window rays.  Returns a dict: k0, cnt (None without a window ray), edges (the slices' bounds), window_rays,
+    evaluated, blocks_hit, segments (window rays that hold a sample)."""
+    import torch
+    L, stream = _lib.lib(), _lib.stream_ptr()
+    dev, ch = parts[0][0].params.device, int(parts[0][0].data_channel)
+    sizes = [pt.wrows * pt.wcols for pt in pts]
+    edges = [0]
+    for n in sizes:
+        edges.append(edges[-1] + n)
+    window_rays = edges[-1]
+    out = dict(k0=None, cnt=None, edges=edges, window_rays=window_rays, evaluated=0, blocks_hit=0, segments=0)
+    if window_rays == 0:
+        return out
+    if clipped is None:
+        k0, cnt = torch.empty(window_rays, dtype=torch.int32, device=dev), torch.empty(window_rays, dtype=torch.int32, device=dev)
+        for v, pt, base, n in zip(vs, pts, edges, sizes):            # the clip needs no net
+            if n:
+                _lib.check(L.brief_view_part_clip(C.byref(v), C.byref(pt), _at_ray(k0, base), _at_ray(cnt, base), stream))
+    else:
+        k0, cnt = clipped
+    out["k0"], out["cnt"] = k0, cnt
+    n_w = cnt if counts is None else counts
+    # ONE scan of the counts (and of the hit flags, for the lanes per ray) and ONE read of the per-block totals
+    off = torch.zeros((2, window_rays + 1), dtype=torch.int64, device=dev)
+    torch.cumsum(n_w, 0, dtype=torch.int64, out=off[0, 1:])
+    torch.cumsum(n_w > 0, 0, dtype=torch.int64, out=off[1, 1:])
+    at = off[:, torch.tensor(edges, dtype=torch.int64, device=dev)].cpu().tolist()
+    off = off[0]
+    totals = [b - a for a, b in zip(at[0][:-1], at[0][1:])]
+    hit_rays = [b - a for a, b in zip(at[1][:-1], at[1][1:])]
+    evaluated = at[0][-1]
+    out["evaluated"], out["blocks_hit"], out["segments"] = evaluated, sum(1 for t in totals if t > 0), at[1][-1]
+    if evaluated > 0:
+        # the chunks of every block's span, and the window rays that may hold a sample of each, in ONE search and read
+        plan = [(i, s0, min(s0 + chunk, at[0][i + 1])) for i, t in enumerate(totals) if t > 0 for s0 in range(at[0][i], at[0][i + 1], chunk)]
+        cuts = torch.tensor([[p[1] for p in plan], [p[2] for p in plan]], dtype=torch.int64, device=dev)
+        r0s, r1s = torch.stack([torch.searchsorted(off[1:], cuts[0], right=True),      # the first ray that ends behind s0
+                                torch.searchsorted(off[:-1], cuts[1], right=False)]).cpu().tolist()      # ... that starts at or behind s1
+        room = min(chunk, max(totals))
+        coords = torch.empty((room, 3), dtype=torch.float32, device=dev)
+        vals = torch.empty((room, ch), dtype=dt, device=dev)
+        p_coords, p_vals = _lib.ptr(coords), _lib.ptr(vals)
+        block = -1
+        for (i, s0, s1), r0, r1 in zip(plan, r0s, r1s):
+            if i != block:                                       # the block's net, descriptors and slices, once per block
+                block, phi, base = i, parts[i][0], edges[i]
+                phi.sync_packed()
+                v, pt, k0_b, off_b = C.byref(vs[i]), C.byref(pts[i]), _at_ray(k0, base), _at_ray(off, base)
+                lanes = _lanes(totals[i] / hit_rays[i])
+            n = s1 - s0
+            _lib.check(L.brief_view_part_coords(v, pt, k0_b, off_b, s0, s1, r0 - base, r1 - base, lanes, p_coords, stream))
+            b = _lib.BatchDesc(coords.data_ptr(), None, None, None, 0, n, 0, 0, 0)
+            _lib.check(phi._abi_forward(None, b, vals, kind, parts[i][5], parts[i][6], n))
+            fold(i, v, pt, base, k0_b, off_b, s0, s1, r0 - base, r1 - base, lanes, p_vals)
+    return out
+
+
+def render_partition(parts, view, mode, out_kind, chunk=None):
+    """render for a PARTITION of the grid view.dims: parts is a list of blocks (phi, start, dims, lo, hi, scale, vrange), one net per
+    block on its own linspace grid `dims` over [lo, hi] whose first voxel is `start` in the whole volume, with its own integer
+    epilogue (scale, vrange).  The nearest block owns a sample: a block evaluates exactly the samples inside the clip box whose
+    global position lies in its half-open cell start - 0.5 <= p < start + dims - 0.5, on block-local coordinates (up to half a voxel
+    outside its own grid).  Blocks must not overlap; a sample in a gap no block covers is neither evaluated nor folded.  Returns
+    render's (image, hits, stats); every fold is an integer fold, so the order of the blocks and the chunking change no bit.
+
+    All blocks are clipped first, each over its own WINDOW of rays (part_window), into one block-major array; one scan and one read of
+    the per-block totals follow, then block by block the net's own forward entry on chunks of the block's span (a chunk never spans
+    two blocks) and the fold.  A block whose window or total is empty launches nothing after the clip.  The nets may be of different
+    kinds; their channel count must agree.  Memory: one chunk, the window arrays and the accumulators (and the nets themselves).
+    stats: render's keys over the whole image, plus blocks, blocks_hit (blocks that own a sample) and rays_clipped (the windows' sum)."""
+    import torch
+    if mode not in MODES:
+        raise ValueError("view mode %r is not one of %s" % (mode, " | ".join(MODES)))
+    if out_kind not in ("u8", "u16"):
+        raise ValueError("render_partition folds the integer decode only: out_kind must be 'u8' or 'u16' (got %r)" % (out_kind,))
+    if mode == "slice" and view.depth != 1:
+        raise ValueError("mode 'slice' needs a view of one plane (depth 1); this one has %d samples per ray" % view.depth)
+    parts, ch, chunk, pts, vs = _plan_partition(parts, view, chunk, "render_partition")
+    L, stream = _lib.lib(), _lib.stream_ptr()
     dev = parts[0][0].params.device
     rays = view.rows * view.cols
     kind, dt = (_lib.OUT_U8, torch.uint8) if out_kind == "u8" else (_lib.OUT_U16, torch.uint16)
@@ -403,48 +481,12 @@ def render_partition(parts, view, mode, out_kind, chunk=None):
         acc = torch.zeros((rays, ch), dtype=torch.int64, device=dev)
     else:
         acc = torch.full((rays, ch), 0x7FFFFFFF if mode == "min" else 0, dtype=torch.int32, device=dev)
-    sizes = [pt.wrows * pt.wcols for pt in pts]
-    edges = [0]
-    for n in sizes:
-        edges.append(edges[-1] + n)
-    window_rays, evaluated, blocks_hit = edges[-1], 0, 0
-    if window_rays > 0:
-        k0, cnt = torch.empty(window_rays, dtype=torch.int32, device=dev), torch.empty(window_rays, dtype=torch.int32, device=dev)
-        at_ray = lambda t, base: C.c_void_p(t.data_ptr() + t.element_size() * base)      # a block's slice of a window-ray array
-        for v, pt, base, n in zip(vs, pts, edges, sizes):            # the clip needs no net
-            if n:
-                _lib.check(L.brief_view_part_clip(C.byref(v), C.byref(pt), at_ray(k0, base), at_ray(cnt, base), stream))
-        # ONE scan of the counts (and of the hit flags, for the lanes per ray) and ONE read of the per-block totals
-        off = torch.zeros((2, window_rays + 1), dtype=torch.int64, device=dev)
-        torch.cumsum(cnt, 0, dtype=torch.int64, out=off[0, 1:])
-        torch.cumsum(cnt > 0, 0, dtype=torch.int64, out=off[1, 1:])
-        at = off[:, torch.tensor(edges, dtype=torch.int64, device=dev)].cpu().tolist()
-        off = off[0]
-        totals = [b - a for a, b in zip(at[0][:-1], at[0][1:])]
-        hit_rays = [b - a for a, b in zip(at[1][:-1], at[1][1:])]
-        evaluated, blocks_hit = at[0][-1], sum(1 for t in totals if t > 0)
-        if evaluated > 0:
-            # the chunks of every block's span, and the window rays that may hold a sample of each, in ONE search and read
-            plan = [(i, s0, min(s0 + chunk, at[0][i + 1])) for i, t in enumerate(totals) if t > 0 for s0 in range(at[0][i], at[0][i + 1], chunk)]
-            cuts = torch.tensor([[p[1] for p in plan], [p[2] for p in plan]], dtype=torch.int64, device=dev)
-            r0s, r1s = torch.stack([torch.searchsorted(off[1:], cuts[0], right=True),      # the first ray that ends behind s0
-                                    torch.searchsorted(off[:-1], cuts[1], right=False)]).cpu().tolist()      # ... that starts at or behind s1
-            room = min(chunk, max(totals))
-            coords = torch.empty((room, 3), dtype=torch.float32, device=dev)
-            vals = torch.empty((room, ch), dtype=dt, device=dev)
-            p_coords, p_vals, p_hits, p_acc = _lib.ptr(coords), _lib.ptr(vals), _lib.ptr(hits), _lib.ptr(acc)
-            block = -1
-            for (i, s0, s1), r0, r1 in zip(plan, r0s, r1s):
-                if i != block:                                       # the block's net, descriptors and slices, once per block
-                    block, phi, base = i, parts[i][0], edges[i]
-                    phi.sync_packed()
-                    v, pt, k0_b, off_b = C.byref(vs[i]), C.byref(pts[i]), at_ray(k0, base), at_ray(off, base)
-                    lanes = _lanes(totals[i] / hit_rays[i])
-                n = s1 - s0
-                _lib.check(L.brief_view_part_coords(v, pt, k0_b, off_b, s0, s1, r0 - base, r1 - base, lanes, p_coords, stream))
-                b = _lib.BatchDesc(coords.data_ptr(), None, None, None, 0, n, 0, 0, 0)
-                _lib.check(phi._abi_forward(None, b, vals, kind, parts[i][5], parts[i][6], n))
-                _lib.check(L.brief_view_part_fold(v, pt, k0_b, off_b, s0, s1, r0 - base, r1 - base, lanes, p_vals, kind, ch, m, p_hits, p_acc, stream))
+    p_hits, p_acc = _lib.ptr(hits), _lib.ptr(acc)
+
+    def fold(i, v, pt, base, k0_b, off_b, s0, s1, r0, r1, lanes, p_vals):
+        _lib.check(L.brief_view_part_fold(v, pt, k0_b, off_b, s0, s1, r0, r1, lanes, p_vals, kind, ch, m, p_hits, p_acc, stream))
+    march = _march_partition(parts, vs, pts, kind, dt, chunk, fold)
+    window_rays, evaluated, blocks_hit = march["window_rays"], march["evaluated"], march["blocks_hit"]
     image = torch.empty((view.rows, view.cols, ch), dtype=torch.float32 if mode == "mean" else dt, device=dev)
     _lib.check(L.brief_view_finish(C.byref(vs[0]), kind, ch, m, _lib.ptr(hits), _lib.ptr(acc), _lib.ptr(image), stream))
     rays_hit, inside = torch.stack([(hits > 0).sum(), hits.sum(dtype=torch.int64)]).cpu().tolist()      # (a ray's range is exact: hit <=> hits > 0)

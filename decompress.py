@@ -63,8 +63,15 @@ view options that shape the geometry apply; not with `--view-mode` or `--view-of
 integer decode (control points `level:r,g,b,a`, levels strictly ascending and before `Decompress.postprocess`, colours 0 .. 255, `a` the
 opacity over one voxel of depth; linear between the points, constant outside) and composited front to back over `--view-background`,
 in integers: the image does not depend on the chunking or the run.  `.png` holds R,G,B, `.npy` uint8 [rows, cols, 4] = R,G,B,A
-(SingleTask artefacts with an identity postprocess; the view options that shape the geometry apply; not with `--view-mode`,
-`--view-offset`, `--view-surface...`, `--view-owner`, `--mip`, `--gradient`, `--hessian`, `--shape` or `--step`).
+(artefacts with an identity postprocess; the view options that shape the geometry apply; not with `--view-mode`,
+`--view-offset`, `--view-surface...`, `--mip`, `--gradient`, `--hessian`, `--shape` or `--step`).
+
+    python decompress.py -p <run yaml> -c <.../compressed of a DivideTask job> --region :,:,: --view dz,dy,dx --view-composite SPEC --view-owner nearest ... -o out.png|out.npy
+
+`--view-composite SPEC --view-owner nearest` renders the composite of a DivideTask artefact: the nearest block owns a sample, as for
+`--view`, and the optical depth in front of a sample is carried across the blocks of its ray, so the image is the composite of the
+whole volume's samples in depth order, bit for bit independent of the order of the blocks.  Blocks behind something partly opaque are
+evaluated a second time.  Without `--view-owner` a DivideTask artefact is refused; `--view-owner` on a SingleTask artefact is refused.
 """
 import argparse
 import os
@@ -101,7 +108,7 @@ def main(argv=None):
     ap.add_argument("--view-size", default=None, metavar="R,C", help="image size (default: the smallest image that covers the clip box)")
     ap.add_argument("--view-offset", type=float, default=None, help="slice: the plane's offset from the volume's centre along the direction (default 0)")
     ap.add_argument("--view-owner", default=None, metavar="{nearest}",
-                    help="the rule that gives every sample of a --view of a DivideTask artefact its block: nearest (the block whose cell, half a voxel "
+                    help="the rule that gives every sample of a --view (or of a --view --view-composite) of a DivideTask artefact its block: nearest (the block whose cell, half a voxel "
                          "around its index range, holds the sample); without it a DivideTask artefact is refused")
     ap.add_argument("--view-surface", type=int, default=None, metavar="LEVEL", help="render the isosurface of this grey level of the integer decode: first-hit depth and shaded normals")
     ap.add_argument("--view-surface-side", default=None, help="above (value >= LEVEL, default) | below (value <= LEVEL)")
@@ -109,7 +116,8 @@ def main(argv=None):
     ap.add_argument("--view-channel", type=int, default=None, metavar="C", help="the channel the level is tested on (default 0)")
     ap.add_argument("--view-light", default=None, metavar="lz,ly,lx", help="the physical direction the light travels (default: the view direction)")
     ap.add_argument("--view-composite", default=None, metavar="SPEC",
-                    help="render the view through a transfer function, level:r,g,b,a;level:r,g,b,a;... or @file: front-to-back emission-absorption compositing")
+                    help="render the view through a transfer function, level:r,g,b,a;level:r,g,b,a;... or @file: front-to-back emission-absorption compositing "
+                         "(a DivideTask artefact with --view-owner nearest)")
     ap.add_argument("--view-composite-channel", type=int, default=None, metavar="C", help="the channel the transfer function classifies (default 0)")
     ap.add_argument("--view-background", default=None, metavar="r,g,b", help="the colour behind the composite, 0 .. 255 each (default 0,0,0)")
     ap.add_argument("--view-composite-bits", type=int, default=None, metavar="B", help="the transfer table has 2^B rows (default 8 for uint8, 12 for uint16)")
@@ -282,7 +290,7 @@ def _view(args, opt, region, divide):
     if args.view_surface is not None:
         return _surface(args, opt, region)
     if args.view_composite is not None:
-        return _composite(args, opt, region)
+        return _composite(args, opt, region, divide)
     module, side_path, blocks_dir = _paths(args.c)
     t0 = time.perf_counter()
     kw = dict(up=_floats(args.view_up, 3, "--view-up") if args.view_up is not None else None, mode=args.view_mode, region=region,
@@ -357,10 +365,15 @@ def _composite_refusals(args):
                          "with --view-composite SPEC")
     if args.view is None:
         raise SystemExit("--view-composite renders a --view through a transfer function: give the view's direction with --view dz,dy,dx")
+    from brief_pytorch_amd.view import OWNERS
+    divide = os.path.isdir(_paths(args.c)[2])
+    if args.view_owner is not None and divide and args.view_owner not in OWNERS:
+        raise SystemExit("--view-owner %s: unknown rule (%s)" % (args.view_owner, ", ".join(OWNERS)))
     for flag, on in (("--view-mode %s" % args.view_mode, args.view_mode != "max"), ("--view-offset", args.view_offset is not None),
                      ("--view-surface", args.view_surface is not None), ("--view-surface-side", args.view_surface_side is not None),
                      ("--view-refine", args.view_refine is not None), ("--view-channel", args.view_channel is not None),
-                     ("--view-light", args.view_light is not None), ("--view-owner", args.view_owner is not None), ("--mip", args.mip),
+                     ("--view-light", args.view_light is not None),
+                     ("--view-owner", args.view_owner is not None and not (args.view_owner in OWNERS and divide)), ("--mip", args.mip),
                      ("--gradient", args.gradient is not None), ("--hessian", args.hessian is not None), ("--shape", args.shape is not None),
                      ("--step %d" % args.step, args.step != 1)):
         if on:
@@ -381,7 +394,7 @@ def _composite_refusals(args):
         raise SystemExit("--view-composite-channel %d: a channel is 0 or above" % args.view_composite_channel)
     if args.view_composite_bits is not None and not 1 <= args.view_composite_bits <= 16:
         raise SystemExit("--view-composite-bits %d: the transfer table has 2^B rows, B 1 .. 8 for uint8 and 1 .. 16 for uint16" % args.view_composite_bits)
-    if os.path.isdir(_paths(args.c)[2]):
+    if divide and args.view_owner is None:
         raise SystemExit("--view-composite: " + composite.DIVIDE_REFUSAL)
 
 
@@ -391,15 +404,19 @@ def _write_rgb_png(path, rgb):
     write_png(path, rgb[..., ::-1])
 
 
-def _composite(args, opt, region):
+def _composite(args, opt, region, divide):
     import numpy as np
     import torch
-    from brief_pytorch_amd.framework import NFGR
-    module, side_path, _ = _paths(args.c)
+    from brief_pytorch_amd.framework import NFGR, decompress_divide_composite
+    module, side_path, blocks_dir = _paths(args.c)
     t0 = time.perf_counter()
     try:
-        img, hits, stats = NFGR.decompress_composite(
-            opt, module, side_path, _floats(args.view, 3, "--view"), args.view_composite,
+        if divide:                                                # (--view-owner nearest: _composite_refusals refused everything else)
+            render = lambda *a, **kw: decompress_divide_composite(opt, side_path, module, blocks_dir, *a, **kw)
+        else:
+            render = lambda *a, **kw: NFGR.decompress_composite(opt, module, side_path, *a, **kw)
+        img, hits, stats = render(
+            _floats(args.view, 3, "--view"), args.view_composite,
             up=_floats(args.view_up, 3, "--view-up") if args.view_up is not None else None, region=region,
             spacing=args.view_spacing, depth_spacing=args.view_depth_spacing,
             size=[int(x) for x in _floats(args.view_size, 2, "--view-size")] if args.view_size is not None else None,
@@ -417,7 +434,9 @@ def _composite(args, opt, region):
     else:
         data = np.ascontiguousarray(img[..., :3])
         _write_rgb_png(args.o, data)
-    print("SingleTask composite view %s of region %s: image %s, dtype %s, %d of %d rays hit, %d samples evaluated, decoded in %.3f s -> %s" % (
+    print("%s composite view %s of region %s: image %s, dtype %s, %d of %d rays hit, %d samples evaluated, decoded in %.3f s -> %s" % (
+        "DivideTask (%d of %d blocks hit, owner %s, %d samples in the second pass)" % (
+            stats["blocks_hit"], stats["blocks"], args.view_owner, stats["samples_second_pass"]) if divide else "SingleTask",
         args.view, args.region, tuple(data.shape), data.dtype, stats["rays_hit"], stats["rays"], stats["samples_evaluated"], dt, args.o))
     return 0
 

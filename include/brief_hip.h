@@ -718,6 +718,55 @@ int brief_view_composite_host(const brief_view_desc *view, const int32_t *k0, co
                               int32_t channel, const int32_t *tf, int32_t tf_bits, const int32_t *background, int32_t *hits, int32_t *tau_run,
                               uint64_t *acc, uint8_t *out);
 
+/* ---- composite view of a partition: the prefix is carried across blocks (csrc/brief_composite.inc, .h) -----------------------------
+ * The view of a partition is brief_view_part_*'s: per pixel and block the owned samples are one interval of k, a SEGMENT; a pixel's
+ * segments are disjoint and their k0 order them front to back.  The image is the composite above over a pixel's owned samples in
+ * ascending k, whichever block owns them: the weight of a sample is W(min(C + L, TAU_SAT)), L the optical depth in front of it inside
+ * its own segment, C = min(sum of the totals T of the segments in front, TAU_SAT).  The blocks are evaluated in separate passes, in no
+ * depth order, so the state lives per WINDOW RAY (k0, cnt and off's numbering), in block-major arrays over the windows of all blocks:
+ *   brief_view_composite_part_fold    brief_view_composite_fold on a block's list with brief_view_part_fold's exact test (clip box and
+ *                                     cell); lane 0 of a ray's group does one plain read-modify-write of hits_w[w] (int32; may be NULL),
+ *                                     tau_w[w] (int32: the carry-in, then the carry-out) and acc_w[w][3] (uint64), w the window ray within
+ *                                     the block's slice.  PASS A: all state 0; it leaves T = tau_w and the colour sums under carry-in 0;
+ *   brief_view_composite_part_carry   one thread per window ray of all blocks: carry[w] = C over the segments of the same pixel with a
+ *                                     smaller k0, and cnt2[w] = cnt[w] where 0 < C < TAU_SAT, else 0.  wins: the DEVICE table of the
+ *                                     blocks' windows and slice bases (base[0] = 0, base[b + 1] = base[b] + wrows * wcols of b, the
+ *                                     last one ending at window_rays; an empty window has wrows = wcols = 0);
+ *   PASS B                            the same march and fold over the scan of cnt2, tau_w2 preloaded with carry, acc_w2 zeroed: only
+ *                                     segments behind something partly opaque are evaluated a second time (C == 0: pass A is final;
+ *                                     C == TAU_SAT: nothing is visible);
+ *   brief_view_composite_part_gather  one thread per pixel, over the blocks whose window holds it: hits = sum of hits_w, tau_run = the
+ *                                     saturated sum of tau_w (pass A's), acc = sum of acc_w where carry == 0 and of acc_w2 where
+ *                                     0 < carry < TAU_SAT; hits, tau_run, acc are per image ray, for brief_view_composite_finish.
+ * Integers throughout, and the carry follows k0, not the order of the blocks: the image does not depend on that order, on chunking,
+ * `lanes` or the run.  No atomics: a window ray has one owner in a launch, and a block's chunks follow each other on one stream.
+ * The *_host entries are the same arithmetic on the host CPU, without any GPU call: every buffer is host memory; the fold's vals holds
+ * the block's whole list (sample s at s - off[0]); the table of windows is checked entry by entry there.  A DEVICE table cannot be read
+ * before a launch: the device entries trust it, and a malformed one is undefined behaviour.
+ * Limits (BRIEF_ERR_INVALID with a message naming the limit, before any launch): those of brief_view_part_fold and
+ * brief_view_composite_fold; no null buffer (hits_w of the fold excepted); blocks >= 1; window_rays >= 1. */
+typedef struct {
+    int64_t base;                            /* the first entry of the block's slice of the window-ray arrays */
+    int32_t row0, col0, wrows, wcols;        /* the block's window (brief_view_part's) */
+} brief_composite_window;
+int brief_view_composite_part_fold(const brief_view_desc *view, const brief_view_part *part, const int32_t *k0, const int64_t *off, int64_t s0,
+                                   int64_t s1, int64_t r0, int64_t r1, int32_t lanes, const void *vals, int elem_kind, int32_t channels,
+                                   int32_t channel, const int32_t *tf, int32_t tf_bits, int32_t *hits_w, int32_t *tau_w, uint64_t *acc_w,
+                                   void *stream);
+int brief_view_composite_part_carry(const brief_view_desc *view, const brief_composite_window *wins, int32_t blocks, int64_t window_rays,
+                                    const int32_t *k0, const int32_t *cnt, const int32_t *tau_w, int32_t *carry, int32_t *cnt2, void *stream);
+int brief_view_composite_part_gather(const brief_view_desc *view, const brief_composite_window *wins, int32_t blocks, int64_t window_rays,
+                                     const int32_t *hits_w, const int32_t *tau_w, const uint64_t *acc_w, const int32_t *carry,
+                                     const uint64_t *acc_w2, int32_t *hits, int32_t *tau_run, uint64_t *acc, void *stream);
+int brief_view_composite_part_fold_host(const brief_view_desc *view, const brief_view_part *part, const int32_t *k0, const int64_t *off,
+                                        const void *vals, int elem_kind, int32_t channels, int32_t channel, const int32_t *tf, int32_t tf_bits,
+                                        int32_t *hits_w, int32_t *tau_w, uint64_t *acc_w);
+int brief_view_composite_part_carry_host(const brief_view_desc *view, const brief_composite_window *wins, int32_t blocks, int64_t window_rays,
+                                         const int32_t *k0, const int32_t *cnt, const int32_t *tau_w, int32_t *carry, int32_t *cnt2);
+int brief_view_composite_part_gather_host(const brief_view_desc *view, const brief_composite_window *wins, int32_t blocks, int64_t window_rays,
+                                          const int32_t *hits_w, const int32_t *tau_w, const uint64_t *acc_w, const int32_t *carry,
+                                          const uint64_t *acc_w2, int32_t *hits, int32_t *tau_run, uint64_t *acc);
+
 /* ---- Hessian decode of an fp32 SIREN (csrc/brief_hess.inc) ------------------------------------------------------------------------
  * value[n][cout] and jac[n][cout][cin] as brief_siren_jac_forward gives them, and hess[n][cout][nh] = d2 phi_c / d x_a d x_b (x_n), the
  * analytic second derivatives with respect to the coordinates in coordinate units; with output_act, of the activated output.  nh = 6 in
