@@ -141,7 +141,9 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_siren_hess_forward", "brief_siren_hess_forward_box",
            "brief_view_composite_fold", "brief_view_composite_finish", "brief_view_composite_host",
            "brief_view_composite_part_fold", "brief_view_composite_part_carry", "brief_view_composite_part_gather",
-           "brief_view_composite_part_fold_host", "brief_view_composite_part_carry_host", "brief_view_composite_part_gather_host"] \
+           "brief_view_composite_part_fold_host", "brief_view_composite_part_carry_host", "brief_view_composite_part_gather_host",
+           "brief_surface_part_fold", "brief_surface_part_route", "brief_surface_part_coords", "brief_surface_part_step", "brief_surface_part_shade",
+           "brief_surface_part_route_host", "brief_view_part_sample_t_host"] \
     + ["brief_%s_%s" % (prefix, entry) for prefix, _, _ in FAMILIES for entry in FAMILY_ENTRIES]
 
 
@@ -285,6 +287,13 @@ def lib():
     L.brief_view_composite_part_fold_host.argtypes = [wp, pp, vp, vp, vp, C.c_int, i32, i32, vp, i32, vp, vp, vp]
     L.brief_view_composite_part_carry_host.argtypes = [wp, vp, i32, i64, vp, vp, vp, vp, vp]
     L.brief_view_composite_part_gather_host.argtypes = [wp, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.brief_surface_part_fold.argtypes = [wp, pp, vp, vp, i64, i64, i64, i64, i32, vp, C.c_int, i32, i32, i32, i32, vp, vp, vp]
+    L.brief_surface_part_route.argtypes = [wp, vp, i32, vp, vp, i32, vp, vp]
+    L.brief_surface_part_coords.argtypes = [wp, pp, vp, vp, i32, vp, i64, vp, vp, vp]
+    L.brief_surface_part_step.argtypes = [vp, i64, vp, C.c_int, i32, i32, i32, i32, vp, vp, vp]
+    L.brief_surface_part_shade.argtypes = [vp, i64, vp, vp, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp, vp]
+    L.brief_surface_part_route_host.argtypes = [wp, vp, i32, vp, vp, i32, vp]
+    L.brief_view_part_sample_t_host.argtypes = [wp, pp, vp, vp, vp, i64, vp, vp, vp, vp, vp]
     _LIB = L
     return L
 

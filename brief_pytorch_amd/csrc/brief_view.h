@@ -196,3 +196,34 @@ BRIEF_HD void brief_view_part_ray_range(const brief_view_desc &v, const brief_vi
     cnt = e > b ? e - b : 0;
     k0 = cnt ? b : 0;
 }
+
+// ---- the surface view of a PARTITION: every point the refinement evaluates, and the hit itself, is ROUTED to the block that owns it.
+// The depth a round evaluates is the surface view's: the midpoint of a bracket (brief_view_mid) where t_lo < t_hi and the round asks for
+// it, else t_hi (the hit; NaN without one).  The point's owner is found by the same half-open cell test on the same global float
+// p_a = brief_view_at_t(...) that gives a sample its owner (brief_view_part_owned): a point exactly on a face s - 0.5 belongs to the
+// UPPER block, and a point no block's cell holds (a pruned block's gap) has no owner, -1.  The gap rule `empty`: such a point holds
+// nothing, it fails the side test on either side, so an unowned midpoint becomes the new t_lo.
+BRIEF_HD float brief_view_surface_t(float t_lo, float t_hi, bool mid) { return mid && t_lo < t_hi ? brief_view_mid(t_lo, t_hi) : t_hi; }
+
+// the index of the block among parts[0 .. nparts) whose cell holds p, -1 if none does (the first one, should cells overlap)
+BRIEF_HD int32_t brief_view_part_owner(const brief_view_part *parts, int32_t nparts, float p0, float p1, float p2)
+{
+    for (int32_t b = 0; b < nparts; ++b)
+        if (brief_view_part_owned(parts[b], p0, p1, p2)) return b;
+    return -1;
+}
+
+// one ray's routing: the owner of its point at brief_view_surface_t(t_lo, t_hi, mid), -1 where the ray has nothing to evaluate (NaN;
+// with mid, not t_lo < t_hi; with mid, a point in a gap, and then t_lo becomes the midpoint)
+BRIEF_HD int32_t brief_view_part_route(const brief_view_desc &v, const brief_view_part *parts, int32_t nparts, int32_t row, int32_t col, float &t_lo,
+                                       float t_hi, bool mid)
+{
+    if (mid && !(t_lo < t_hi)) return -1;
+    const float t = brief_view_surface_t(t_lo, t_hi, mid);
+    if (!(t == t)) return -1;
+    const int32_t o = brief_view_part_owner(parts, nparts, brief_view_at_t(v, 0, brief_view_base(v, 0, row, col), t),
+                                            brief_view_at_t(v, 1, brief_view_base(v, 1, row, col), t),
+                                            brief_view_at_t(v, 2, brief_view_base(v, 2, row, col), t));
+    if (mid && o < 0) t_lo = t;
+    return o;
+}

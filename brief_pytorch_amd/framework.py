@@ -296,6 +296,13 @@ class NFGR:
         from . import view
         return view.decompress_surface(view.open_single(opt, module_path, sideinfos), direction, level, **kwargs)
 
+    def decompress_divide_surface(self, orig_sideinfos_path, module_save_dir, sideinfos_save_dir, direction, level, opt=None, **kwargs):
+        """the same for a stored DivideTask artefact: the isosurface of the whole volume in which the nearest block owns a sample and
+        every refinement point and hit is routed to the block that owns it (view.decompress_divide_surface)"""
+        from . import view
+        return view.decompress_divide_surface(opt if opt is not None else _wrap(self.opt), orig_sideinfos_path, module_save_dir, sideinfos_save_dir,
+                                              direction, level, **{"device": self.device, **kwargs})
+
     @staticmethod
     def decompress_composite(opt, module_path, sideinfos, direction, transfer, **kwargs):
         """the composite view of a stored SingleTask artefact as a numpy image uint8 [rows, cols, 4] = R, G, B, A: direct volume rendering
@@ -1061,6 +1068,13 @@ def decompress_divide_view(opt, orig_sideinfos, module_dir, sideinfos_dir, direc
     """an orthographic view of a stored DivideTask artefact, the nearest block owning a sample (view.decompress_divide_view); opt: the whole option tree"""
     from . import view
     return view.decompress_divide_view(opt, orig_sideinfos, module_dir, sideinfos_dir, direction, **kwargs)
+
+
+def decompress_divide_surface(opt, orig_sideinfos, module_dir, sideinfos_dir, direction, level, **kwargs):
+    """the isosurface view of a stored DivideTask artefact, the nearest block owning a sample and every refinement point and hit routed to
+    the block that owns it (view.decompress_divide_surface); opt: the whole option tree"""
+    from . import view
+    return view.decompress_divide_surface(opt, orig_sideinfos, module_dir, sideinfos_dir, direction, level, **kwargs)
 
 
 def decompress_divide_composite(opt, orig_sideinfos, module_dir, sideinfos_dir, direction, transfer, **kwargs):

@@ -9,10 +9,12 @@ crosses a level, refines that hit by bisection and shades it with the net's anal
 
 A view of a DivideTask artefact (render_partition, decompress_divide_view) is the same lattice over the whole volume with one net per
 block: the nearest block owns a sample (DESIGN.md "View decode of a partition").  Its march, _march_partition, also serves the composite
-of a partition (composite.render_composite_partition).
+of a partition (composite.render_composite_partition) and its surface view (render_surface_partition, decompress_divide_surface: every
+refinement point and the hit are routed to the block that owns them; DESIGN.md "Surface view of a partition").
 
-make_view, part_window and make_part are host arithmetic; brief_view_sample_host / brief_view_sample_t_host / brief_view_clip_host and
-brief_view_part_clip_host / brief_view_part_sample_host restate the device's geometry on the CPU; everything else needs a ROCm GPU
+make_view, part_window and make_part are host arithmetic; brief_view_sample_host / brief_view_sample_t_host / brief_view_clip_host,
+brief_view_part_clip_host / brief_view_part_sample_host / brief_view_part_sample_t_host and brief_surface_part_route_host restate the
+device's geometry on the CPU; everything else needs a ROCm GPU
 (there is no CPU fallback)."""
 import ctypes as C
 import math
@@ -28,7 +30,8 @@ MAX_COUNT = 1 << 24          # rows, cols and depth travel as floats
 OWNERS = ("nearest",)
 DIVIDE_REFUSAL = ("view decode of a DivideTask artefact is refused unless the ownership rule is named: every block has its own net and "
                   "coordinate grid, and a sample between two blocks needs an owner; ask for --view-owner nearest "
-                  "(decompress_divide_view: the nearest block owns a sample).  The surface view of a partition is a follow-up")
+                  "(decompress_divide_view: the nearest block owns a sample; nothing is blended across a face, that is a follow-up).  "
+                  "The surface view of a partition also asks for its gap rule, --view-surface-gap empty (decompress_divide_surface)")
 PART_MAX_DIM = 1 << 23       # a block's cell bounds s - 0.5 and e + 0.5 are exact floats below it
 
 
@@ -614,6 +617,198 @@ def render_surface(phi, view, level, lo, hi, out_kind, scale, vrange, channel=0,
             "t": t_hi.view(shape), "position": pos.view(*shape, 3), "normal": normal, "shade": shade, "hits": hits.view(shape), "stats": stats}
 
 
+# ---- surface view of a partition: hits are routed across blocks (csrc/brief_view.h "the surface view of a PARTITION") ----------------
+GAPS = ("empty",)
+
+
+def _check_gap(gap):
+    if gap not in GAPS:
+        raise ValueError("gap %r is not a gap rule of the surface view of a partition (%s): 'empty' is the only one, a point no block "
+                         "owns holds nothing and fails the side test on either side" % (gap, " | ".join(GAPS)))
+
+
+def _part_array(pts):
+    """a ctypes array of brief_view_part from a list of descriptors (empty windows allowed: the route does not read them)"""
+    arr = (_lib.ViewPart * len(pts))()
+    for i, pt in enumerate(pts):
+        arr[i] = pt
+    return arr
+
+
+def part_sample_t_host(view, part, row, col, t):
+    """part_sample_host at real depths t (float32, 0 <= t <= depth - 1): (pos, local, coord [n, 3] float32, inside, owned [n] bool) of
+    the points the refinement of a surface evaluates for the block (brief_view_part_sample_t_host); at an integer t it is
+    part_sample_host's sample k = t, bit for bit"""
+    row, col = (np.ascontiguousarray(x, np.int32).ravel() for x in (row, col))
+    t = np.ascontiguousarray(t, np.float32).ravel()
+    n = len(row)
+    if len(col) != n or len(t) != n:
+        raise ValueError("row, col and t must have one entry per sample")
+    pos, local, coord = (np.empty((n, 3), np.float32) for _ in range(3))
+    inside, owned = np.empty(n, np.uint8), np.empty(n, np.uint8)
+    if part.wrows < 1 or part.wcols < 1:
+        part = make_part(view, list(part.start), list(part.dims), "image")
+    p = (lambda a: a.ctypes.data_as(C.c_void_p))
+    _lib.check(_lib.lib().brief_view_part_sample_t_host(C.byref(view), C.byref(part), p(row), p(col), p(t), n, p(pos), p(local), p(coord), p(inside),
+                                                        p(owned)))
+    return pos, local, coord, inside.astype(bool), owned.astype(bool)
+
+
+def route_host(view, pts, t_lo, t_hi, midpoint):
+    """(owner int32 [rows, cols], t_lo float32 [rows, cols]) of one routing round on the host CPU (brief_surface_part_route_host): the
+    index in `pts` (block descriptors) of the block that owns every ray's point at the bracket's midpoint (midpoint=True) or at t_hi,
+    -1 where the ray has nothing to evaluate, and t_lo moved to the midpoint where that point lies in a gap"""
+    shape = (view.rows, view.cols)
+    lo = np.array(t_lo, np.float32).reshape(shape).copy()
+    hi = np.ascontiguousarray(np.array(t_hi, np.float32).reshape(shape))
+    owner = np.empty(shape, np.int32)
+    arr = _part_array(pts)
+    p = (lambda a: a.ctypes.data_as(C.c_void_p))
+    _lib.check(_lib.lib().brief_surface_part_route_host(C.byref(view), C.cast(arr, C.c_void_p), len(pts), p(lo), p(hi), int(bool(midpoint)), p(owner)))
+    return owner, lo
+
+
+def render_surface_partition(parts, view, level, out_kind, channel=0, side="above", refine=8, shading=True, light=None, voxel_size=(1, 1, 1),
+                             gap="empty", chunk=None):
+    """render_surface for a PARTITION of the grid view.dims (parts: render_partition's blocks (phi, start, dims, lo, hi, scale, vrange)).
+    The march is render_partition's: the nearest block owns a sample, and first is the smallest owned inside k whose value passes the
+    side test, a min over all blocks.  The bracket is (first - 1, first) where first is behind the ray's first sample inside the clip
+    box, whether sample first - 1 is owned or lies in a gap; a CUT ray (first is that first sample) has none.  A bracket can straddle
+    a face, so every refinement point, and the hit itself, is ROUTED: its owner is the block whose half-open cell holds its global
+    position (a point exactly on a face belongs to the upper block), evaluated on that block's local coordinates with its own integer
+    epilogue.  gap 'empty' (the only rule): a point no block owns holds nothing, it fails the test on either side.  Returns
+    render_surface's dict, and
+        owner     int32 [rows, cols]: the index in `parts` of the block that owns the hit, -1 without one
+        normal, shade  from the OWNER's analytic Jacobian at the hit, scaled by the owner's own gradient.voxel_scale(block dims, lo, hi,
+                  scale, vrange) / voxel_size; refused by name before any decode if any block's net has no Jacobian kernel
+                  (shading=False then serves blocks of mixed kinds).  light: default the view's own direction ddepth
+        stats     render_surface's keys (refine_points: the points the refinement evaluated) plus blocks, blocks_hit, rays_clipped,
+                  rays_straddle (rays whose initial bracket's two ends have different owners, or an unowned lower end) and
+                  refine_launch_blocks (the sum over the rounds of the blocks that received a point)
+    A round is one route launch, one bucketing of the rays by owner (a stable sort and a count, ONE host read), and per block that
+    received points coords -> the net's forward entry -> step, in lists of at most mip.DEFAULT_CHUNK; a block without points launches
+    nothing.  Every decision compares decoded integers: first, t_lo, t_hi and owner do not depend on the order of the blocks, on
+    chunking or on the run."""
+    import torch
+    from . import gradient, mip
+    _check_gap(gap)
+    if out_kind not in ("u8", "u16"):
+        raise ValueError("render_surface_partition tests the integer decode only: out_kind must be 'u8' or 'u16' (got %r)" % (out_kind,))
+    parts = list(parts)
+    if not parts:
+        raise ValueError("render_surface_partition needs at least one block")
+    level, channel, refine = check_surface(level, channel, side, refine, int(parts[0][0].data_channel), out_kind)
+    if shading:
+        for phi, start, *_ in parts:
+            why = gradient.refusal(getattr(type(phi), "kind", "SIREN"), phi.precision, phi.features)
+            if why is not None:
+                raise ValueError("normals and shading need the analytic Jacobian of every block's net, and the block at %s has none: %s; ask "
+                                 "for shading=False" % ([int(x) for x in start], why))
+    vs3 = _vec3(voxel_size, "voxel_size")
+    if (vs3 <= 0).any():
+        raise ValueError("voxel_size must be positive on every axis (got %r)" % (tuple(voxel_size),))
+    parts, ch, chunk, pts, vs = _plan_partition(parts, view, chunk, "render_surface_partition")
+    L, stream = _lib.lib(), _lib.stream_ptr()
+    dev, rays, nb = parts[0][0].params.device, view.rows * view.cols, len(parts)
+    kind, dt = (_lib.OUT_U8, torch.uint8) if out_kind == "u8" else (_lib.OUT_U16, torch.uint16)
+    sd = _lib.SURFACE_SIDE[side]
+    hits = torch.zeros(rays, dtype=torch.int32, device=dev)
+    first = torch.full((rays,), NO_HIT, dtype=torch.int32, device=dev)
+    p_hits, p_first = _lib.ptr(hits), _lib.ptr(first)
+
+    def fold(i, v, pt, base, k0_b, off_b, s0, s1, r0, r1, lanes, p_vals):
+        _lib.check(L.brief_surface_part_fold(v, pt, k0_b, off_b, s0, s1, r0, r1, lanes, p_vals, kind, ch, channel, level, sd, p_hits, p_first, stream))
+    march = _march_partition(parts, vs, pts, kind, dt, chunk, fold)
+    # the bracket: the clip of the WHOLE view (no net), then brief_surface_bracket as for a single net
+    v0 = C.byref(vs[0])
+    k0, cnt = torch.empty(rays, dtype=torch.int32, device=dev), torch.empty(rays, dtype=torch.int32, device=dev)
+    _lib.check(L.brief_view_clip(v0, _lib.ptr(k0), _lib.ptr(cnt), stream))
+    t_lo, t_hi = torch.empty(rays, dtype=torch.float32, device=dev), torch.empty(rays, dtype=torch.float32, device=dev)
+    _lib.check(L.brief_surface_bracket(v0, _lib.ptr(k0), p_first, _lib.ptr(t_lo), _lib.ptr(t_hi), stream))
+    table = torch.frombuffer(bytearray(bytes(_part_array(pts))), dtype=torch.uint8).to(dev)      # the route's table of blocks
+    owner, owner_lo = torch.empty(rays, dtype=torch.int32, device=dev), torch.empty(rays, dtype=torch.int32, device=dev)
+    p_lo, p_hi, p_table = _lib.ptr(t_lo), _lib.ptr(t_hi), _lib.ptr(table)
+
+    def route(mid):
+        _lib.check(L.brief_surface_part_route(v0, p_table, nb, p_lo, p_hi, mid, _lib.ptr(owner), stream))
+    # the ends of the initial bracket: the owner of t_lo (the route at t_hi of the bracket (t_lo, t_lo)) against the owner of t_hi
+    _lib.check(L.brief_surface_part_route(v0, p_table, nb, p_lo, p_lo, 0, _lib.ptr(owner_lo), stream))
+    route(0)
+    hit = first != NO_HIT
+    bracketed = hit & (first != k0)
+    rays_surface, rays_cut, rays_hit, inside, straddle = torch.stack([
+        hit.sum(), (hit & (first == k0)).sum(), (hits > 0).sum(), hits.sum(dtype=torch.int64), (bracketed & (owner_lo != owner)).sum()]).cpu().tolist()
+    # the window of a block whose cell the clip box misses is empty: the list entries take the whole image then (the window plays no part)
+    full = [pt if pt.wrows > 0 and pt.wcols > 0 else make_part(view, list(pt.start), list(pt.dims), "image") for pt in pts]
+    room = mip.DEFAULT_CHUNK
+
+    def buckets():
+        """the rays grouped by owner, one stable sort and ONE host read of the per-block counts: (order, [(block, offset, count)])"""
+        order = torch.argsort(owner, stable=True)
+        counts = torch.bincount((owner + 1).to(torch.int64), minlength=nb + 1).cpu().tolist()
+        out, at = [], counts[0]                                     # (the rays without an owner come first)
+        for i in range(nb):
+            if counts[i + 1]:
+                out.append((i, at, counts[i + 1]))
+            at += counts[i + 1]
+        return order, out
+
+    def lists(order, found):
+        """(block, pointer to the list, entries) per list of at most `room` rays"""
+        for i, at, n in found:
+            for o in range(0, n, room):
+                yield i, _at_ray(order, at + o), min(room, n - o)
+    refine_points = launch_blocks = 0
+    coords = vals = None
+    if refine and rays_surface > rays_cut:
+        for _ in range(refine):
+            route(1)
+            order, found = buckets()
+            launch_blocks += len(found)
+            if found and coords is None:
+                most = min(room, rays)
+                coords = torch.empty((most, 3), dtype=torch.float32, device=dev)
+                vals = torch.empty((most, ch), dtype=dt, device=dev)
+            block = -1
+            for i, p_list, n in lists(order, found):
+                if i != block:
+                    block = i
+                    parts[i][0].sync_packed()
+                _lib.check(L.brief_surface_part_coords(C.byref(vs[i]), C.byref(full[i]), p_lo, p_hi, 1, p_list, n, _lib.ptr(coords), None, stream))
+                b = _lib.BatchDesc(coords.data_ptr(), None, None, None, 0, n, 0, 0, 0)
+                _lib.check(parts[i][0]._abi_forward(None, b, vals, kind, parts[i][5], parts[i][6], n))
+                _lib.check(L.brief_surface_part_step(p_list, n, _lib.ptr(vals), kind, ch, channel, level, sd, p_lo, p_hi, stream))
+                refine_points += n
+    # the hit is t_hi, always an evaluated point: it has an owner
+    route(0)
+    pos = torch.full((rays, 3), float("nan"), dtype=torch.float32, device=dev)
+    normal = shade = None
+    if shading:
+        normal = torch.zeros((view.rows, view.cols, 3), dtype=torch.float32, device=dev)
+        shade = torch.zeros((view.rows, view.cols), dtype=torch.float32, device=dev)
+        l = _unit3(light if light is not None else list(view.ddepth), "light")
+        f3 = C.c_float * 3
+    if rays_surface:
+        order, found = buckets()
+        if coords is None:
+            coords = torch.empty((min(room, rays), 3), dtype=torch.float32, device=dev)
+        for i, p_list, n in lists(order, found):
+            phi, _, dims, lo, hi, scale, vrange = parts[i]
+            _lib.check(L.brief_surface_part_coords(C.byref(vs[i]), C.byref(full[i]), p_lo, p_hi, 0, p_list, n, _lib.ptr(coords), _lib.ptr(pos), stream))
+            if shading:
+                g = gradient.voxel_scale([int(x) for x in dims], lo, hi, scale, vrange[0], vrange[1]) / vs3
+                _, jac = phi.spatial_gradient(coords[:n], want_value=False)
+                _lib.check(L.brief_surface_part_shade(p_list, n, p_hi, _lib.ptr(jac), ch, channel, sd, f3(*g), f3(*l), _lib.ptr(normal), _lib.ptr(shade),
+                                                      stream))
+    shape = (view.rows, view.cols)
+    stats = {"rays": rays, "rays_hit": rays_hit, "samples_inside": inside, "samples_evaluated": march["evaluated"], "rays_surface": rays_surface,
+             "rays_cut": rays_cut, "refine_points": refine_points, "blocks": nb, "blocks_hit": march["blocks_hit"],
+             "rays_clipped": march["window_rays"], "rays_straddle": straddle, "refine_launch_blocks": launch_blocks}
+    return {"first": torch.where(hit, first, torch.full_like(first, -1)).view(shape), "t_lo": t_lo.view(shape), "t_hi": t_hi.view(shape),
+            "t": t_hi.view(shape), "position": pos.view(*shape, 3), "normal": normal, "shade": shade, "hits": hits.view(shape),
+            "owner": owner.view(shape), "stats": stats}
+
+
 # ---- artefacts ------------------------------------------------------------------------------------------------------------------
 ENVELOPE = dict(
     no_error_bound="a view of an error-bounded artefact is refused: its corrections (error_bound %s) exist on the points of the "
@@ -696,6 +891,21 @@ def decompress_divide_view(opt, orig_sideinfos, module_dir, sideinfos_dir, direc
     Decompress.postprocess acts on the image as in decompress_view.  Refused by name before any net is opened: per block everything
     check_envelope refuses (error-bounded blocks, dtype, normalisation, postprocess, an axis of length 1), blocks of different
     dtypes or channel counts, overlapping blocks, 2-D data, an axis of 2^23 or more."""
+    data_shape, _, arts, starts = _divide_plan(opt, orig_sideinfos, module_dir, sideinfos_dir, mode)
+    depth = _plane_depth(mode, depth, offset)
+    view = make_view(data_shape[:-1], direction, up, centre, spacing, depth_spacing, size, depth, voxel_size, region)
+    make_part(view, starts[0], arts[0].dims, "image")             # (the 2^23 rule, before any net is opened)
+    parts = [(art.load_phi(device), s, art.dims, art.lo, art.hi, art.norm_range, art.vrange) for art, s in zip(arts, starts)]
+    image, hits, stats = render_partition(parts, view, mode, arts[0].out_kind, chunk=chunk)
+    img = image.cpu().numpy()
+    if mode != "mean":
+        img = np.array(arts[0].postprocess_local(img), copy=True)
+        img[hits.cpu().numpy() == 0] = 0                            # (a ray without a sample stays 0 whatever the clip's floor is)
+    return (img, hits.cpu().numpy(), stats) if return_hits else img
+
+
+def _divide_plan(opt, orig_sideinfos, module_dir, sideinfos_dir, mode):
+    """decompress_divide_view's envelope and refusals, before any net is opened: (data_shape, arts, starts)"""
     from . import config
     if isinstance(opt, str):
         opt = config.load(opt)
@@ -713,16 +923,40 @@ def decompress_divide_view(opt, orig_sideinfos, module_dir, sideinfos_dir, direc
     for b, art, s in zip(blocks, arts, starts):
         if art.cout != data_shape[-1] or art.dims != [b.ranges[a][1] - b.ranges[a][0] + 1 for a in "dhw"]:
             raise ValueError("the block %s holds data of shape %s: not its index range of a volume with %d channels" % (b.name, art.data_shape, data_shape[-1]))
-    depth = _plane_depth(mode, depth, offset)
+    return data_shape, blocks, arts, starts
+
+
+def decompress_divide_surface(opt, orig_sideinfos, module_dir, sideinfos_dir, direction, level, up=None, region=None, centre=None, spacing=1.0,
+                              depth_spacing=1.0, size=None, depth=None, voxel_size=(1, 1, 1), channel=0, side="above", refine=8, shading=True,
+                              light=None, device="cuda", chunk=None, gap="empty"):
+    """decompress_surface for a stored DivideTask artefact (orig_sideinfos, module_dir, sideinfos_dir: decompress_divide_view's), without
+    decoding the volume or any block: render_surface_partition's dict as numpy arrays (first, t_lo, t_hi, t, position, normal, shade,
+    hits, owner: the index of the hit's block in the artefact's block order, stats) plus depth = t * depth_spacing.  The view is a view
+    of the WHOLE volume; the nearest block owns a sample, every refinement point and the hit are routed to the block that owns them,
+    and a point in a gap no block covers holds nothing (gap 'empty', the only rule).  `level` is a grey level of the blocks' shared
+    integer dtype, compared before Decompress.postprocess.  Normals are physical, each from its owner's net and its owner's own scale.
+    Refused by name before any net is opened: everything decompress_divide_view refuses (error-bounded or overlapping blocks, blocks
+    of different dtypes or channel counts, 2-D data, an axis of 2^23 or more or of length 1), everything check_surface refuses, a gap
+    rule other than 'empty', and shading where any block's net has no Jacobian kernel (ask for shading=False)."""
+    from . import gradient
+    _check_gap(gap)
+    data_shape, blocks, arts, starts = _divide_plan(opt, orig_sideinfos, module_dir, sideinfos_dir, "max")
+    check_surface(level, channel, side, refine, data_shape[-1], arts[0].dtype)
+    if shading:
+        for b, art in zip(blocks, arts):
+            why = gradient.refusal(art.phi_name, art.precision, art.phi_features)
+            if why is not None:
+                raise ValueError("normals and shading need the analytic Jacobian of every block's net, and the block %s has none: %s; ask for "
+                                 "shading=False" % (b.name, why))
     view = make_view(data_shape[:-1], direction, up, centre, spacing, depth_spacing, size, depth, voxel_size, region)
     make_part(view, starts[0], arts[0].dims, "image")             # (the 2^23 rule, before any net is opened)
+    physical = frame(direction, up)[2] if light is None else _unit3(light, "light")
     parts = [(art.load_phi(device), s, art.dims, art.lo, art.hi, art.norm_range, art.vrange) for art, s in zip(arts, starts)]
-    image, hits, stats = render_partition(parts, view, mode, arts[0].out_kind, chunk=chunk)
-    img = image.cpu().numpy()
-    if mode != "mean":
-        img = np.array(arts[0].postprocess_local(img), copy=True)
-        img[hits.cpu().numpy() == 0] = 0                            # (a ray without a sample stays 0 whatever the clip's floor is)
-    return (img, hits.cpu().numpy(), stats) if return_hits else img
+    out = render_surface_partition(parts, view, level, arts[0].out_kind, channel=channel, side=side, refine=refine, shading=shading, light=physical,
+                                   voxel_size=voxel_size, gap=gap, chunk=chunk)
+    res = {k: (x.cpu().numpy() if hasattr(x, "cpu") else x) for k, x in out.items()}
+    res["depth"] = res["t"] * np.float32(depth_spacing)
+    return res
 
 
 def decompress_surface(art, direction, level, up=None, region=None, centre=None, spacing=1.0, depth_spacing=1.0,

@@ -43,7 +43,16 @@ not with `--mip`, `--gradient`, `--shape` or a `--step` other than 1).
 A DivideTask artefact has one net per block, so a sample between two blocks needs an owner: `--view-owner nearest` names the rule (the
 block whose cell, half a voxel around its index range, holds the sample evaluates it; nothing is blended across a face).  The view is
 a view of the whole volume.  Without the option a DivideTask artefact is refused; the option on a SingleTask artefact, without
-`--view`, or with `--view-surface` is refused by name.
+`--view`, or with `--view-surface` but without `--view-surface-gap` is refused by name.
+
+    python decompress.py -p <run yaml> -c <.../compressed of a DivideTask job> --region :,:,: --view dz,dy,dx --view-owner nearest
+        --view-surface LEVEL --view-surface-gap empty [--view-surface-side ...] [--view-refine N] ... -o out.png|out.tif|out.npy
+
+`--view-surface LEVEL --view-surface-gap empty` with `--view-owner nearest` renders the isosurface of a DivideTask artefact: the march is
+the view's, and every point of the bisection, and the hit itself, is routed to the block whose cell holds it, so a bracket may straddle a
+face; the normal is the owning block's.  `--view-surface-gap empty` names what a point no block owns holds: nothing, it fails the level
+test on either side.  The outputs are those of `--view-surface` below.  The option without `--view-surface`, on a SingleTask artefact or
+with another value is refused by name.
 
     python decompress.py -p <run yaml> -c <.../compressed> --region :,:,: --view dz,dy,dx --view-surface LEVEL
         [--view-surface-side above|below] [--view-refine N] [--view-channel C] [--view-light lz,ly,lx] -o out.png|out.tif|out.npy
@@ -115,6 +124,9 @@ def main(argv=None):
     ap.add_argument("--view-refine", type=int, default=None, metavar="N", help="rounds of bisection of the hit, 0 .. 16 (default 8)")
     ap.add_argument("--view-channel", type=int, default=None, metavar="C", help="the channel the level is tested on (default 0)")
     ap.add_argument("--view-light", default=None, metavar="lz,ly,lx", help="the physical direction the light travels (default: the view direction)")
+    ap.add_argument("--view-surface-gap", default=None, metavar="{empty}",
+                    help="the rule that says what a point no block owns holds in the --view-surface of a DivideTask artefact (with --view-owner nearest): "
+                         "empty (nothing: it fails the level test on either side); without it the isosurface of a DivideTask artefact is refused")
     ap.add_argument("--view-composite", default=None, metavar="SPEC",
                     help="render the view through a transfer function, level:r,g,b,a;level:r,g,b,a;... or @file: front-to-back emission-absorption compositing "
                          "(a DivideTask artefact with --view-owner nearest)")
@@ -136,9 +148,10 @@ def main(argv=None):
     elif args.view_owner is not None:
         raise SystemExit("--view-owner names the rule that gives the samples of a --view of a DivideTask artefact their blocks: give the "
                          "view's direction with --view dz,dy,dx")
-    elif args.view_surface is not None or any(v is not None for v in (args.view_surface_side, args.view_refine, args.view_channel, args.view_light)):
-        raise SystemExit("--view-surface / --view-surface-side / --view-refine / --view-channel / --view-light describe the isosurface of a "
-                         "--view: give its direction with --view dz,dy,dx")
+    elif args.view_surface is not None or any(v is not None for v in (args.view_surface_side, args.view_refine, args.view_channel, args.view_light,
+                                                                      args.view_surface_gap)):
+        raise SystemExit("--view-surface / --view-surface-side / --view-surface-gap / --view-refine / --view-channel / --view-light describe the "
+                         "isosurface of a --view: give its direction with --view dz,dy,dx")
     elif any(v is not None for v in (args.view_up, args.view_size, args.view_offset, args.voxel_size)) or args.view_mode != "max" \
             or args.view_spacing != 1.0 or args.view_depth_spacing != 1.0:
         raise SystemExit("--view-up / --view-mode / --view-spacing / --view-depth-spacing / --view-size / --view-offset / --voxel-size "
@@ -230,10 +243,16 @@ def _view_refusals(args):
         if on:
             raise SystemExit("--view with %s: a view is one image of the fitted grid along its own direction (its sampling is set by "
                              "--view-spacing and --view-depth-spacing); ask for one of them" % flag)
-    from brief_pytorch_amd.view import DIVIDE_REFUSAL, MODES, OWNERS
+    from brief_pytorch_amd.view import DIVIDE_REFUSAL, GAPS, MODES, OWNERS
+    if args.view_surface_gap is not None and args.view_surface is not None:
+        if args.view_surface_gap not in GAPS:
+            raise SystemExit("--view-surface-gap %s: unknown rule (%s)" % (args.view_surface_gap, ", ".join(GAPS)))
+        if not os.path.isdir(_paths(args.c)[2]):
+            raise SystemExit("--view-surface-gap %s: the rule says what a point between the blocks of a DivideTask artefact holds, and %s is a "
+                             "SingleTask artefact (one net covers the volume); leave the option out" % (args.view_surface_gap, args.c))
     if args.view_surface is None:
         for flag, v in (("--view-surface-side", args.view_surface_side), ("--view-refine", args.view_refine), ("--view-channel", args.view_channel),
-                        ("--view-light", args.view_light)):
+                        ("--view-light", args.view_light), ("--view-surface-gap", args.view_surface_gap)):
             if v is not None:
                 raise SystemExit("%s describes an isosurface: give its level with --view-surface LEVEL" % flag)
     else:
@@ -272,9 +291,10 @@ def _view_refusals(args):
     if args.view_owner is not None:
         if args.view_owner not in OWNERS:
             raise SystemExit("--view-owner %s: unknown rule (%s)" % (args.view_owner, ", ".join(OWNERS)))
-        if args.view_surface is not None:
-            raise SystemExit("--view-surface with --view-owner: the isosurface of a DivideTask artefact is refused: the refinement of a hit and its "
-                             "normal need per-point routing between blocks (a bracket can straddle a face); decode the region and render it")
+        if args.view_surface is not None and args.view_surface_gap is None:
+            raise SystemExit("--view-surface with --view-owner: the isosurface of a DivideTask artefact is refused unless its gap rule is named: "
+                             "the refinement of a hit and its normal need per-point routing between blocks (a bracket can straddle a face, or "
+                             "end in a gap no block covers); ask for --view-surface-gap empty (a point no block owns holds nothing)")
         if not divide:
             raise SystemExit("--view-owner %s: the rule chooses among the blocks of a DivideTask artefact, and %s is a SingleTask artefact (one "
                              "net owns every sample); leave the option out" % (args.view_owner, args.c))
@@ -288,7 +308,7 @@ def _view(args, opt, region, divide):
     from brief_pytorch_amd.framework import NFGR, decompress_divide_view
     from brief_pytorch_amd.tool import save_img
     if args.view_surface is not None:
-        return _surface(args, opt, region)
+        return _surface(args, opt, region, divide)
     if args.view_composite is not None:
         return _composite(args, opt, region, divide)
     module, side_path, blocks_dir = _paths(args.c)
@@ -317,21 +337,28 @@ def _view(args, opt, region, divide):
     return 0
 
 
-def _surface(args, opt, region):
+def _surface(args, opt, region, divide):
     import numpy as np
     import torch
-    from brief_pytorch_amd import gradient, view
+    from brief_pytorch_amd import artefact, gradient, view
     from brief_pytorch_amd.tool import save_img
-    module, side_path, _ = _paths(args.c)
+    module, side_path, blocks_dir = _paths(args.c)
     npy = os.path.splitext(args.o)[1].lower() == ".npy"
     t0 = time.perf_counter()
     try:
-        art = view.open_single(opt, module, side_path)
-        why = gradient.refusal(art.phi_name, art.precision, art.phi_features)
+        if divide:                                                # (--view-owner nearest --view-surface-gap empty: _view_refusals refused everything else)
+            arts = [artefact.open_artefact(opt, b.module_path, b.side)      # (opening reads the side info only, no net)
+                    for b in artefact.divide_blocks(side_path, module, blocks_dir, one_dtype="the view decode")[1]]
+            why = next((w for w in (gradient.refusal(a.phi_name, a.precision, a.phi_features) for a in arts) if w is not None), None)
+            render = lambda *a, **kw: view.decompress_divide_surface(opt, side_path, module, blocks_dir, *a, gap=args.view_surface_gap, **kw)
+        else:
+            art = view.open_single(opt, module, side_path)
+            why = gradient.refusal(art.phi_name, art.precision, art.phi_features)
+            render = lambda *a, **kw: view.decompress_surface(art, *a, **kw)
         if why is not None and not npy:
             raise ValueError("a shaded image needs the analytic Jacobian: %s; write the depth with -o <file>.npy" % why)
-        res = view.decompress_surface(
-            art, _floats(args.view, 3, "--view"), args.view_surface,
+        res = render(
+            _floats(args.view, 3, "--view"), args.view_surface,
             up=_floats(args.view_up, 3, "--view-up") if args.view_up is not None else None, region=region,
             spacing=args.view_spacing, depth_spacing=args.view_depth_spacing,
             size=[int(x) for x in _floats(args.view_size, 2, "--view-size")] if args.view_size is not None else None,
@@ -352,8 +379,10 @@ def _surface(args, opt, region):
         data = np.concatenate([res["depth"][..., None], res["normal"], res["shade"][..., None]], axis=-1).astype(np.float32)
         np.save(args.o, data)
     stats = res["stats"]
-    print("SingleTask surface view %s (level %d, %s) of region %s: %s %s, dtype %s, %d of %d rays hit the surface (%d cut by the clip box), "
+    print("%s surface view %s (level %d, %s) of region %s: %s %s, dtype %s, %d of %d rays hit the surface (%d cut by the clip box), "
           "%d samples evaluated, %d refinement points, decoded in %.3f s -> %s" % (
+              "DivideTask (%d of %d blocks hit, owner %s, gap %s, %d brackets straddle a face)" % (
+                  stats["blocks_hit"], stats["blocks"], args.view_owner, args.view_surface_gap, stats["rays_straddle"]) if divide else "SingleTask",
               args.view, args.view_surface, args.view_surface_side or "above", args.region, "image" if not npy else "array", tuple(data.shape),
               data.dtype, stats["rays_surface"], stats["rays"], stats["rays_cut"], stats["samples_evaluated"], stats["refine_points"], dt, args.o))
     return 0
@@ -371,6 +400,7 @@ def _composite_refusals(args):
         raise SystemExit("--view-owner %s: unknown rule (%s)" % (args.view_owner, ", ".join(OWNERS)))
     for flag, on in (("--view-mode %s" % args.view_mode, args.view_mode != "max"), ("--view-offset", args.view_offset is not None),
                      ("--view-surface", args.view_surface is not None), ("--view-surface-side", args.view_surface_side is not None),
+                     ("--view-surface-gap", args.view_surface_gap is not None),
                      ("--view-refine", args.view_refine is not None), ("--view-channel", args.view_channel is not None),
                      ("--view-light", args.view_light is not None),
                      ("--view-owner", args.view_owner is not None and not (args.view_owner in OWNERS and divide)), ("--mip", args.mip),

@@ -685,6 +685,52 @@ int brief_surface_shade(const brief_view_desc *view, const float *t, const float
 int brief_view_sample_t_host(const brief_view_desc *view, const int32_t *row, const int32_t *col, const float *t, int64_t n, float *pos, float *coord,
                              uint8_t *inside);
 
+/* ---- surface view of a partition: hits are routed across blocks (csrc/brief_surface_part.inc, csrc/brief_view.h) ------------------------
+ * The view is brief_view_part_*'s, the test and the bracket are the surface view's.  first[r] is the smallest owned inside k whose value
+ * passes, a min over all blocks; the bracket comes from brief_view_clip on the whole view and brief_surface_bracket: (first - 1, first)
+ * where first > k0[r], whether sample first - 1 is owned or lies in a gap.  A bracket can straddle a face, so every point a round
+ * evaluates, and the hit itself, is routed to the block whose half-open cell holds its global position p_a = fl(base_a + fl(t *
+ * ddepth_a)): a point exactly on a face belongs to the upper block.  The gap rule `empty`: a point no block owns holds nothing and
+ * fails the test on either side.
+ *   brief_surface_part_fold    brief_view_part_fold's arguments and walk (window rays, the exact clip-box-and-cell test on every sample)
+ *                              with brief_surface_fold's fold; lane 0 of a ray's group does one plain read-modify-write of the IMAGE
+ *                              pixel's hits and first (caller-initialised to 0 and INT32_MAX).  No atomics;
+ *   brief_surface_part_route   owner[r] (int32, one per image ray) = the index in parts[0 .. nparts) of the block whose cell holds the ray's
+ *                              point at t = the bracket's midpoint (midpoint == 1) or t_hi (midpoint == 0); -1 where the ray has nothing
+ *                              to evaluate: t is NaN; with midpoint == 1, not t_lo < t_hi; with midpoint == 1, no block owns the point,
+ *                              and then the kernel itself sets t_lo[r] = t_mid.  parts is a DEVICE array of brief_view_part (an empty
+ *                              window, wrows == wcols == 0, is allowed here: the window plays no part); O(nparts) per ray;
+ *   (caller)                   buckets the rays by owner: per block a LIST of image-ray indices, int64, each ray in at most one list;
+ *   brief_surface_part_coords  coords[i][3], block-local (brief_view_part_coords' rule at the real depth t), of the point of ray rays[i],
+ *                              i < n; where pos is not NULL also the global pos[rays[i]][3] (NaN where the ray has no point);
+ *   (caller)                   vals[i][channels] = the owner's forward entry on coords, with the block's own integer epilogue;
+ *   brief_surface_part_step    brief_surface_step on a list: vals[i] moves the bracket of ray rays[i];
+ *   brief_surface_part_shade   brief_surface_shade on a list, jac[i][channels][3] for ray rays[i] and the owner's own gscale; it writes
+ *                              normal[rays[i]] and shade[rays[i]] only: the caller zero-initialises both.
+ * Every decision compares decoded integers, or floats that depend on the ray alone: first, t_lo, t_hi and owner do not depend on the
+ * order of the blocks, on chunking, on the bucketing, on `lanes` or on the run.  gscale and light are HOST pointers to three floats.
+ * brief_surface_part_route_host is the route on the host CPU (every buffer host memory, t_lo updated in place);
+ * brief_view_part_sample_t_host is brief_view_part_sample_host at a real depth 0 <= t <= depth - 1.  Neither makes a GPU call.
+ * Limits (BRIEF_ERR_INVALID with a message naming the limit, before any launch): those of brief_view_part_fold and of the surface
+ * entries; nparts 1 .. 2^31 - 1; n >= 1; midpoint 0 | 1; no null buffer (pos excepted).  A DEVICE table or list cannot be read before a
+ * launch: the route trusts parts (it only compares floats against it), brief_surface_part_coords skips a list entry outside the image,
+ * _step and _shade a negative one; the host entry checks every block as brief_view_part_clip does. */
+int brief_surface_part_fold(const brief_view_desc *view, const brief_view_part *part, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1,
+                            int64_t r0, int64_t r1, int32_t lanes, const void *vals, int elem_kind, int32_t channels, int32_t channel, int32_t level,
+                            int32_t side, int32_t *hits, int32_t *first, void *stream);
+int brief_surface_part_route(const brief_view_desc *view, const brief_view_part *parts, int32_t nparts, float *t_lo, const float *t_hi, int32_t midpoint,
+                             int32_t *owner, void *stream);
+int brief_surface_part_coords(const brief_view_desc *view, const brief_view_part *part, const float *t_lo, const float *t_hi, int32_t midpoint,
+                              const int64_t *rays, int64_t n, float *coords, float *pos, void *stream);
+int brief_surface_part_step(const int64_t *rays, int64_t n, const void *vals, int elem_kind, int32_t channels, int32_t channel, int32_t level, int32_t side,
+                            float *t_lo, float *t_hi, void *stream);
+int brief_surface_part_shade(const int64_t *rays, int64_t n, const float *t, const float *jac, int32_t channels, int32_t channel, int32_t side,
+                             const float *gscale, const float *light, float *normal, float *shade, void *stream);
+int brief_surface_part_route_host(const brief_view_desc *view, const brief_view_part *parts, int32_t nparts, float *t_lo, const float *t_hi,
+                                  int32_t midpoint, int32_t *owner);
+int brief_view_part_sample_t_host(const brief_view_desc *view, const brief_view_part *part, const int32_t *row, const int32_t *col, const float *t,
+                                  int64_t n, float *pos, float *local, float *coord, uint8_t *inside, uint8_t *owned);
+
 /* ---- composite view: front-to-back emission-absorption rendering through a transfer table (csrc/brief_composite.inc, .h) ------------
  * Clip, scan and the march's coordinates are brief_view_clip / (caller) / brief_view_coords.  Channel `channel` of the integer decode is
  * classified by the table tf, int32 [2^tf_bits][4] = (tau, eR, eG, eB), at the index value >> (bits of the dtype - tf_bits):
