@@ -101,6 +101,10 @@ class CompositeWindow(C.Structure):  # brief_composite_window
     _fields_ = [("base", C.c_int64), ("row0", C.c_int32), ("col0", C.c_int32), ("wrows", C.c_int32), ("wcols", C.c_int32)]
 
 
+class CompositeShade(C.Structure):   # brief_composite_shade
+    _fields_ = [("gscale", C.c_float * 3), ("light", C.c_float * 3), ("ka_q", C.c_int32), ("kd_q", C.c_int32)]
+
+
 VIEW_MODE = {"max": 0, "min": 1, "mean": 2, "slice": 3}      # BRIEF_VIEW_MAX .. BRIEF_VIEW_SLICE
 SURFACE_SIDE = {"above": 0, "below": 1}                      # BRIEF_SURFACE_ABOVE, BRIEF_SURFACE_BELOW
 
@@ -143,7 +147,9 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_view_composite_part_fold", "brief_view_composite_part_carry", "brief_view_composite_part_gather",
            "brief_view_composite_part_fold_host", "brief_view_composite_part_carry_host", "brief_view_composite_part_gather_host",
            "brief_surface_part_fold", "brief_surface_part_route", "brief_surface_part_coords", "brief_surface_part_step", "brief_surface_part_shade",
-           "brief_surface_part_route_host", "brief_view_part_sample_t_host"] \
+           "brief_surface_part_route_host", "brief_view_part_sample_t_host",
+           "brief_view_composite_select", "brief_view_composite_pick", "brief_view_composite_shade_fold", "brief_view_composite_shade_host",
+           "brief_composite_shade_q_host"] \
     + ["brief_%s_%s" % (prefix, entry) for prefix, _, _ in FAMILIES for entry in FAMILY_ENTRIES]
 
 
@@ -294,6 +300,12 @@ def lib():
     L.brief_surface_part_shade.argtypes = [vp, i64, vp, vp, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp, vp]
     L.brief_surface_part_route_host.argtypes = [wp, vp, i32, vp, vp, i32, vp]
     L.brief_view_part_sample_t_host.argtypes = [wp, pp, vp, vp, vp, i64, vp, vp, vp, vp, vp]
+    hp = C.POINTER(CompositeShade)
+    L.brief_view_composite_select.argtypes = [wp, vp, vp, i64, i64, i64, i64, i32, vp, C.c_int, i32, i32, vp, i32, vp, vp, vp]
+    L.brief_view_composite_pick.argtypes = [vp, vp, vp, i64, vp, vp]
+    L.brief_view_composite_shade_fold.argtypes = [wp, vp, vp, i64, i64, i64, i64, i32, vp, C.c_int, i32, i32, vp, i32, vp, vp, vp, hp, vp, vp, vp, vp]
+    L.brief_view_composite_shade_host.argtypes = [wp, vp, vp, vp, C.c_int, i32, i32, vp, i32, C.POINTER(i32), vp, hp, vp, vp, vp, vp, vp]
+    L.brief_composite_shade_q_host.argtypes = [vp, i64, hp, vp]
     _LIB = L
     return L
 

@@ -13,9 +13,13 @@ volume with one net per block, the nearest block owning a sample: the blocks are
 front of a block's part of a ray is carried across the blocks, and only the parts behind something partly opaque are marched a
 second time (DESIGN.md "Composite view of a partition").
 
-parse_transfer, make_transfer and check_transfer are host arithmetic; composite_host, part_fold_host, part_carry_host and
-part_gather_host restate the device's folds on the CPU (brief_view_composite_host, brief_view_composite_part_*_host); everything else
-needs a ROCm GPU (there is no CPU fallback)."""
+The shaded composite (render_composite with shade=(KA, KD)) lights every sample's emission by the net's analytic gradient, a
+two-sided Lambert term in Q8; the Jacobian is evaluated only at the samples that emit and are not hidden, which the integer prefix
+names exactly (DESIGN.md "Shaded composite").
+
+parse_transfer, make_transfer, check_transfer and shade_quant are host arithmetic; composite_host, composite_shade_host, shade_q_host,
+part_fold_host, part_carry_host and part_gather_host restate the device's folds on the CPU (brief_view_composite_host,
+brief_view_composite_shade_host, brief_view_composite_part_*_host); everything else needs a ROCm GPU (there is no CPU fallback)."""
 import ctypes as C
 import math
 import os
@@ -33,6 +37,10 @@ DIVIDE_REFUSAL = ("a composite view of a DivideTask artefact is refused: every b
                   "ray; it needs a second pass over the blocks (a follow-up).  Decode the region and render it, or use --view with "
                   "--view-owner nearest for a projection.  That second pass exists where the ownership rule is named: --view-composite with "
                   "--view-owner nearest (decompress_divide_composite) renders the composite of the partition")
+
+DIVIDE_SHADE_REFUSAL = ("a shaded composite of a DivideTask artefact is refused: the partition composite marches the blocks behind something "
+                        "partly opaque a second time, and that second pass would have to carry every block's gradients too (a follow-up).  "
+                        "Leave --view-composite-shade out for the plain composite of the partition")
 
 
 def _kind(out_kind):
@@ -162,6 +170,68 @@ def composite_host(view, k0, off, vals, tf, channel=0, background=(0, 0, 0)):
     return out.reshape(*shape, 4), hits.reshape(shape), tau_run.reshape(shape), acc.reshape(*shape, 3)
 
 
+def shade_quant(shade):
+    """(ka_q, kd_q) = (round(256 * KA), round(256 * KD)), integers 0 .. 256, of shade = (KA, KD): the ambient and the diffuse weight of
+    the shaded composite, each in [0, 1]"""
+    try:
+        ka, kd = (float(x) for x in shade)
+    except (TypeError, ValueError):
+        raise ValueError("shade must be two numbers KA,KD, the ambient and the diffuse weight, each in [0, 1] (got %r)" % (shade,)) from None
+    if not (0.0 <= ka <= 1.0 and 0.0 <= kd <= 1.0):        # (a NaN fails both comparisons)
+        raise ValueError("shade KA,KD = %r is refused: the ambient and the diffuse weight must each lie in [0, 1]" % (tuple(shade),))
+    return int(math.floor(256.0 * ka + 0.5)), int(math.floor(256.0 * kd + 0.5))
+
+
+def _shade_desc(gscale, light, ka_q, kd_q):
+    """the brief_composite_shade of gscale and light (three finite numbers each, (z, y, x)) and the quantised weights"""
+    g, l = view_mod._vec3(gscale, "gscale"), view_mod._vec3(light, "light")
+    sh = _lib.CompositeShade()
+    for a in range(3):
+        sh.gscale[a], sh.light[a] = g[a], l[a]
+    sh.ka_q, sh.kd_q = int(ka_q), int(kd_q)
+    return sh
+
+
+def shade_q_host(jac, gscale, light, ka_q, kd_q):
+    """s_q int32 [n], the factor of a sample's emission in Q8, of the Jacobian rows jac [n, 3] float32 on the host CPU
+    (brief_composite_shade_q_host: the header the kernels run); ka_q = 0, kd_q = 256 gives c_q = round(256 * |cos|) itself"""
+    jac = np.ascontiguousarray(jac, np.float32)
+    if jac.ndim != 2 or jac.shape[1] != 3 or not len(jac):
+        raise ValueError("jac must be float32 [n, 3], n >= 1 (got %s)" % (jac.shape,))
+    out = np.empty(len(jac), np.int32)
+    sh = _shade_desc(gscale, light, ka_q, kd_q)
+    _lib.check(_lib.lib().brief_composite_shade_q_host(jac.ctypes.data_as(C.c_void_p), len(jac), C.byref(sh), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def composite_shade_host(view, k0, off, vals, tf, jac, gscale, light, ka_q, kd_q, channel=0, background=(0, 0, 0)):
+    """composite_host with every emission lit (brief_view_composite_shade_host), no GPU call: (image, hits, tau_run, acc, need int32
+    [off[-1]]: the samples that need a gradient).  jac [off[-1], channels, 3] float32 is the dense Jacobian, one row per sample."""
+    vals = np.ascontiguousarray(vals)
+    if vals.dtype not in (np.uint8, np.uint16) or vals.ndim != 2:
+        raise ValueError("vals must be uint8 or uint16 [samples, channels] (got %s %s)" % (vals.dtype, vals.shape))
+    kind = "u8" if vals.dtype == np.uint8 else "u16"
+    tf, bits = check_transfer(tf, kind)
+    rays = view.rows * view.cols
+    k0, off = np.ascontiguousarray(k0, np.int32).ravel(), np.ascontiguousarray(off, np.int64).ravel()
+    if len(k0) != rays or len(off) != rays + 1:
+        raise ValueError("k0 needs one entry per ray and off one more (%d rays; got %d and %d)" % (rays, len(k0), len(off)))
+    if len(vals) != int(off[-1]):
+        raise ValueError("vals holds %d samples, off names %d" % (len(vals), int(off[-1])))
+    jac = np.ascontiguousarray(jac, np.float32)
+    if jac.shape != (len(vals), vals.shape[1], 3):
+        raise ValueError("jac must be float32 [samples, channels, 3] = %s (got %s)" % ((len(vals), vals.shape[1], 3), jac.shape))
+    sh = _shade_desc(gscale, light, ka_q, kd_q)
+    hits, tau_run, need = np.empty(rays, np.int32), np.empty(rays, np.int32), np.zeros(len(vals), np.int32)
+    acc, out = np.empty((rays, 3), np.uint64), np.empty((rays, 4), np.uint8)
+    bg = (C.c_int32 * 3)(*[int(b) for b in background])
+    _lib.check(_lib.lib().brief_view_composite_shade_host(C.byref(view), _hp(k0), _hp(off), _hp(vals), _lib.OUT_U8 if kind == "u8" else _lib.OUT_U16,
+                                                          vals.shape[1], int(channel), _hp(tf), bits, bg, _hp(jac), C.byref(sh), _hp(need),
+                                                          _hp(hits), _hp(tau_run), _hp(acc), _hp(out)))
+    shape = (view.rows, view.cols)
+    return out.reshape(*shape, 4), hits.reshape(shape), tau_run.reshape(shape), acc.reshape(*shape, 3), need
+
+
 def _background(background):
     try:
         bg = [int(b) for b in background]
@@ -187,16 +257,32 @@ def _device_table(tf, kind_name, width, dev):
     return torch.from_numpy(t).to(dev), bits
 
 
-def render_composite(phi, view, tf, lo, hi, out_kind, scale, vrange, channel=0, background=(0, 0, 0), chunk=None):
+def render_composite(phi, view, tf, lo, hi, out_kind, scale, vrange, channel=0, background=(0, 0, 0), chunk=None, shade=None, light=None,
+                     gscale=None, compact=True):
     """the composite view of the net `phi` (any net kind and precision its forward entry serves) on the linspace grid view.dims over
     [lo, hi]: (image uint8 [rows, cols, 4] = R, G, B, A, hits [rows, cols] int32, stats) as device tensors.  Channel `channel` of the
     integer decode (out_kind 'u8' | 'u16' with scale / vrange: view.render's) is classified by the table `tf` (make_transfer's: a numpy
     array, checked here, or an int32 device tensor of the same form, taken as it is) and composited front to back along every ray, in
     ascending k; RGB is already composited over `background` (0 .. 255 per channel), A is the ray's opacity.  A ray without an inside
     sample shows the background with A = 0.  Samples are evaluated in chunks of at most `chunk` (default mip.DEFAULT_CHUNK) in the
-    list's order; the image does not depend on it.  stats: view.render's keys."""
+    list's order; the image does not depend on it.  stats: view.render's keys.
+
+    shade=(KA, KD), each in [0, 1]: the SHADED composite (csrc/brief_composite.h; DESIGN.md "Shaded composite").  Opacity, hits and A
+    stay the plain composite's; a sample's emission is scaled by KA + KD * |n . l| in Q8, n the direction of the channel's analytic
+    gradient times `gscale` (default gradient.voxel_scale: voxels of extent 1) and l the unit direction `light` travels (default the
+    view's own direction ddepth; decompress_composite passes the physical ones).  The Jacobian is evaluated only at the samples that
+    emit and are not hidden behind a saturated prefix; stats gains samples_shaded, their count.  compact=False evaluates it at every
+    sample instead (the reference path: the same image).  A net without the Jacobian kernel (anything but an fp32 SIREN of at most
+    1024 features) is refused before any decode.  shade=None is the plain composite; light, gscale or compact=False without shade
+    are refused."""
     import torch
     from . import mip
+    if shade is None:
+        for name, given in (("light", light is not None), ("gscale", gscale is not None), ("compact=False", not compact)):
+            if given:
+                raise ValueError("%s describes the shaded composite: give its weights with shade=(KA, KD)" % name)
+    else:
+        return _render_composite_shaded(phi, view, tf, lo, hi, out_kind, scale, vrange, channel, background, chunk, shade, light, gscale, compact)
     kind_name, width = _kind(out_kind)
     if int(phi.coords_channel) != 3:
         raise ValueError("a view is defined for 3-D data only (the net takes %d coordinates)" % phi.coords_channel)
@@ -225,6 +311,73 @@ def render_composite(phi, view, tf, lo, hi, out_kind, scale, vrange, channel=0, 
     image = torch.empty((v.rows, v.cols, 4), dtype=torch.uint8, device=dev)
     _lib.check(L.brief_view_composite_finish(C.byref(v), bg, _lib.ptr(hits), _lib.ptr(tau_run), _lib.ptr(acc), _lib.ptr(image), st()))
     stats = {"rays": rays, "rays_hit": rays_hit, "samples_inside": int(hits.sum(dtype=torch.int64).item()), "samples_evaluated": total}
+    return image, hits.view(v.rows, v.cols), stats
+
+
+def _render_composite_shaded(phi, view, tf, lo, hi, out_kind, scale, vrange, channel, background, chunk, shade, light, gscale, compact):
+    """render_composite with shade: per chunk select (which samples need a gradient), scan, pick, the Jacobian on the picked samples
+    and the shaded fold; a chunk that lights nothing is folded by the plain fold (every one of its samples adds 0)"""
+    import torch
+    from . import gradient, mip
+    kind_name, width = _kind(out_kind)
+    ka_q, kd_q = shade_quant(shade)
+    if int(phi.coords_channel) != 3:
+        raise ValueError("a view is defined for 3-D data only (the net takes %d coordinates)" % phi.coords_channel)
+    ch = int(phi.data_channel)
+    if int(channel) != channel or not 0 <= int(channel) < ch:
+        raise ValueError("channel %r does not exist: the net has the channels 0 .. %d" % (channel, ch - 1))
+    why = gradient.refusal(getattr(type(phi), "kind", "SIREN"), phi.precision, phi.features)
+    if why is not None:
+        raise ValueError("a shaded composite needs the analytic Jacobian: %s" % why)
+    g = gscale if gscale is not None else gradient.voxel_scale(list(view.dims), lo, hi, scale, vrange[0], vrange[1])
+    sh = _shade_desc(g, view_mod._unit3(light if light is not None else list(view.ddepth), "light"), ka_q, kd_q)
+    bg = (C.c_int32 * 3)(*_background(background))
+    phi._require_gpu()
+    dev = phi.params.device
+    table, bits = _device_table(tf, kind_name, width, dev)
+    chunk = int(chunk or mip.DEFAULT_CHUNK)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    L, st = _lib.lib(), _lib.stream_ptr
+    v = view_mod._with_range(view, lo, hi)
+    rays = v.rows * v.cols
+    kind, dt = (_lib.OUT_U8, torch.uint8) if kind_name == "u8" else (_lib.OUT_U16, torch.uint16)
+    hits = torch.zeros(rays, dtype=torch.int32, device=dev)
+    tau_run = torch.zeros(rays, dtype=torch.int32, device=dev)
+    acc = torch.zeros((rays, 3), dtype=torch.int64, device=dev)         # (uint64 on the device)
+    buf = {}
+    shaded = [0]
+
+    def fold(k0, off, s0, s1, r0, r1, lanes, vals, coords):
+        n = s1 - s0
+        if not buf:                                                  # (the march's own chunk size: min(chunk, total))
+            buf["need"] = torch.empty(len(vals), dtype=torch.int32, device=dev)
+            buf["slot"] = torch.empty(len(vals), dtype=torch.int64, device=dev)
+            buf["sel"] = torch.empty((len(vals), 3), dtype=torch.float32, device=dev) if compact else None
+        need, slot = buf["need"], buf["slot"]
+        head = (C.byref(v), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(vals), kind, ch, int(channel), _lib.ptr(table), bits)
+        _lib.check(L.brief_view_composite_select(*head, _lib.ptr(tau_run), _lib.ptr(need), st()))
+        torch.cumsum(need[:n], 0, dtype=torch.int64, out=slot[:n])  # inclusive: the last entry is m
+        m = int(slot[n - 1].item())                                  # the chunk's one host read
+        shaded[0] += m
+        if m == 0:
+            _lib.check(L.brief_view_composite_fold(*head, _lib.ptr(hits), _lib.ptr(tau_run), _lib.ptr(acc), st()))
+            return
+        if compact:
+            slot[:n] -= need[:n]                                     # exclusive
+            _lib.check(L.brief_view_composite_pick(_lib.ptr(need), _lib.ptr(slot), _lib.ptr(coords), n, _lib.ptr(buf["sel"]), st()))
+            _, jac = phi.spatial_gradient(buf["sel"][:m], want_value=False)
+            p_slot = _lib.ptr(slot)
+        else:
+            _, jac = phi.spatial_gradient(coords[:n], want_value=False)
+            p_slot = None
+        _lib.check(L.brief_view_composite_shade_fold(*head, _lib.ptr(need), p_slot, _lib.ptr(jac), C.byref(sh), _lib.ptr(hits), _lib.ptr(tau_run),
+                                                     _lib.ptr(acc), st()))
+    _, total, rays_hit = view_mod._march(phi, v, kind, dt, scale, vrange, chunk, fold, with_coords=True)
+    image = torch.empty((v.rows, v.cols, 4), dtype=torch.uint8, device=dev)
+    _lib.check(L.brief_view_composite_finish(C.byref(v), bg, _lib.ptr(hits), _lib.ptr(tau_run), _lib.ptr(acc), _lib.ptr(image), st()))
+    stats = {"rays": rays, "rays_hit": rays_hit, "samples_inside": int(hits.sum(dtype=torch.int64).item()), "samples_evaluated": total,
+             "samples_shaded": shaded[0]}
     return image, hits.view(v.rows, v.cols), stats
 
 
@@ -377,7 +530,8 @@ def open_single(opt, module_path, sideinfos):
 
 
 def decompress_composite(art, direction, transfer, up=None, region=None, centre=None, spacing=1.0, depth_spacing=1.0, size=None, depth=None,
-                         voxel_size=(1, 1, 1), channel=0, background=(0, 0, 0), bits=None, device="cuda", chunk=None, return_hits=False):
+                         voxel_size=(1, 1, 1), channel=0, background=(0, 0, 0), bits=None, device="cuda", chunk=None, return_hits=False,
+                         shade=None, light=None):
     """the composite view of a stored SingleTask artefact (art: open_single's) as a numpy image uint8 [rows, cols, 4] = R, G, B, A, without
     decoding the volume.  The geometry arguments are view.make_view's; `region` is the clip box.
 
@@ -388,9 +542,27 @@ def decompress_composite(art, direction, transfer, up=None, region=None, centre=
     refused: a threshold or a clip would have to act on every sample before its classification, and the samples are never held.
     Refused by name before any decode: everything view.check_envelope refuses (error-bounded artefacts, 2-D data, dtype,
     normalisation, an axis of length 1), a non-identity postprocess, a channel that does not exist, a background outside 0 .. 255, a
-    malformed transfer function; DivideTask artefacts by open_single.  return_hits: (image, hits [rows, cols] int32, stats)."""
+    malformed transfer function; DivideTask artefacts by open_single.  return_hits: (image, hits [rows, cols] int32, stats).
+
+    shade=(KA, KD): the shaded composite (render_composite).  The gradient is physical, the stored net's analytic Jacobian in grey
+    levels per physical unit, and `light` is the physical direction the light travels, default `direction` (a headlight): both as
+    decompress_surface derives them (view.physical_shading).  Refused by name before any decode too: KA or KD outside [0, 1], light
+    without shade, a zero light, and a net without the Jacobian kernel (anything but an fp32 SIREN of at most 1024 features;
+    quantised artefacts load as one)."""
     view_mod.check_envelope(art, "max")
     _check_postprocess(art)
+    shading = {}
+    if shade is None:
+        if light is not None:
+            raise ValueError("light describes the shaded composite: give its weights with shade=(KA, KD)")
+    else:
+        from . import gradient
+        shade_quant(shade)
+        why = gradient.refusal(art.phi_name, art.precision, art.phi_features)
+        if why is not None:
+            raise ValueError("a shaded composite needs the analytic Jacobian: %s" % why)
+        physical, gscale = view_mod.physical_shading(art, direction, up, light, voxel_size)
+        shading = dict(shade=shade, light=physical, gscale=gscale)
     if int(channel) != channel or not 0 <= int(channel) < int(art.cout):
         raise ValueError("channel %r does not exist: the artefact has the channels 0 .. %d" % (channel, int(art.cout) - 1))
     _background(background)
@@ -398,7 +570,7 @@ def decompress_composite(art, direction, transfer, up=None, region=None, centre=
     tf = make_transfer(points, art.out_kind, depth_spacing, bits)
     view = view_mod.make_view(art.dims, direction, up, centre, spacing, depth_spacing, size, depth, voxel_size, region)
     image, hits, stats = render_composite(art.load_phi(device), view, tf, art.lo, art.hi, art.out_kind, art.norm_range, art.vrange,
-                                          channel=int(channel), background=background, chunk=chunk)
+                                          channel=int(channel), background=background, chunk=chunk, **shading)
     img = image.cpu().numpy()
     return (img, hits.cpu().numpy(), stats) if return_hits else img
 
@@ -415,7 +587,7 @@ def _check_postprocess(art):
 
 def decompress_divide_composite(opt, orig_sideinfos, module_dir, sideinfos_dir, direction, transfer, up=None, region=None, centre=None, spacing=1.0,
                                 depth_spacing=1.0, size=None, depth=None, voxel_size=(1, 1, 1), channel=0, background=(0, 0, 0), bits=None,
-                                device="cuda", chunk=None, return_hits=False):
+                                device="cuda", chunk=None, return_hits=False, shade=None, light=None):
     """decompress_composite for a stored DivideTask artefact (orig_sideinfos: the job's side info, dict or path; module_dir /
     sideinfos_dir: the blocks' trees), without decoding the volume or any block: the view is a view of the WHOLE volume, `region` and
     `centre` index it, the nearest block owns a sample (view.decompress_divide_view's rule; nothing is blended across a face), and the
@@ -423,8 +595,11 @@ def decompress_divide_composite(opt, orig_sideinfos, module_dir, sideinfos_dir, 
     are decompress_composite's.  Refused by name before any net is opened: per block everything view.check_envelope refuses
     (error-bounded blocks, dtype, normalisation, an axis of length 1), a Decompress.postprocess that changes values, blocks of
     different dtypes or channel counts, overlapping blocks, 2-D data, an axis of 2^23 or more, a channel that does not exist, a
-    background outside 0 .. 255, a malformed transfer function.  return_hits: (image, hits [rows, cols] int32, stats)."""
+    background outside 0 .. 255, a malformed transfer function; shade or light (the shaded composite of a partition is a follow-up).
+    return_hits: (image, hits [rows, cols] int32, stats)."""
     from . import artefact, config
+    if shade is not None or light is not None:
+        raise ValueError(DIVIDE_SHADE_REFUSAL)
     if isinstance(opt, str):
         opt = config.load(opt)
     data_shape, blocks = artefact.divide_blocks(orig_sideinfos, module_dir, sideinfos_dir, one_dtype="the composite view")

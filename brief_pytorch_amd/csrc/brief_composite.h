@@ -28,6 +28,24 @@
 //     acc_c < 2^17 * sum (Wr(P_i) + delta) * alpha_i <= 2^17 * (2^32 + delta * 2^24) < 2^50,
 // and the finish adds at most 65280 * 2^32 + 2^39 < 2^48.  A table that is merely in range (the entries' own limits are all the
 // host-visible entries check) may pair a large e with tau = 0; then acc_c wraps modulo 2^64, on the device and on the host alike.
+//
+// SHADED composite (brief_view_composite_select / _pick / _shade_fold, brief_view_composite_shade_host).  Opacity is not touched: tau,
+// P_i, hits, tau_run and A are the plain composite's.  Only a sample's emission is scaled, by a two-sided Lambert term s = KA + KD *
+// |n . l|, n = g / |g|, g the physical gradient of the classified channel (the net's analytic Jacobian times gscale) and l the unit
+// direction the light travels.  Every fp32 operation rounds on its own, nothing is contracted, sqrt and division are the correctly
+// rounded ones on the device as on the host:
+//     g_a  = fl(j_a * gscale_a)
+//     d    = fl(fl(fl(g0 * l0) + fl(g1 * l1)) + fl(g2 * l2)),   q = fl(fl(fl(g0 * g0) + fl(g1 * g1)) + fl(g2 * g2)),   len = sqrt(q)
+//     c_q  = 256 where len is not a finite positive number (a sample without a gradient direction is lit fully), else
+//            min(256, (int)fl(fl(fl(|d| / len) * 256) + 0.5)); a term that is not below 256 as a float (a NaN from a light far from
+//            unit length among them) is 256
+//     s_q  = min(256, ka_q + ((kd_q * c_q + 128) >> 8)),   ka_q = round(256 * KA), kd_q = round(256 * KD), 0 .. 256, from the host
+//     e'_c = (e_c * s_q + 128) >> 8,   acc_c += W(P_i) * e'_c
+// s_q <= 256, so e'_c <= e_c (e_c * 256 + 128 < 2^32): every term is at most the plain composite's and the 64-bit bound above still
+// holds.  ka_q = 256, kd_q = 0 gives s_q = 256 and e' = e: the plain composite, whatever the Jacobian holds.
+// A sample NEEDS a gradient iff it is inside the clip box, its table row has eR | eG | eB != 0 and P_i < TAU_SAT
+// (brief_composite_need): every other sample contributes 0 whatever its shade (e = 0, or W(P_i) = 0 for a saturated prefix).  The rule
+// reads integers only, so the selection depends on a sample's place along its ray alone, as the image does.
 #pragma once
 #include <stdint.h>
 #include "brief_view.h"
@@ -126,6 +144,51 @@ BRIEF_HD void brief_composite_pixel(uint32_t tau_total, const uint64_t acc[3], c
     }
     const uint64_t a = ((((uint64_t)1 << 32) - w) * 255u + ((uint64_t)1 << 31)) >> 32;
     out[3] = (uint8_t)(a < 255u ? a : 255u);
+}
+
+// ---- the SHADED composite: the Lambert term of a sample in Q8, and the rule that says which samples need one.
+// sqrtf and `/` are IEEE-correctly rounded in device code (clang's default for HIP, -fhip-fp32-correctly-rounded-divide-sqrt) as they
+// are on the host; __fsqrt_rn is NOT used: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers define it as the native, 1-ulp sqrt.
+
+// c_q = round(256 * |cos(g, light)|) of g_a = j_a * gscale_a, 0 .. 256; 256 where g has no direction
+BRIEF_HD int32_t brief_composite_cos_q(const float j[3], const float gscale[3], const float light[3])
+{
+    BRIEF_VIEW_NO_CONTRACT
+    const float g0 = j[0] * gscale[0];
+    const float g1 = j[1] * gscale[1];
+    const float g2 = j[2] * gscale[2];
+    const float d0 = g0 * light[0];
+    const float d1 = g1 * light[1];
+    const float d2 = g2 * light[2];
+    const float d01 = d0 + d1;
+    const float d = d01 + d2;
+    const float q0 = g0 * g0;
+    const float q1 = g1 * g1;
+    const float q2 = g2 * g2;
+    const float q01 = q0 + q1;
+    const float q = q01 + q2;
+    const float len = __builtin_sqrtf(q);
+    if (!(len > 0.f) || len - len != 0.f) return 256;
+    const float c = __builtin_fabsf(d) / len;
+    const float t = c * 256.f;
+    const float u = t + 0.5f;
+    return u < 256.f ? (int32_t)u : 256;                         // (u >= 0 or NaN here)
+}
+
+// s_q, the factor of a sample's emission in Q8, 0 .. 256 for ka_q, kd_q in 0 .. 256
+BRIEF_HD int32_t brief_composite_shade_q(const float j[3], const float gscale[3], const float light[3], int32_t ka_q, int32_t kd_q)
+{
+    const int32_t s = ka_q + ((kd_q * brief_composite_cos_q(j, gscale, light) + 128) >> 8);
+    return s < 256 ? s : 256;
+}
+
+// e' = (e * s_q + 128) >> 8 <= e
+BRIEF_HD uint32_t brief_composite_lit(uint32_t e, int32_t s_q) { return (e * (uint32_t)s_q + 128u) >> 8; }
+
+// whether a sample can reach the pixel, so that its shade matters: inside the clip box, emitting, and in front of saturation
+BRIEF_HD bool brief_composite_need(bool inside, uint32_t er, uint32_t eg, uint32_t eb, uint32_t prefix)
+{
+    return inside && (er | eg | eb) != 0u && prefix < (uint32_t)BRIEF_COMPOSITE_TAU_SAT;
 }
 
 // ---- the composite of a PARTITION (one net per block, view.render_partition's ownership): carry the prefix across blocks.

@@ -18,6 +18,9 @@
 // The table is read through the cache with plain 16-byte loads, whatever its size (4 KiB for a uint8 table, 64 KiB at the default
 // b = 12 of uint16, 1 MiB at b = 16).  A copy of a small table in LDS, gathered there, was measured against this and bought nothing
 // (profiles/r20_composite.md: 1.58 against 1.59 ms behind a 4x22 net, inside the spread), so there is one path.
+//
+// The composite of a partition follows these, and at the very end the SHADED composite (k_composite_select, k_composite_pick,
+// k_composite_shade_fold and their entries): copies of the fold's structure that leave the kernels above as they are.
 #include "brief_composite.h"
 
 struct CompositeTable { int32_t channel, shift; };      // index = value[channel] >> shift: below 2^tf_bits for every value of the dtype
@@ -450,6 +453,257 @@ int brief_view_composite_part_gather_host(const brief_view_desc *view, const bri
         brief_composite_gather(wins, blocks, row, col, hits_w, tau_w, acc_w, carry, acc_w2, hits[r], run, acc + r * 3);
         tau_run[r] = (int32_t)run;
     }
+    return 0;
+}
+
+}   // extern "C"
+
+// ---- shaded composite: every sample's emission lit by the net's analytic gradient (csrc/brief_composite.h "SHADED composite";
+// composite.render_composite with shade; DESIGN.md "Shaded composite").
+//   k_composite_select      k_composite_fold's walk, lookup and scan with the ray's carry read from tau_run[r]: need[s - s0] = the sample
+//                           is inside, emits and its prefix is below TAU_SAT (brief_composite_need).  It writes nothing else.
+//   k_composite_pick        coords_sel[slot[i]] = coords[i] where need[i]: the needed samples, in the list's order.
+//   k_composite_shade_fold  k_composite_fold with e scaled by s_q (brief_composite_shade_q of the sample's Jacobian row, read only where
+//                           need is 1: at slot[s - s0], or at s - s0 for a dense jac).  A sample that needs no gradient adds 0 as it is.
+// The kernels are copies of the fold's structure: the plain fold stays as it was.
+template <typename T>
+__global__ __launch_bounds__(256) void k_composite_select(brief_view_desc v, ViewChunk ch, const int32_t *__restrict__ k0, const int64_t *__restrict__ off,
+                                                          const T *__restrict__ vals, int C, CompositeTable tb, const int4 *__restrict__ tf,
+                                                          const int32_t *__restrict__ tau_run, int32_t *__restrict__ need)
+{
+    const int G = 1 << ch.lg, sub = threadIdx.x & (G - 1);
+    const int64_t groups = ((int64_t)gridDim.x * blockDim.x) >> ch.lg, nr = ch.r1 - ch.r0;
+    const int64_t iters = (nr + groups - 1) / groups;               // the same for every lane: the scan below needs the whole group
+    int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> ch.lg;
+    for (int64_t it = 0; it < iters; ++it, g += groups) {
+        const ViewRay q = view_ray(v, ch, off, g);
+        const int32_t kb = k0[q.r];
+        uint32_t carry = (uint32_t)tau_run[q.r];
+        for (int64_t sb = q.lo; sb < q.hi; sb += G) {                // a pass; q.lo and q.hi are the group's: its lanes stay together
+            const int64_t s = sb + sub;
+            int4 e = make_int4(0, 0, 0, 0);
+            bool inside = false;
+            if (s < q.hi) {
+                const int32_t k = kb + (int32_t)(s - q.a);
+                inside = brief_view_inside(v, brief_view_at(v, 0, q.base[0], k), brief_view_at(v, 1, q.base[1], k), brief_view_at(v, 2, q.base[2], k));
+                if (inside) e = tf[(int)vals[(s - ch.s0) * C + tb.channel] >> tb.shift];
+            }
+            uint32_t incl = (uint32_t)e.x;                           // at most G * TAU_SAT <= 2^27: no overflow before the saturation
+            for (int o = 1; o < G; o <<= 1) {
+                const uint32_t y = (uint32_t)__shfl_up((int)incl, o, G);
+                if (sub >= o) incl += y;
+            }
+            const uint32_t prefix = brief_composite_add(carry, incl - (uint32_t)e.x);
+            if (s < q.hi) need[s - ch.s0] = brief_composite_need(inside, (uint32_t)e.y, (uint32_t)e.z, (uint32_t)e.w, prefix) ? 1 : 0;
+            carry = brief_composite_add(carry, (uint32_t)__shfl((int)incl, G - 1, G));
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_composite_pick(int64_t n, const int32_t *__restrict__ need, const int64_t *__restrict__ slot,
+                                                        const float *__restrict__ coords, float *__restrict__ coords_sel)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (!need[i]) continue;
+        const int64_t at = slot[i];
+        if (at < 0 || at >= n) continue;                             // (a scan of need never gives one)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) coords_sel[at * 3 + a] = coords[i * 3 + a];
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_composite_shade_fold(brief_view_desc v, ViewChunk ch, const int32_t *__restrict__ k0, const int64_t *__restrict__ off,
+                                                              const T *__restrict__ vals, int C, CompositeTable tb, const int4 *__restrict__ tf,
+                                                              const int32_t *__restrict__ need, const int64_t *__restrict__ slot,
+                                                              const float *__restrict__ jac, brief_composite_shade sh,
+                                                              int32_t *__restrict__ hits, int32_t *__restrict__ tau_run,
+                                                              unsigned long long *__restrict__ acc)
+{
+    const int G = 1 << ch.lg, sub = threadIdx.x & (G - 1);
+    const int64_t groups = ((int64_t)gridDim.x * blockDim.x) >> ch.lg, nr = ch.r1 - ch.r0;
+    const int64_t iters = (nr + groups - 1) / groups;               // the same for every lane: the butterfly below needs the whole group
+    int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> ch.lg;
+    for (int64_t it = 0; it < iters; ++it, g += groups) {
+        const ViewRay q = view_ray(v, ch, off, g);
+        const int32_t kb = k0[q.r];
+        uint32_t carry = (uint32_t)tau_run[q.r];                     // (read by the whole group before its lane 0 writes it, below)
+        int n = 0;
+        unsigned long long m[3] = {0, 0, 0};
+        for (int64_t sb = q.lo; sb < q.hi; sb += G) {                // a pass; q.lo and q.hi are the group's: its lanes stay together
+            const int64_t s = sb + sub;
+            int4 e = make_int4(0, 0, 0, 0);
+            if (s < q.hi) {
+                const int32_t k = kb + (int32_t)(s - q.a);
+                if (brief_view_inside(v, brief_view_at(v, 0, q.base[0], k), brief_view_at(v, 1, q.base[1], k), brief_view_at(v, 2, q.base[2], k))) {
+                    ++n;
+                    e = tf[(int)vals[(s - ch.s0) * C + tb.channel] >> tb.shift];
+                    if (need[s - ch.s0]) {                           // the only samples whose emission reaches the pixel
+                        const int64_t row = slot ? slot[s - ch.s0] : s - ch.s0;
+                        const float *jp = jac + (row * C + tb.channel) * 3;
+                        const float j[3] = {jp[0], jp[1], jp[2]};
+                        const int32_t s_q = brief_composite_shade_q(j, sh.gscale, sh.light, sh.ka_q, sh.kd_q);
+                        e.y = (int)brief_composite_lit((uint32_t)e.y, s_q);
+                        e.z = (int)brief_composite_lit((uint32_t)e.z, s_q);
+                        e.w = (int)brief_composite_lit((uint32_t)e.w, s_q);
+                    }
+                }
+            }
+            uint32_t incl = (uint32_t)e.x;                           // at most G * TAU_SAT <= 2^27: no overflow before the saturation
+            for (int o = 1; o < G; o <<= 1) {
+                const uint32_t y = (uint32_t)__shfl_up((int)incl, o, G);
+                if (sub >= o) incl += y;
+            }
+            const unsigned long long w = brief_composite_w(brief_composite_add(carry, incl - (uint32_t)e.x));
+            m[0] += w * (unsigned long long)(uint32_t)e.y;
+            m[1] += w * (unsigned long long)(uint32_t)e.z;
+            m[2] += w * (unsigned long long)(uint32_t)e.w;
+            carry = brief_composite_add(carry, (uint32_t)__shfl((int)incl, G - 1, G));
+        }
+        for (int o = G >> 1; o >= 1; o >>= 1) {                      // (G is the launch's: every group of the wave takes the same steps)
+            n += __shfl_xor(n, o);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) m[c] += composite_shfl_xor(m[c], o);
+        }
+        if (sub == 0 && n > 0) {                                     // the pixel's owner
+            hits[q.r] += n;
+            tau_run[q.r] = (int32_t)carry;
+            unsigned long long *d = acc + q.r * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) d[c] += m[c];
+        }
+    }
+}
+
+// ---- host side of the shaded entries
+static int check_composite_shade(const brief_composite_shade *sh)
+{
+    if (!sh) return fail(BRIEF_ERR_INVALID, "composite: null shade descriptor");
+    if (sh->ka_q < 0 || sh->ka_q > 256 || sh->kd_q < 0 || sh->kd_q > 256)
+        return fail(BRIEF_ERR_INVALID, "composite: ka_q and kd_q must be 0 .. 256 (round(256 * KA), round(256 * KD) of KA, KD in [0, 1])");
+    for (int a = 0; a < 3; ++a)
+        if (sh->gscale[a] - sh->gscale[a] != 0.f || sh->light[a] - sh->light[a] != 0.f)
+            return fail(BRIEF_ERR_INVALID, "composite: gscale and light must be finite");
+    return 0;
+}
+
+extern "C" {
+
+int brief_view_composite_select(const brief_view_desc *view, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1, int64_t r0, int64_t r1,
+                                int32_t lanes, const void *vals, int elem_kind, int32_t channels, int32_t channel, const int32_t *tf, int32_t tf_bits,
+                                const int32_t *tau_run, int32_t *need, void *stream)
+{
+    ViewChunk ch;
+    CompositeTable tb;
+    if (int rc = check_view_chunk(view, k0, off, s0, s1, r0, r1, lanes, &ch)) return rc;
+    if (!vals || !tau_run || !need) return fail(BRIEF_ERR_INVALID, "composite: null buffer");
+    if (int rc = check_composite_table(elem_kind, channels, channel, tf, tf_bits, &tb)) return rc;
+    const dim3 grid(view_blocks((r1 - r0) << ch.lg)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define COMPOSITE_SELECT(T) hipLaunchKernelGGL((k_composite_select<T>), grid, block, 0, st, *view, ch, k0, off, (const T *)vals, (int)channels, tb, \
+                                               (const int4 *)tf, tau_run, need)
+    if (elem_kind == BRIEF_OUT_U8) COMPOSITE_SELECT(uint8_t); else COMPOSITE_SELECT(uint16_t);
+#undef COMPOSITE_SELECT
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_view_composite_pick(const int32_t *need, const int64_t *slot, const float *coords, int64_t n, float *coords_sel, void *stream)
+{
+    if (!need || !slot || !coords || !coords_sel) return fail(BRIEF_ERR_INVALID, "composite: null buffer");
+    if (n < 1) return fail(BRIEF_ERR_INVALID, "composite: n must be >= 1");
+    hipLaunchKernelGGL(k_composite_pick, dim3(view_blocks(n)), dim3(256), 0, (hipStream_t)stream, n, need, slot, coords, coords_sel);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brief_view_composite_shade_fold(const brief_view_desc *view, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1, int64_t r0,
+                                    int64_t r1, int32_t lanes, const void *vals, int elem_kind, int32_t channels, int32_t channel,
+                                    const int32_t *tf, int32_t tf_bits, const int32_t *need, const int64_t *slot, const float *jac,
+                                    const brief_composite_shade *shade, int32_t *hits, int32_t *tau_run, uint64_t *acc, void *stream)
+{
+    ViewChunk ch;
+    CompositeTable tb;
+    if (int rc = check_view_chunk(view, k0, off, s0, s1, r0, r1, lanes, &ch)) return rc;
+    if (!vals || !need || !jac || !hits || !tau_run || !acc) return fail(BRIEF_ERR_INVALID, "composite: null buffer (slot alone may be NULL: a dense jac)");
+    if (int rc = check_composite_table(elem_kind, channels, channel, tf, tf_bits, &tb)) return rc;
+    if (int rc = check_composite_shade(shade)) return rc;
+    const dim3 grid(view_blocks((r1 - r0) << ch.lg)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define COMPOSITE_SHADE_FOLD(T) hipLaunchKernelGGL((k_composite_shade_fold<T>), grid, block, 0, st, *view, ch, k0, off, (const T *)vals, (int)channels, tb, \
+                                                   (const int4 *)tf, need, slot, jac, *shade, hits, tau_run, (unsigned long long *)acc)
+    if (elem_kind == BRIEF_OUT_U8) COMPOSITE_SHADE_FOLD(uint8_t); else COMPOSITE_SHADE_FOLD(uint16_t);
+#undef COMPOSITE_SHADE_FOLD
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// select, shade_fold and finish on the host CPU, sample after sample: no GPU call.  Every buffer is host memory; vals and the dense jac
+// hold the WHOLE list.
+int brief_view_composite_shade_host(const brief_view_desc *view, const int32_t *k0, const int64_t *off, const void *vals, int elem_kind,
+                                    int32_t channels, int32_t channel, const int32_t *tf, int32_t tf_bits, const int32_t *background,
+                                    const float *jac, const brief_composite_shade *shade, int32_t *need, int32_t *hits, int32_t *tau_run,
+                                    uint64_t *acc, uint8_t *out)
+{
+    CompositeTable tb;
+    CompositeBg bg;
+    if (int rc = check_view(view)) return rc;
+    if (!k0 || !off || !vals || !jac || !out) return fail(BRIEF_ERR_INVALID, "composite: null buffer (need, hits, tau_run and acc alone may be NULL)");
+    if (int rc = check_composite_table(elem_kind, channels, channel, tf, tf_bits, &tb)) return rc;
+    if (int rc = check_composite_bg(background, &bg)) return rc;
+    if (int rc = check_composite_shade(shade)) return rc;
+    for (int32_t i = 0; i < (int32_t)1 << tf_bits; ++i) {
+        const int32_t *e = tf + 4 * (int64_t)i;
+        if (e[0] < 0 || e[0] > BRIEF_COMPOSITE_TAU_SAT) return fail(BRIEF_ERR_INVALID, "composite: a table entry's tau lies outside 0 .. TAU_SAT (32 * 65536)");
+        for (int c = 1; c < 4; ++c)
+            if (e[c] < 0 || e[c] > BRIEF_COMPOSITE_E_MAX) return fail(BRIEF_ERR_INVALID, "composite: a table entry's emission lies outside 0 .. 65280");
+    }
+    const int64_t rays = (int64_t)view->rows * view->cols;
+    if (off[0] != 0) return fail(BRIEF_ERR_INVALID, "composite: off[0] must be 0 (vals and jac hold the whole list)");
+    for (int64_t r = 0; r < rays; ++r) {
+        const int64_t cnt = off[r + 1] - off[r];
+        if (cnt < 0 || k0[r] < 0 || cnt > (int64_t)view->depth - k0[r])
+            return fail(BRIEF_ERR_INVALID, "composite: off must not decrease, and a ray's samples k0 .. k0 + cnt - 1 must lie inside 0 .. depth - 1");
+    }
+    for (int64_t r = 0; r < rays; ++r) {
+        const int32_t row = (int32_t)(r / view->cols), col = (int32_t)(r - (int64_t)row * view->cols);
+        float base[3];
+        for (int a = 0; a < 3; ++a) base[a] = brief_view_base(*view, a, row, col);
+        uint32_t run = 0;
+        uint64_t sum[3] = {0, 0, 0};
+        int32_t n = 0;
+        for (int64_t s = off[r]; s < off[r + 1]; ++s) {
+            const int32_t k = k0[r] + (int32_t)(s - off[r]);
+            if (need) need[s] = 0;
+            if (!brief_view_inside(*view, brief_view_at(*view, 0, base[0], k), brief_view_at(*view, 1, base[1], k), brief_view_at(*view, 2, base[2], k)))
+                continue;
+            ++n;
+            const int64_t at = s * channels + channel;
+            const int value = elem_kind == BRIEF_OUT_U8 ? (int)((const uint8_t *)vals)[at] : (int)((const uint16_t *)vals)[at];
+            const int32_t *e = tf + 4 * (int64_t)(value >> tb.shift);
+            if (brief_composite_need(true, (uint32_t)e[1], (uint32_t)e[2], (uint32_t)e[3], run)) {
+                if (need) need[s] = 1;
+                const int32_t s_q = brief_composite_shade_q(jac + at * 3, shade->gscale, shade->light, shade->ka_q, shade->kd_q);
+                const uint64_t w = brief_composite_w(run);
+                for (int c = 0; c < 3; ++c) sum[c] += w * (uint64_t)brief_composite_lit((uint32_t)e[1 + c], s_q);
+            }
+            run = brief_composite_add(run, (uint32_t)e[0]);
+        }
+        if (hits) hits[r] = n;
+        if (tau_run) tau_run[r] = (int32_t)run;
+        if (acc)
+            for (int c = 0; c < 3; ++c) acc[r * 3 + c] = sum[c];
+        brief_composite_pixel(run, sum, bg.c, out + r * 4);
+    }
+    return 0;
+}
+
+int brief_composite_shade_q_host(const float *jac, int64_t n, const brief_composite_shade *shade, int32_t *s_q)
+{
+    if (!jac || !s_q) return fail(BRIEF_ERR_INVALID, "composite: null buffer");
+    if (n < 1) return fail(BRIEF_ERR_INVALID, "composite: n must be >= 1");
+    if (int rc = check_composite_shade(shade)) return rc;
+    for (int64_t i = 0; i < n; ++i) s_q[i] = brief_composite_shade_q(jac + i * 3, shade->gscale, shade->light, shade->ka_q, shade->kd_q);
     return 0;
 }
 

@@ -197,9 +197,11 @@ def _lanes(mean_count):
     return g
 
 
-def _march(phi, v, kind, dt, scale, vrange, chunk, fold):
+def _march(phi, v, kind, dt, scale, vrange, chunk, fold, with_coords=False):
     """the part every view shares: clip the rays of `v` (lo / hi set), scan, and evaluate the compacted sample list chunk by chunk with
-    the net's own forward entry, handing each chunk to fold(k0, off, s0, s1, r0, r1, lanes, vals).  Returns (k0, total, rays_hit)."""
+    the net's own forward entry, handing each chunk to fold(k0, off, s0, s1, r0, r1, lanes, vals); with_coords: the chunk's
+    coordinates [n, 3] too, as the keyword `coords` (the shaded composite picks the samples it lights from them).
+    Returns (k0, total, rays_hit)."""
     import torch
     L, st = _lib.lib(), _lib.stream_ptr
     dev, ch = phi.params.device, int(phi.data_channel)
@@ -223,7 +225,10 @@ def _march(phi, v, kind, dt, scale, vrange, chunk, fold):
             _lib.check(L.brief_view_coords(C.byref(v), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(coords), st()))
             b = _lib.BatchDesc(coords.data_ptr(), None, None, None, 0, n, 0, 0, 0)
             _lib.check(phi._abi_forward(None, b, vals, kind, scale, vrange, n))
-            fold(k0, off, s0, s1, r0, r1, lanes, vals)
+            if with_coords:
+                fold(k0, off, s0, s1, r0, r1, lanes, vals, coords=coords)
+            else:
+                fold(k0, off, s0, s1, r0, r1, lanes, vals)
     return k0, total, rays_hit
 
 
@@ -959,6 +964,16 @@ def decompress_divide_surface(opt, orig_sideinfos, module_dir, sideinfos_dir, di
     return res
 
 
+def physical_shading(art, direction, up, light, voxel_size):
+    """(light, gscale) of a shaded view of a stored artefact, both physical: the unit direction the light travels, (z, y, x), default
+    the view's own `direction` (a headlight), and per axis the factor between the net's Jacobian and grey levels per physical unit,
+    gradient.voxel_scale / voxel_size.  The surface view's and the shaded composite's."""
+    from . import gradient
+    physical = frame(direction, up)[2] if light is None else _unit3(light, "light")
+    gscale = gradient.voxel_scale(art.dims, art.lo, art.hi, art.norm_range, art.vrange[0], art.vrange[1]) / _vec3(voxel_size, "voxel_size")
+    return physical, gscale
+
+
 def decompress_surface(art, direction, level, up=None, region=None, centre=None, spacing=1.0, depth_spacing=1.0,
                        size=None, depth=None, voxel_size=(1, 1, 1), channel=0, side="above", refine=8, shading=True, light=None, device="cuda",
                        chunk=None):
@@ -982,8 +997,7 @@ def decompress_surface(art, direction, level, up=None, region=None, centre=None,
         if why is not None:
             raise ValueError("normals and shading need the analytic Jacobian: %s; ask for shading=False" % why)
     view = make_view(art.dims, direction, up, centre, spacing, depth_spacing, size, depth, voxel_size, region)
-    physical = frame(direction, up)[2] if light is None else _unit3(light, "light")
-    gscale = gradient.voxel_scale(art.dims, art.lo, art.hi, art.norm_range, art.vrange[0], art.vrange[1]) / _vec3(voxel_size, "voxel_size")
+    physical, gscale = physical_shading(art, direction, up, light, voxel_size)
     out = render_surface(art.load_phi(device), view, level, art.lo, art.hi, art.out_kind, art.norm_range, art.vrange,
                          channel=channel, side=side, refine=refine, shading=shading, light=physical, gscale=gscale, chunk=chunk)
     res = {k: (x.cpu().numpy() if hasattr(x, "cpu") else x) for k, x in out.items()}

@@ -66,7 +66,8 @@ float32 [rows, cols, 5] = depth, normal (z, y, x), shade, with NaN depth where n
 view options that shape the geometry apply; not with `--view-mode` or `--view-offset`).
 
     python decompress.py -p <run yaml> -c <.../compressed> --region :,:,: --view dz,dy,dx --view-composite 'L:r,g,b,a;L:r,g,b,a;...'|@file
-        [--view-composite-channel C] [--view-background r,g,b] [--view-composite-bits B] -o out.png|out.npy
+        [--view-composite-channel C] [--view-background r,g,b] [--view-composite-bits B]
+        [--view-composite-shade KA,KD [--view-composite-light lz,ly,lx]] -o out.png|out.npy
 
 `--view-composite SPEC` renders the view through a TRANSFER FUNCTION instead: every sample of a ray is classified by channel C of the
 integer decode (control points `level:r,g,b,a`, levels strictly ascending and before `Decompress.postprocess`, colours 0 .. 255, `a` the
@@ -74,6 +75,11 @@ opacity over one voxel of depth; linear between the points, constant outside) an
 in integers: the image does not depend on the chunking or the run.  `.png` holds R,G,B, `.npy` uint8 [rows, cols, 4] = R,G,B,A
 (artefacts with an identity postprocess; the view options that shape the geometry apply; not with `--view-mode`,
 `--view-offset`, `--view-surface...`, `--mip`, `--gradient`, `--hessian`, `--shape` or `--step`).
+`--view-composite-shade KA,KD` lights every sample's emission by the stored net's own analytic gradient: the emission is scaled by
+KA + KD * |n . l| (KA, KD in [0, 1]; two-sided, a density has no outside), n the direction of the physical gradient (`--voxel-size`)
+and l the physical direction `--view-composite-light` travels (default: the view direction, a headlight).  Opacity and the A channel
+do not change, and the gradient is evaluated only at samples that emit and are not hidden.  fp32 SIREN artefacts up to 1024 features
+(quantised ones included); a DivideTask artefact with `--view-composite-shade` is refused (a follow-up).
 
     python decompress.py -p <run yaml> -c <.../compressed of a DivideTask job> --region :,:,: --view dz,dy,dx --view-composite SPEC --view-owner nearest ... -o out.png|out.npy
 
@@ -133,10 +139,15 @@ def main(argv=None):
     ap.add_argument("--view-composite-channel", type=int, default=None, metavar="C", help="the channel the transfer function classifies (default 0)")
     ap.add_argument("--view-background", default=None, metavar="r,g,b", help="the colour behind the composite, 0 .. 255 each (default 0,0,0)")
     ap.add_argument("--view-composite-bits", type=int, default=None, metavar="B", help="the transfer table has 2^B rows (default 8 for uint8, 12 for uint16)")
+    ap.add_argument("--view-composite-shade", default=None, metavar="KA,KD",
+                    help="light the composite by the net's analytic gradient: emission x (KA + KD |n . l|), the ambient and the diffuse weight each in [0, 1]")
+    ap.add_argument("--view-composite-light", default=None, metavar="lz,ly,lx",
+                    help="the physical direction the light of --view-composite-shade travels (default: the view direction)")
     ap.add_argument("--voxel-size", default=None, metavar="sz,sy,sx", help="physical extent of a voxel per axis (default 1,1,1)")
     ap.add_argument("-o", required=True, help="output file (.tif / .tiff / .npy / .png / .jpg)")
     args = ap.parse_args(argv)
-    if any(v is not None for v in (args.view_composite, args.view_composite_channel, args.view_background, args.view_composite_bits)):
+    if any(v is not None for v in (args.view_composite, args.view_composite_channel, args.view_background, args.view_composite_bits,
+                                   args.view_composite_shade, args.view_composite_light)):
         _composite_refusals(args)     # every refusal by name, before the GPU path is imported
     if args.hessian is not None:
         why = "each writes a result of its own; ask for one of them"
@@ -390,8 +401,8 @@ def _surface(args, opt, region, divide):
 
 def _composite_refusals(args):
     if args.view_composite is None:
-        raise SystemExit("--view-composite-channel / --view-background / --view-composite-bits describe a composite: give its transfer function "
-                         "with --view-composite SPEC")
+        raise SystemExit("--view-composite-channel / --view-background / --view-composite-bits / --view-composite-shade / --view-composite-light "
+                         "describe a composite: give its transfer function with --view-composite SPEC")
     if args.view is None:
         raise SystemExit("--view-composite renders a --view through a transfer function: give the view's direction with --view dz,dy,dx")
     from brief_pytorch_amd.view import OWNERS
@@ -414,6 +425,7 @@ def _composite_refusals(args):
         raise SystemExit("--view-composite writes an RGB image as .png or the RGBA array as .npy (got %s): the .tif writer holds one channel "
                          "per page, and no other format is supported" % (ext or "no extension"))
     from brief_pytorch_amd import composite
+    from brief_pytorch_amd import view as view_mod
     try:
         composite.parse_transfer(args.view_composite)
         if args.view_background is not None:
@@ -424,8 +436,20 @@ def _composite_refusals(args):
         raise SystemExit("--view-composite-channel %d: a channel is 0 or above" % args.view_composite_channel)
     if args.view_composite_bits is not None and not 1 <= args.view_composite_bits <= 16:
         raise SystemExit("--view-composite-bits %d: the transfer table has 2^B rows, B 1 .. 8 for uint8 and 1 .. 16 for uint16" % args.view_composite_bits)
+    if args.view_composite_light is not None and args.view_composite_shade is None:
+        raise SystemExit("--view-composite-light names the direction the light of a shaded composite travels: give the weights of the shading "
+                         "with --view-composite-shade KA,KD")
+    if args.view_composite_shade is not None:
+        try:
+            composite.shade_quant(_floats(args.view_composite_shade, 2, "--view-composite-shade"))
+            if args.view_composite_light is not None:
+                view_mod._unit3(_floats(args.view_composite_light, 3, "--view-composite-light"), "--view-composite-light")
+        except ValueError as e:
+            raise SystemExit("--view-composite-shade: %s" % e)
     if divide and args.view_owner is None:
         raise SystemExit("--view-composite: " + composite.DIVIDE_REFUSAL)
+    if divide and args.view_composite_shade is not None:
+        raise SystemExit("--view-composite-shade: " + composite.DIVIDE_SHADE_REFUSAL)
 
 
 def _write_rgb_png(path, rgb):
@@ -445,6 +469,10 @@ def _composite(args, opt, region, divide):
             render = lambda *a, **kw: decompress_divide_composite(opt, side_path, module, blocks_dir, *a, **kw)
         else:
             render = lambda *a, **kw: NFGR.decompress_composite(opt, module, side_path, *a, **kw)
+        shading = {}
+        if args.view_composite_shade is not None:                 # (a SingleTask artefact: _composite_refusals refused a DivideTask one)
+            shading = dict(shade=_floats(args.view_composite_shade, 2, "--view-composite-shade"),
+                           light=_floats(args.view_composite_light, 3, "--view-composite-light") if args.view_composite_light is not None else None)
         img, hits, stats = render(
             _floats(args.view, 3, "--view"), args.view_composite,
             up=_floats(args.view_up, 3, "--view-up") if args.view_up is not None else None, region=region,
@@ -453,8 +481,8 @@ def _composite(args, opt, region, divide):
             voxel_size=_floats(args.voxel_size, 3, "--voxel-size") if args.voxel_size is not None else (1, 1, 1),
             channel=args.view_composite_channel or 0,
             background=_floats(args.view_background, 3, "--view-background") if args.view_background is not None else (0, 0, 0),
-            bits=args.view_composite_bits, return_hits=True)
-    except ValueError as e:                                       # a refusal (artefact kind, dtype, normalisation, postprocess, transfer, geometry)
+            bits=args.view_composite_bits, return_hits=True, **shading)
+    except ValueError as e:                                       # a refusal (artefact kind, dtype, normalisation, postprocess, transfer, geometry, net)
         raise SystemExit("--view-composite: %s" % e)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -464,10 +492,11 @@ def _composite(args, opt, region, divide):
     else:
         data = np.ascontiguousarray(img[..., :3])
         _write_rgb_png(args.o, data)
-    print("%s composite view %s of region %s: image %s, dtype %s, %d of %d rays hit, %d samples evaluated, decoded in %.3f s -> %s" % (
+    print("%s composite view %s of region %s: image %s, dtype %s, %d of %d rays hit, %d samples evaluated%s, decoded in %.3f s -> %s" % (
         "DivideTask (%d of %d blocks hit, owner %s, %d samples in the second pass)" % (
             stats["blocks_hit"], stats["blocks"], args.view_owner, stats["samples_second_pass"]) if divide else "SingleTask",
-        args.view, args.region, tuple(data.shape), data.dtype, stats["rays_hit"], stats["rays"], stats["samples_evaluated"], dt, args.o))
+        args.view, args.region, tuple(data.shape), data.dtype, stats["rays_hit"], stats["rays"], stats["samples_evaluated"],
+        ", %d of them shaded (%s)" % (stats["samples_shaded"], args.view_composite_shade) if "samples_shaded" in stats else "", dt, args.o))
     return 0
 
 

@@ -813,6 +813,51 @@ int brief_view_composite_part_gather_host(const brief_view_desc *view, const bri
                                           const int32_t *hits_w, const int32_t *tau_w, const uint64_t *acc_w, const int32_t *carry,
                                           const uint64_t *acc_w2, int32_t *hits, int32_t *tau_run, uint64_t *acc);
 
+/* ---- shaded composite: every sample's emission lit by the net's analytic gradient (csrc/brief_composite.inc, .h) ---------------------
+ * Opacity is not touched: tau, the prefix P_i, hits, tau_run and the image's A are the plain composite's, bit for bit.  The emission of
+ * a sample is scaled by a two-sided Lambert term in Q8 (csrc/brief_composite.h has the arithmetic, every fp32 operation rounded on its
+ * own): g_a = jac[.][channel][a] * gscale[a], c_q = round(256 * |g . light| / |g|) (256 where |g| is 0 or not finite),
+ * s_q = min(256, ka_q + ((kd_q * c_q + 128) >> 8)), e'_c = (e_c * s_q + 128) >> 8, acc_c += W(P_i) * e'_c.
+ * A sample NEEDS a gradient iff it is inside the clip box, its table row has eR | eG | eB != 0 and P_i < TAU_SAT; every other sample
+ * contributes 0 whatever its shade, so the Jacobian is evaluated on the needed samples alone.  Per chunk of the list, after
+ * brief_view_coords and the integer forward:
+ *   brief_view_composite_select      brief_view_composite_fold's walk, lookup and scan, with the ray's carry read from tau_run[r]; it
+ *                                    writes nothing to the pixel state, only need[s - s0] (int32 0 | 1) for every sample of the chunk;
+ *   (caller)                         slot (int64) = the exclusive scan of need, m = its total (one host read); m == 0: the chunk lights
+ *                                    nothing, fold it with brief_view_composite_fold;
+ *   brief_view_composite_pick        coords_sel[slot[i]] = coords[i] where need[i], i < n: the needed samples in the list's order (an
+ *                                    entry whose slot lies outside 0 .. n - 1 is skipped);
+ *   (caller)                         jac[m][channels][3] = brief_siren_jac_forward on coords_sel[0 .. m), value NULL;
+ *   brief_view_composite_shade_fold  brief_view_composite_fold with the lit emission: the same walk, scan, butterfly and single plain
+ *                                    read-modify-write of hits, tau_run and acc by the pixel's owner, no atomics.  A lane reads jac only
+ *                                    where need is 1, at row slot[s - s0]; slot == NULL is the identity (a dense jac, one row per
+ *                                    sample of the chunk).
+ * The finish is brief_view_composite_finish.  need reads integers only: the selection, like the image, does not depend on chunking,
+ * `lanes` or the run.  ka_q = 256, kd_q = 0 is the plain composite.  Every device entry only enqueues on `stream`.
+ * brief_view_composite_shade_host is select, shade_fold and finish on the host CPU, without any GPU call: every buffer is host memory,
+ * off[0] is 0, vals and the dense jac [off[rays]][channels][3] hold the whole list; need (int32 [off[rays]]), hits, tau_run and acc may
+ * be NULL.  brief_composite_shade_q_host gives s_q[i] of the rows jac[i][3], i < n.
+ * Limits (BRIEF_ERR_INVALID with a message naming the limit, before any launch): those of brief_view_composite_fold; no null buffer
+ * (slot of the fold excepted); n >= 1; ka_q and kd_q 0 .. 256; gscale and light finite. */
+typedef struct {
+    float gscale[3];                         /* grey levels per physical unit and coordinate unit, per axis (z, y, x) */
+    float light[3];                          /* the unit direction the light travels, physical (z, y, x) */
+    int32_t ka_q, kd_q;                      /* round(256 * KA), round(256 * KD): 0 .. 256 */
+} brief_composite_shade;
+int brief_view_composite_select(const brief_view_desc *view, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1, int64_t r0, int64_t r1,
+                                int32_t lanes, const void *vals, int elem_kind, int32_t channels, int32_t channel, const int32_t *tf, int32_t tf_bits,
+                                const int32_t *tau_run, int32_t *need, void *stream);
+int brief_view_composite_pick(const int32_t *need, const int64_t *slot, const float *coords, int64_t n, float *coords_sel, void *stream);
+int brief_view_composite_shade_fold(const brief_view_desc *view, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1, int64_t r0,
+                                    int64_t r1, int32_t lanes, const void *vals, int elem_kind, int32_t channels, int32_t channel,
+                                    const int32_t *tf, int32_t tf_bits, const int32_t *need, const int64_t *slot, const float *jac,
+                                    const brief_composite_shade *shade, int32_t *hits, int32_t *tau_run, uint64_t *acc, void *stream);
+int brief_view_composite_shade_host(const brief_view_desc *view, const int32_t *k0, const int64_t *off, const void *vals, int elem_kind,
+                                    int32_t channels, int32_t channel, const int32_t *tf, int32_t tf_bits, const int32_t *background,
+                                    const float *jac, const brief_composite_shade *shade, int32_t *need, int32_t *hits, int32_t *tau_run,
+                                    uint64_t *acc, uint8_t *out);
+int brief_composite_shade_q_host(const float *jac, int64_t n, const brief_composite_shade *shade, int32_t *s_q);
+
 /* ---- Hessian decode of an fp32 SIREN (csrc/brief_hess.inc) ------------------------------------------------------------------------
  * value[n][cout] and jac[n][cout][cin] as brief_siren_jac_forward gives them, and hess[n][cout][nh] = d2 phi_c / d x_a d x_b (x_n), the
  * analytic second derivatives with respect to the coordinates in coordinate units; with output_act, of the activated output.  nh = 6 in
