@@ -933,7 +933,7 @@ static int launch_wgrad(const brief_siren_desc &d, const WgradArgs &wa, int bloc
     } else {
 #define BRIEF_CASE(NTV)                                                                                    \
     case NTV:                                                                                              \
-        hipLaunchKernelGGL((k_wgrad<NTV>), dim3(blocks), dim3(512), sizeof(float) * wgrad_lds_floats(NTV), st, wa); \
+        hipLaunchKernelGGL((k_wgrad<NTV>), dim3(blocks), dim3(512), sizeof(float) * wgrad_lds_floats_ct(NTV), st, wa); \
         break;
         switch (nt) {
             BRIEF_CASE(1) BRIEF_CASE(2) BRIEF_CASE(3) BRIEF_CASE(4)

@@ -64,6 +64,19 @@ constexpr int wgrad_qt(int NT) { return (NT + wgrad_nq(NT) - 1) / wgrad_nq(NT); 
 #ifndef BRIEF_WGRAD_FRAG_PIPE2
 #define BRIEF_WGRAD_FRAG_PIPE2 1      // the same for the two-k-slice layouts (4 and 6 tiles per side): both of a wave's k-groups requested up front
 #endif
+// (the pipelined branch of the 8-tile layout takes no fragment-side bias sums: without the staged ones the hidden bias gradients would be silent zeros)
+static_assert(!(BRIEF_WGRAD_FRAG_PIPE && !BRIEF_WGRAD_STAGE_BIAS), "BRIEF_WGRAD_FRAG_PIPE needs BRIEF_WGRAD_STAGE_BIAS: the pipelined 8-tile branch has no other bias sums");
+// The operand feed of the compile-time 8-tile rectangular layout (the headline's k_wgrad<8>).  1: both panels of a chunk go global -> LDS by LDS-DMA
+// (16 bytes per lane, no operand data in VGPRs), the sine and the bias sums are taken in place by the thread that fetched a piece.  0: the
+// register-staged feed every other layout has (A/B builds).  The LDS image of the DMA feed has unpadded 128-byte rows — one wave-level DMA
+// instruction writes 1 KiB at wave-uniform base + lane * 16, i.e. 8 whole rows — with the 16-byte piece index XOR-ed by (row >> 1) & 7: a
+// ds_read_b128 is served in 16-lane groups {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} (+ 32), whose rows must spread over the 16 (row parity, slot)
+// pairs of the 256-byte bank row; row & 7 would put rows r and r + 24 of a group on one slot (2-way), (row >> 1) & 7 does not.  The swizzle is on
+// the SOURCE address of the DMA and on the fragment reads; the LDS destination stays lane-linear.
+#ifndef BRIEF_WGRAD_DMA_FEED
+#define BRIEF_WGRAD_DMA_FEED 1
+#endif
+constexpr bool wgrad_dma_feed(int NT, int QT) { return BRIEF_WGRAD_DMA_FEED && BRIEF_WGRAD_FRAG_PIPE && NT != 0 && QT == 8 && !BRIEF_WGRAD_LIST(QT); }
 constexpr int wgrad_wmk(int QT) { return QT >= 2 ? 2 : 1; }
 constexpr int wgrad_wnk(int QT) { return QT >= 7 ? 4 : (QT >= 2 ? 2 : 1); }
 constexpr bool wgrad_list(int QT) { return BRIEF_WGRAD_LIST(QT); }      // LIST mode (below): every wave owns a run of the QT^2 tiles in row-major order
@@ -77,6 +90,8 @@ constexpr int wgrad_lds_floats(int NT)
     const int fold = (WK - 1) * NWv * TN * 1024 + (WK - 1) * NWv * 64, panels = 4 * 32 * QT * 36;
     return fold > panels ? fold : panels;
 }
+// ... of the compile-time widths' k_wgrad<NT>: the DMA-fed layout has unpadded rows (two buffers x two panels x 256 rows x 128 bytes = 128 KiB)
+constexpr int wgrad_lds_floats_ct(int NT) { return wgrad_dma_feed(NT, wgrad_qt(NT)) ? 4 * 32 * wgrad_qt(NT) * 32 : wgrad_lds_floats(NT); }
 
 // NT > 0: compile-time width.  NT == 0: run-time width above 16 tiles (k_lean's nets), QTR tiles per quadrant side, ceil(nt / 8)
 // quadrants per side; the last quadrant row / column may hold fewer than QTR tiles (its missing rows are staged as zeros).
@@ -96,6 +111,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad(const WgradArgs a)
     constexpr bool LIST = wgrad_list(QT);
     constexpr int LCNT = QT * QT / 8, LREM = QT * QT % 8;      // tiles per wave; the last LREM waves (on different SIMDs, LREM <= 4) take one more
     constexpr bool HET7 = QT == 7 && !LIST;
+    constexpr bool DMA_FEED = wgrad_dma_feed(NT, QT) && !LIST && !HET7;      // (= !RTW && QT == 8: see BRIEF_WGRAD_DMA_FEED)
     // XS: 9, 25 and 49 tiles are 8 n + 1.  Given whole to one wave, the odd tile makes that wave's SIMD the slowest (3 tiles against 2 at QT = 3, 7 against 6 at 5,
     // 13 against 12 at 7); instead waves 0 .. 3 — one per SIMD — each take ONE of the four k-groups of every chunk of it into an extra accumulator, and wave 0 adds the
     // three partners' partial tiles through the (by then dead) LDS panels at the end, in wave order.  Roles 0 .. 3: the wave number = the k-group; 4: no share; 5 (HET7): wave 7.
@@ -215,6 +231,42 @@ __global__ __launch_bounds__(512, 2) void k_wgrad(const WgradArgs a)
 //  clamped re-load of the last one and for workgroups that owe no bias gradient)
 #define WG_BIAS_M(i, cm_) { bsum[i] = __fmaf_rn((cm_), (ra[i].x + ra[i].y) + (ra[i].z + ra[i].w), bsum[i]); }      /* rows past a short quadrant's end were loaded as zeros */
 #define WG_BIAS(i) WG_BIAS_M(i, 1.0f)
+    // DMA feed (8 tiles per side, compile-time width).  Piece e = tid + 512 i of a panel is 16 bytes of row e >> 3; one wave's 64 pieces of a pass are
+    // 8 whole rows, written lane-linear at float e * 4 of the panel.  The lane at slot e & 7 fetches piece (e & 7) ^ sw(row), sw(row) = (row >> 1) & 7 — the
+    // same for every pass (512 pieces = 64 rows) — so piece p of a row sits at slot p ^ sw(row), where the fragment reads look for it.
+    constexpr int PANEL_D = QP * 32;                                    // unpadded panel (floats); a buffer is [A panel | B panel]
+    typedef __attribute__((address_space(3))) void wg_lds_void;
+    const int voff_dma = ((tid >> 3) * 8 + ((tid & 7) ^ ((tid >> 4) & 7))) * 16;
+#define WG_DMA_ISSUE(buf, cc)                                                                                          \
+    _Pragma("unroll") for (int i = 0; i < NLD; ++i) {                                                                  \
+        float *dst_ = smem + (buf) * 2 * PANEL_D + (wave * 64 + 512 * i) * 4;      /* wave-uniform; the hardware adds lane * 16 */ \
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsD, (wg_lds_void *)dst_, 16, voff_dma, (int)((cc) * (FP * 128)) + i * 8192, 0, BRIEF_WGRAD_AUX); \
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsZ, (wg_lds_void *)(dst_ + PANEL_D), 16, voff_dma, (int)((cc) * (FP * 128)) + i * 8192, 0, BRIEF_WGRAD_AUX); \
+    }
+// LDS-DMA data is ordered for a ds_read by the issuing wave's own vmcnt only (and, for the other waves, by a barrier behind it)
+// (the sched_barrier pins the MFMAs written before the wait in front of it: register-only instructions are not ordered by the "memory" clobber, and the
+//  wait would otherwise drift up to the DMA issue and stall the wave there for the whole fetch)
+#define WG_DMA_WAIT() { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// the thread that fetched a piece finishes it in place: delta piece -> bias sum (the add order of WG_BIAS: a row's eight sums meet in the XOR tree of the
+// epilogue, which gives the same bits whichever lane holds which piece), phase piece -> sine, written back where it lies
+#define WG_DMA_FINISH(buf, i)                                                                                          \
+    {                                                                                                                  \
+        float *pa_ = smem + (buf) * 2 * PANEL_D + (tid + 512 * (i)) * 4;                                               \
+        if (want_bias) {                                                                                               \
+            const float4 dv_ = *reinterpret_cast<const float4 *>(pa_);                                                 \
+            bsum[i] += (dv_.x + dv_.y) + (dv_.z + dv_.w);                                                              \
+        }                                                                                                              \
+        float4 h_ = *reinterpret_cast<const float4 *>(pa_ + PANEL_D);                                                  \
+        h_.x = BRIEF_SIN_REV(h_.x); h_.y = BRIEF_SIN_REV(h_.y);   /* the stash holds revolutions */                    \
+        h_.z = BRIEF_SIN_REV(h_.z); h_.w = BRIEF_SIN_REV(h_.w);                                                        \
+        *reinterpret_cast<float4 *>(pa_ + PANEL_D) = h_;                                                               \
+    }
+    if constexpr (DMA_FEED) {
+        WG_DMA_ISSUE(0, c0)
+        WG_DMA_WAIT();
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) WG_DMA_FINISH(0, i)
+    } else {
     WG_ISSUE(c0)
 #pragma unroll
     for (int i = 0; i < NLD; ++i) { WG_STAGE_A(0, i) WG_STAGE_B(0, i) }
@@ -226,11 +278,26 @@ __global__ __launch_bounds__(512, 2) void k_wgrad(const WgradArgs a)
         const int64_t cn = c0 + 1 < c1 ? c0 + 1 : c1 - 1;
         WG_ISSUE(cn)
     }
+    }
     lds_barrier();
 #ifdef BRIEF_STAMPS
     float st_acc[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     long long st_last = clock64();
 #endif
+// a k-group of the rectangular layouts: every tile of the wave's TM x TN block takes the group's four k-steps
+#define WG_MFMAS(AF, BF)                                                                                               \
+        {                                                                                                              \
+            _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                           \
+                _Pragma("unroll") for (int jn = 0; jn < TN; ++jn) {                                                    \
+                    if ((MEX || wmk * TM + i < QT) && (NEX || wnk * TN + jn < QT)) {                                   \
+                        acc[i][jn] = MFMA(AF[i].x, BF[jn].x, acc[i][jn]);                                              \
+                        acc[i][jn] = MFMA(AF[i].y, BF[jn].y, acc[i][jn]);                                              \
+                        acc[i][jn] = MFMA(AF[i].z, BF[jn].z, acc[i][jn]);                                              \
+                        acc[i][jn] = MFMA(AF[i].w, BF[jn].w, acc[i][jn]);                                              \
+                    }                                                                                                  \
+                }                                                                                                      \
+            }                                                                                                          \
+        }
     if constexpr (LIST || HET7) {
     // (one copy of the whole chunk loop per role — a role test INSIDE the loop makes the compiler carry two sets of accumulators through
     //  the merge points and spill; every wave meets the same barriers in either copy.  The rectangular layouts below keep their plain
@@ -342,6 +409,52 @@ __global__ __launch_bounds__(512, 2) void k_wgrad(const WgradArgs a)
         if (LIST ? (LREM > 0 && wave >= 8 - LREM) : wave == 7) chunk_loop(RoleC<1>{});
         else chunk_loop(RoleC<0>{});
     }
+    } else if constexpr (DMA_FEED) {
+    // After the barrier that ended chunk c - 1 every wave has left buffer cur ^ 1.  Chunk c + 1's sixteen DMA instructions per wave (eight per thread: 4 delta + 4
+    // phase pieces) are issued into it BEHIND chunk c's last fragment read — behind the builtin hipcc waits vmcnt(0) in front of the next ds_read of any LDS
+    // address, so issued at the top of the chunk they would stall every k-group's fragment reads for the whole fetch — and land under k-group 2's MFMAs; in the
+    // shadow of k-group 3 the wave waits for its OWN pieces and finishes them in place; the chunk-end barrier (lgkmcnt(0) + s_barrier: it does not drain VMEM,
+    // and nothing is in flight there) publishes the buffer, whose fragments are read one phase later.  No VGPR carries operand data from one iteration to the
+    // next; the last chunk is its own copy of the body with nothing to stage.  (Measured beside it, profiles/r22_wgrad_feed.md: wait + finish behind k-group 3,
+    // and the issue at the top of the chunk as a hand-written statement that hipcc does not count — both slower.)
+    const int sw_d = ((ln >> 1) & 7) * 4;
+#define WG_READ_FRAGS_D(gq_, AF, BF)                                                                                   \
+        {                                                                                                              \
+            const int fo_ = ln * 32 + ((8 * (gq_) + 4 * hi) ^ sw_d);                                                   \
+            _Pragma("unroll") for (int i = 0; i < TM; ++i) AF[i] = *reinterpret_cast<const float4 *>(As + 1024 * (wmk * TM + i) + fo_); \
+            _Pragma("unroll") for (int jn = 0; jn < TN; ++jn) BF[jn] = *reinterpret_cast<const float4 *>(Bs + 1024 * (wnk * TN + jn) + fo_); \
+        }
+#define WG_DMA_CHUNK(ST)                                                                                               \
+    {                                                                                                                  \
+        const int cur = (int)(c - c0) & 1;                                                                             \
+        const float *As = smem + cur * 2 * PANEL_D, *Bs = As + PANEL_D;                                                \
+        STAMP(0)                                                                                                       \
+        float4 af0[TM], bf0[TN], af1[TM], bf1[TN];                                                                     \
+        WG_READ_FRAGS_D(0, af0, bf0)                                                                                   \
+        WG_READ_FRAGS_D(1, af1, bf1)                                                                                   \
+        __builtin_amdgcn_sched_barrier(0);                                                                             \
+        WG_MFMAS(af0, bf0)                                                                                             \
+        WG_READ_FRAGS_D(2, af0, bf0)                                                                                   \
+        __builtin_amdgcn_sched_barrier(0);                                                                             \
+        WG_MFMAS(af1, bf1)                                                                                             \
+        WG_READ_FRAGS_D(3, af1, bf1)                                                                                   \
+        __builtin_amdgcn_sched_barrier(0);                                                                             \
+        if (ST) { WG_DMA_ISSUE(cur ^ 1, c + 1) }                                                                       \
+        WG_MFMAS(af0, bf0)                                                                                             \
+        if (ST) { WG_DMA_WAIT(); WG_DMA_FINISH(cur ^ 1, 0) WG_DMA_FINISH(cur ^ 1, 2) }                                 \
+        WG_MFMAS(af1, bf1)                                                                                             \
+        if (ST) { WG_DMA_FINISH(cur ^ 1, 1) WG_DMA_FINISH(cur ^ 1, 3) }                                                \
+        STAMP(1)                                                                                                       \
+    }
+    int64_t c = c0;
+    for (; c + 1 < c1; ++c) {
+        WG_DMA_CHUNK(1)
+        lds_barrier();
+        STAMP(3)
+    }
+    WG_DMA_CHUNK(0)
+#undef WG_DMA_CHUNK
+#undef WG_READ_FRAGS_D
     } else {
     for (int64_t c = c0; c < c1; ++c) {
         const int cur = (int)(c - c0) & 1;
@@ -359,19 +472,6 @@ __global__ __launch_bounds__(512, 2) void k_wgrad(const WgradArgs a)
                 const int nt = wnk * TN + jn;                                                                          \
                 BF[jn] = make_float4(0.f, 0.f, 0.f, 0.f);                                                              \
                 if (NEX || nt < QT) BF[jn] = *reinterpret_cast<const float4 *>(Bs + (32 * nt + ln) * LDSW + 8 * (gq_) + 4 * hi); \
-            }                                                                                                          \
-        }
-#define WG_MFMAS(AF, BF)                                                                                               \
-        {                                                                                                              \
-            _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                           \
-                _Pragma("unroll") for (int jn = 0; jn < TN; ++jn) {                                                    \
-                    if ((MEX || wmk * TM + i < QT) && (NEX || wnk * TN + jn < QT)) {                                   \
-                        acc[i][jn] = MFMA(AF[i].x, BF[jn].x, acc[i][jn]);                                              \
-                        acc[i][jn] = MFMA(AF[i].y, BF[jn].y, acc[i][jn]);                                              \
-                        acc[i][jn] = MFMA(AF[i].z, BF[jn].z, acc[i][jn]);                                              \
-                        acc[i][jn] = MFMA(AF[i].w, BF[jn].w, acc[i][jn]);                                              \
-                    }                                                                                                  \
-                }                                                                                                      \
             }                                                                                                          \
         }
         // The next chunk's staging rides in the shadow of the LAST two MFMA groups: its global loads were
@@ -453,6 +553,9 @@ __global__ __launch_bounds__(512, 2) void k_wgrad(const WgradArgs a)
 #undef WG_STAGE_B
 #undef WG_BIAS
 #undef WG_BIAS_M
+#undef WG_DMA_ISSUE
+#undef WG_DMA_WAIT
+#undef WG_DMA_FINISH
     if (WK > 1) {
         // fold the k-slices, one row of wave tiles at a time: slices 1..WK-1 park accumulator row i in LDS (the panels are dead now:
         // the loop ended on a barrier), slice 0 adds them in slice order (row by row so that the area never exceeds the panels)
