@@ -96,6 +96,17 @@ int64_t brief_param_count(const brief_siren_desc *d);
 int64_t brief_packed_count(const brief_siren_desc *d);
 /* bytes of scratch a train step of n samples needs (activation stash + gradient slabs) */
 int64_t brief_train_workspace_bytes(const brief_siren_desc *d, int64_t n);
+/* Scratch.  This holds for every workspace of the train, fit and decode entries (this one, brief_forward_workspace_bytes,
+ * brief_quant_workspace_bytes, the families' brief_*_train_workspace_bytes) and for the fragment-ordered copies (brief_packed_count,
+ * brief_siren_jac_packed_count, the families' *_packed_count): what the buffer holds on entry is irrelevant: it need not be
+ * initialised and may hold anything, NaN bit patterns and the data of an earlier, larger batch included; what it holds on exit is
+ * unspecified.  No entry reads or writes outside [workspace, workspace + bytes) of the size its *_bytes function returns for the call's
+ * n (a larger buffer is accepted; the part behind that size is left alone), and no entry keeps state in a workspace from one call to
+ * the next: brief_multi_fit writes the device table of a group into the first job's workspace again in every call.
+ * brief_siren_repack (and the families' *_repack, brief_siren_jac_repack) writes all brief_packed_count floats of `packed`, padding
+ * included.  A train step writes all brief_param_count floats of `grads` (the bvals span of an FFN as zeros), loss_out, and n * cout
+ * floats of yhat_out where given.  The only caller memory that carries state between calls is what the signatures name as such:
+ * params, packed, state1 / state2.  tests/test_gpu_scratch_contract.py holds every train, fit and decode kernel to this. */
 
 /* canonical params -> fragment-ordered copies read by the kernels.  Call after every change of
  * `params` made outside brief_optim_step's caller loop (init, load_model utils/ModelSave.py:8-27). */
