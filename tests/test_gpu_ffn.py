@@ -18,58 +18,10 @@ import torch
 from brief_pytorch_amd import _lib
 from brief_pytorch_amd.fit import Fitter
 from brief_pytorch_amd.networks import FFN, init_phi
+from tests._family_ref import BAND_FACTOR, FLOOR, band_check, rand_coords, torch_ffn, torch_loss      # noqa: F401 (BAND_FACTOR, FLOOR: test_gpu_ffn_framework.py)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BAND_FACTOR = 4.0     # fused fp32 vs float64  <=  4 x (torch fp32 vs float64) + floor
-FLOOR = 1e-5          # relative to max |reference|: the reduction-order spread of fp32 sums over K <= 1024 terms
-
-
-def torch_ffn(m, coords, dtype):
-    """the reference's forward: emb = [sin(2 pi x B^T), cos(2 pi x B^T)], Linear + ReLU ..., Linear (skip=False)"""
-    p = m.params.detach().cpu().to(dtype)
-    E, cin = m.embsize, m.coords_channel
-    B = p[:E * cin].view(E, cin)
-    x = coords.detach().cpu().to(dtype)
-    t = (2. * math.pi * x) @ B.T
-    h = torch.cat([torch.sin(t), torch.cos(t)], -1)
-    ws, off = [], E * cin
-    for (o, i) in m._shapes:
-        W = p[off:off + o * i].view(o, i).clone().requires_grad_(True)
-        b = p[off + o * i:off + o * i + o].clone().requires_grad_(True)
-        ws += [W, b]
-        off += o * i + o
-    for l in range(len(m._shapes)):
-        h = h @ ws[2 * l].T + ws[2 * l + 1]
-        if l < len(m._shapes) - 1:
-            h = torch.relu(h)
-    return h, ws
-
-
-def torch_loss(yhat, y, w, kind, thr, beta):
-    we = w.clone()
-    if thr != 0:
-        we = torch.where(yhat.detach() <= thr, torch.ones_like(we), we)
-    d = yhat - y
-    if kind == "datal2":
-        li = d * d
-    else:
-        ad = d.abs()
-        li = torch.where(ad < beta, 0.5 * d * d / beta, ad - 0.5 * beta)
-    return (li * we).mean()
-
-
-def rand_coords(n, cin, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.rand(n, cin, generator=g) * 2 - 1
-
-
-def band_check(got, r64, r32, what):
-    got, r64, r32 = (np.asarray(v, dtype=np.float64) for v in (got, r64, r32))
-    e_fused = np.max(np.abs(got - r64))
-    e_torch = np.max(np.abs(r32 - r64))
-    bound = BAND_FACTOR * e_torch + FLOOR * max(np.max(np.abs(r64)), 1e-30)
-    assert e_fused <= bound, "%s: fused %.3e vs float64, torch fp32 %.3e, bound %.3e" % (what, e_fused, e_torch, bound)
 
 
 FWD_CASES = [

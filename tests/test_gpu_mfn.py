@@ -10,61 +10,10 @@ import torch
 
 from brief_pytorch_amd.fit import Fitter
 from brief_pytorch_amd.networks import MFNFourier, MFNGabor
+from tests._family_ref import BAND_FACTOR, FLOOR, band_check, rand_coords, torch_loss, torch_mfn
 
 pytestmark = pytest.mark.gpu
-BAND_FACTOR = 4.0     # fused fp32 vs float64  <=  4 x (torch fp32 vs float64) + floor
-FLOOR = 1e-5          # relative to max |reference|
 KINDS = {"fourier": MFNFourier, "gabor": MFNGabor}
-
-
-def torch_mfn(m, coords, dtype):
-    """the reference's forward at `dtype`; returns (output, {state_dict key: leaf tensor})"""
-    p = m.params.detach().cpu().to(dtype)
-    t = {}
-    for k, o, shp in m._entries:
-        t[k] = p[o:o + int(np.prod(shp))].view(shp).clone().requires_grad_(True)
-    x = coords.detach().cpu().to(dtype)
-
-    def filt(i):
-        g = torch.sin(x @ t["filters.%d.linear.weight" % i].T + t["filters.%d.linear.bias" % i])
-        if m.GABOR:
-            mu, gam = t["filters.%d.mu" % i], t["filters.%d.gamma" % i]
-            D = (x ** 2).sum(-1)[..., None] + (mu ** 2).sum(-1)[None, :] - 2 * x @ mu.T
-            g = g * torch.exp(-0.5 * D * gam[None, :])
-        return g
-    z = filt(0)
-    for i in range(1, m.layers - 1):
-        z = filt(i) * (z @ t["linear.%d.weight" % (i - 1)].T + t["linear.%d.bias" % (i - 1)])
-    out = z @ t["output_linear.weight"].T + t["output_linear.bias"]
-    if m.output_act:
-        out = torch.sin(out)
-    return out, t
-
-
-def torch_loss(yhat, y, w, kind, thr, beta):
-    we = w.clone()
-    if thr != 0:
-        we = torch.where(yhat.detach() <= thr, torch.ones_like(we), we)
-    d = yhat - y
-    if kind == "datal2":
-        li = d * d
-    else:
-        ad = d.abs()
-        li = torch.where(ad < beta, 0.5 * d * d / beta, ad - 0.5 * beta)
-    return (li * we).mean()
-
-
-def rand_coords(n, cin, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.rand(n, cin, generator=g) * 2 - 1
-
-
-def band_check(got, r64, r32, what):
-    got, r64, r32 = (np.asarray(v, dtype=np.float64) for v in (got, r64, r32))
-    e_fused = np.max(np.abs(got - r64))
-    e_torch = np.max(np.abs(r32 - r64))
-    bound = BAND_FACTOR * e_torch + FLOOR * max(np.max(np.abs(r64)), 1e-30)
-    assert e_fused <= bound, "%s: fused %.3e vs float64, torch fp32 %.3e, bound %.3e" % (what, e_fused, e_torch, bound)
 
 
 def golden_band(got, gold, e32, scale, what):

@@ -13,69 +13,10 @@ import torch
 
 from brief_pytorch_amd.fit import Fitter
 from brief_pytorch_amd.networks import NeRF
+from tests._family_ref import BAND_FACTOR, FLOOR, band_check, encoding, phases, rand_coords, torch_loss, torch_nerf      # noqa: F401 (encoding: test_gpu_nerf_framework.py)
 
 pytestmark = pytest.mark.gpu
-BAND_FACTOR = 4.0     # fused fp32 vs float64  <=  4 x (torch fp32 vs float64) + floor
-FLOOR = 1e-5          # relative to max |reference|: the reduction-order spread of fp32 sums over K <= 1024 + d terms
 ENC_BAND = 1e-6       # encoding vs the reference's fp32 PosEncodingNeRF, absolute (sin / cos within a few ulp of |v| <= 1)
-
-
-def phases(x, frequencies):
-    """[n, cin] float32 -> [n, frequencies, cin] float64: the exact fp32 phases 2^i fl32(fl32(pi) x) the reference's torch.sin sees"""
-    p = (x.to(torch.float32) * torch.tensor(math.pi, dtype=torch.float32)).double()
-    return torch.stack([p * (2.0 ** i) for i in range(frequencies)], 1) if frequencies else p.new_zeros(p.shape[0], 0, p.shape[1])
-
-
-def encoding(x, frequencies, dtype):
-    """PosEncodingNeRF column order: x, then per frequency i and channel c: sin, cos"""
-    n, cin = x.shape
-    ph = phases(x, frequencies).to(dtype)
-    sc = torch.stack([torch.sin(ph), torch.cos(ph)], -1).reshape(n, frequencies * cin * 2)
-    return torch.cat([x.to(dtype), sc], 1)
-
-
-def torch_nerf(m, coords, dtype):
-    """the reference's forward at `dtype` (the skip layer on cat[encoding, h]); returns (output, [W0, b0, ...] leaf tensors)"""
-    p = m.params.detach().cpu().to(dtype)
-    enc = encoding(coords.detach().cpu(), m.frequencies, dtype)
-    ws, off = [], 0
-    for (o, i) in m._shapes:
-        ws += [p[off:off + o * i].view(o, i).clone().requires_grad_(True), p[off + o * i:off + o * i + o].clone().requires_grad_(True)]
-        off += o * i + o
-    h = enc
-    for l in range(m.layers):
-        if l == m.skip_layer:
-            h = torch.cat([enc, h], 1)
-        h = h @ ws[2 * l].T + ws[2 * l + 1]
-        if l < m.layers - 1:
-            h = torch.relu(h)
-    return h, ws
-
-
-def torch_loss(yhat, y, w, kind, thr, beta):
-    we = w.clone()
-    if thr != 0:
-        we = torch.where(yhat.detach() <= thr, torch.ones_like(we), we)
-    d = yhat - y
-    if kind == "datal2":
-        li = d * d
-    else:
-        ad = d.abs()
-        li = torch.where(ad < beta, 0.5 * d * d / beta, ad - 0.5 * beta)
-    return (li * we).mean()
-
-
-def rand_coords(n, cin, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.rand(n, cin, generator=g) * 2 - 1
-
-
-def band_check(got, r64, r32, what):
-    got, r64, r32 = (np.asarray(v, dtype=np.float64) for v in (got, r64, r32))
-    e_fused = np.max(np.abs(got - r64))
-    e_torch = np.max(np.abs(r32 - r64))
-    bound = BAND_FACTOR * e_torch + FLOOR * max(np.max(np.abs(r64)), 1e-30)
-    assert e_fused <= bound, "%s: fused %.3e vs float64, torch fp32 %.3e, bound %.3e" % (what, e_fused, e_torch, bound)
 
 
 def golden_band(got, gold, e32, scale, what):

@@ -16,6 +16,7 @@ import torch
 from brief_pytorch_amd import _lib
 from brief_pytorch_amd.fit import Fitter
 from brief_pytorch_amd.networks import SIREN, SIREN_Pyramid, SIRENFT, SIRENPS
+from tests._family_ref import relerr, torch_loss, torch_taper
 
 pytestmark = pytest.mark.gpu
 KINDS = {"pyramid": SIREN_Pyramid, "ft": SIRENFT, "ps": SIRENPS}
@@ -24,36 +25,6 @@ CASES = [(k, i) for k in sorted(KINDS) for i in range(NCASE[k])]
 LOSSES = [("datal2", False, 0.0), ("datasmoothl1", True, 0.0), ("datal2", True, 0.3)]
 FWD_TOL, LOSS_TOL, GRAD_TOL = 2e-5, 1e-4, 1e-4
 MAX_WIDENED_FRACTION, MAX_BAND = 0.15, 1e-3      # tests/_bands.py
-
-
-def relerr(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-30))
-
-
-def torch_taper(m, coords, dtype):
-    """the reference's forward at `dtype` on the module's parameters; returns (output, [leaf tensors in state_dict order])"""
-    leaves = [v.detach().cpu().to(dtype).clone().requires_grad_(True) for v in m.state_dict().values()]
-    h = coords.detach().cpu().to(dtype)
-    L = m.layers
-    for l in range(L):
-        h = h @ leaves[2 * l].T + leaves[2 * l + 1]
-        if l < L - 1 or m.output_act:
-            h = torch.sin(m.w0s[l] * h)
-    return h, leaves
-
-
-def torch_loss(yhat, y, w, kind, thr, beta):
-    we = w.clone()
-    if thr != 0:
-        we = torch.where(yhat.detach() <= thr, torch.ones_like(we), we)
-    d = yhat - y
-    if kind == "datal2":
-        li = d * d
-    else:
-        ad = d.abs()
-        li = torch.where(ad < beta, 0.5 * d * d / beta, ad - 0.5 * beta)
-    return (li * we).mean()
 
 
 def build(golden, kind, i, device="cuda"):
