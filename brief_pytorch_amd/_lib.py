@@ -93,6 +93,12 @@ class ViewDesc(C.Structure):        # brief_view_desc
                 ("box_lo", C.c_float * 3), ("box_hi", C.c_float * 3)]
 
 
+class RaysDesc(C.Structure):        # brief_rays_desc
+    _fields_ = [("dims", C.c_int64 * 3), ("lo", C.c_float), ("hi", C.c_float),
+                ("rows", C.c_int32), ("cols", C.c_int32), ("depth", C.c_int32), ("reserved", C.c_int32),
+                ("box_lo", C.c_float * 3), ("box_hi", C.c_float * 3)]
+
+
 class ViewPart(C.Structure):        # brief_view_part
     _fields_ = [("start", C.c_int64 * 3), ("dims", C.c_int64 * 3), ("row0", C.c_int32), ("col0", C.c_int32), ("wrows", C.c_int32), ("wcols", C.c_int32)]
 
@@ -149,7 +155,9 @@ EXPORTS = ["brief_version", "brief_last_error", "brief_param_count", "brief_pack
            "brief_surface_part_fold", "brief_surface_part_route", "brief_surface_part_coords", "brief_surface_part_step", "brief_surface_part_shade",
            "brief_surface_part_route_host", "brief_view_part_sample_t_host",
            "brief_view_composite_select", "brief_view_composite_pick", "brief_view_composite_shade_fold", "brief_view_composite_shade_host",
-           "brief_composite_shade_q_host"] \
+           "brief_composite_shade_q_host",
+           "brief_rays_clip", "brief_rays_coords", "brief_rays_fold", "brief_rays_surface_fold", "brief_rays_surface_coords",
+           "brief_rays_surface_shade", "brief_rays_sample_host", "brief_rays_sample_t_host", "brief_rays_clip_host"] \
     + ["brief_%s_%s" % (prefix, entry) for prefix, _, _ in FAMILIES for entry in FAMILY_ENTRIES]
 
 
@@ -306,6 +314,16 @@ def lib():
     L.brief_view_composite_shade_fold.argtypes = [wp, vp, vp, i64, i64, i64, i64, i32, vp, C.c_int, i32, i32, vp, i32, vp, vp, vp, hp, vp, vp, vp, vp]
     L.brief_view_composite_shade_host.argtypes = [wp, vp, vp, vp, C.c_int, i32, i32, vp, i32, C.POINTER(i32), vp, hp, vp, vp, vp, vp, vp]
     L.brief_composite_shade_q_host.argtypes = [vp, i64, hp, vp]
+    rp = C.POINTER(RaysDesc)
+    L.brief_rays_clip.argtypes = [rp, vp, vp, vp, vp]
+    L.brief_rays_coords.argtypes = [rp, vp, vp, vp, i64, i64, i64, i64, i32, vp, vp]
+    L.brief_rays_fold.argtypes = [rp, vp, vp, i64, i64, i64, i64, i32, vp, C.c_int, i32, i32, vp, vp, vp]
+    L.brief_rays_surface_fold.argtypes = [rp, vp, vp, i64, i64, i64, i64, i32, vp, C.c_int, i32, i32, i32, i32, vp, vp, vp]
+    L.brief_rays_surface_coords.argtypes = [rp, vp, vp, vp, i32, vp, vp, vp]
+    L.brief_rays_surface_shade.argtypes = [rp, vp, vp, i32, i32, i32, C.POINTER(C.c_float), vp, vp, vp, vp]
+    L.brief_rays_sample_host.argtypes = [rp, vp, vp, vp, vp, i64, vp, vp, vp]
+    L.brief_rays_sample_t_host.argtypes = [rp, vp, vp, vp, vp, i64, vp, vp, vp]
+    L.brief_rays_clip_host.argtypes = [rp, vp, vp, vp]
     _LIB = L
     return L
 

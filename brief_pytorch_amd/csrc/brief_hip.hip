@@ -1780,3 +1780,4 @@ int brief_quant_decode(const uint16_t *codes, const brief_quant_span *tensors, i
 #include "brief_hess.inc"             // Hessian decode: k_hess_fwd and brief_siren_hess_forward / _forward_box, behind the view kernels (the kernels above keep their order)
 #include "brief_composite.inc"        // composite view: k_composite_fold / k_composite_finish and brief_view_composite_*, behind everything else (the kernels above keep their order)
 #include "brief_surface_part.inc"     // surface view of a partition: k_surface_part_fold / _route / _coords / _step / _shade and brief_surface_part_*, behind everything else (the kernels above keep their order)
+#include "brief_rays.inc"             // ray view (a perspective camera): k_rays_clip / _coords / _fold / _surface_fold / _surface_coords / _surface_shade and brief_rays_*, behind everything else (the kernels above keep their order)

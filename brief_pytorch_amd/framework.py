@@ -303,6 +303,21 @@ class NFGR:
         return view.decompress_divide_surface(opt if opt is not None else _wrap(self.opt), orig_sideinfos_path, module_save_dir, sideinfos_save_dir,
                                               direction, level, **{"device": self.device, **kwargs})
 
+    # ---- camera view: projections and surfaces through a perspective camera (brief_pytorch_amd/view.py make_camera, render_rays)
+    @staticmethod
+    def decompress_camera(opt, module_path, sideinfos, eye, direction, **kwargs):
+        """a perspective view of a stored SingleTask artefact as a numpy image [rows, cols, channels]: mode 'max' | 'min' | 'mean' folds
+        every ray of a camera at the voxel-index position `eye` looking along `direction`; the eye may lie inside the volume.  The
+        volume is never decoded.  view.decompress_camera has the arguments and the envelope."""
+        return decompress_camera(opt, module_path, sideinfos, eye, direction, **kwargs)
+
+    @staticmethod
+    def decompress_camera_surface(opt, module_path, sideinfos, eye, direction, level, **kwargs):
+        """the isosurface view of a stored SingleTask artefact through the same camera, as a dict of numpy arrays (first, t, distance,
+        position, normal, shade, ...); the default light is a point light at the eye.  view.decompress_camera_surface has the
+        arguments and the envelope."""
+        return decompress_camera_surface(opt, module_path, sideinfos, eye, direction, level, **kwargs)
+
     @staticmethod
     def decompress_composite(opt, module_path, sideinfos, direction, transfer, **kwargs):
         """the composite view of a stored SingleTask artefact as a numpy image uint8 [rows, cols, 4] = R, G, B, A: direct volume rendering
@@ -1075,6 +1090,20 @@ def decompress_divide_surface(opt, orig_sideinfos, module_dir, sideinfos_dir, di
     the block that owns it (view.decompress_divide_surface); opt: the whole option tree"""
     from . import view
     return view.decompress_divide_surface(opt, orig_sideinfos, module_dir, sideinfos_dir, direction, level, **kwargs)
+
+
+def decompress_camera(opt, module_path, sideinfos, eye, direction, **kwargs):
+    """a perspective view (max | min | mean) of a stored SingleTask artefact through a camera at `eye` looking along `direction`
+    (view.decompress_camera); a DivideTask artefact is refused by name"""
+    from . import view
+    return view.decompress_camera(view.open_single_camera(opt, module_path, sideinfos), eye, direction, **kwargs)
+
+
+def decompress_camera_surface(opt, module_path, sideinfos, eye, direction, level, **kwargs):
+    """the isosurface view of a stored SingleTask artefact through a camera at `eye` looking along `direction`
+    (view.decompress_camera_surface); a DivideTask artefact is refused by name"""
+    from . import view
+    return view.decompress_camera_surface(view.open_single_camera(opt, module_path, sideinfos), eye, direction, level, **kwargs)
 
 
 def decompress_divide_composite(opt, orig_sideinfos, module_dir, sideinfos_dir, direction, transfer, **kwargs):

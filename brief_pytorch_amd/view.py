@@ -12,7 +12,11 @@ block: the nearest block owns a sample (DESIGN.md "View decode of a partition").
 of a partition (composite.render_composite_partition) and its surface view (render_surface_partition, decompress_divide_surface: every
 refinement point and the hit are routed to the block that owns them; DESIGN.md "Surface view of a partition").
 
-make_view, part_window and make_part are host arithmetic; brief_view_sample_host / brief_view_sample_t_host / brief_view_clip_host,
+A ray view (make_camera, rays_from_view, render_rays, render_surface_rays, decompress_camera, decompress_camera_surface) takes its
+rays from a table instead of a lattice, six floats per ray: a perspective camera at a point, inside the volume or outside it, through
+the same march and folds (csrc/brief_rays.h, csrc/brief_rays.inc, DESIGN.md "Camera view").
+
+make_view, make_camera, part_window and make_part are host arithmetic; brief_rays_sample_host / _sample_t_host / _clip_host and brief_view_sample_host / brief_view_sample_t_host / brief_view_clip_host,
 brief_view_part_clip_host / brief_view_part_sample_host / brief_view_part_sample_t_host and brief_surface_part_route_host restate the
 device's geometry on the CPU; everything else needs a ROCm GPU
 (there is no CPU fallback)."""
@@ -197,17 +201,91 @@ def _lanes(mean_count):
     return g
 
 
+class _Lattice:
+    """the geometry of an orthographic view as the shared march and renderers call it: the descriptor (lo / hi set) and the entries
+    that read it.  _Bundle is the same for a ray view; everything else of a render is shared."""
+    slice_ok = True
+
+    def __init__(self, v):
+        self.desc = self.flat = v               # flat: the brief_view_desc that finish, bracket and step read rows x cols of
+        self.rows, self.cols, self.depth = v.rows, v.cols, v.depth
+
+    def clip(self, k0, cnt):
+        _lib.check(_lib.lib().brief_view_clip(C.byref(self.desc), _lib.ptr(k0), _lib.ptr(cnt), _lib.stream_ptr()))
+
+    def coords(self, k0, off, s0, s1, r0, r1, lanes, coords):
+        _lib.check(_lib.lib().brief_view_coords(C.byref(self.desc), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(coords), _lib.stream_ptr()))
+
+    def fold(self, k0, off, s0, s1, r0, r1, lanes, vals, kind, ch, m, hits, acc):
+        _lib.check(_lib.lib().brief_view_fold(C.byref(self.desc), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(vals), kind, ch, m,
+                                              _lib.ptr(hits), _lib.ptr(acc), _lib.stream_ptr()))
+
+    def surface_fold(self, k0, off, s0, s1, r0, r1, lanes, vals, kind, ch, channel, level, sd, hits, first):
+        _lib.check(_lib.lib().brief_surface_fold(C.byref(self.desc), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(vals), kind, ch, channel,
+                                                 level, sd, _lib.ptr(hits), _lib.ptr(first), _lib.stream_ptr()))
+
+    def surface_coords(self, t_lo, t_hi, mid, coords, pos):
+        _lib.check(_lib.lib().brief_surface_coords(C.byref(self.desc), _lib.ptr(t_lo), _lib.ptr(t_hi), mid, _lib.ptr(coords), _lib.ptr(pos),
+                                                   _lib.stream_ptr()))
+
+    def surface_shade(self, t, jac, ch, channel, sd, g, light, normal, shade):
+        f3 = C.c_float * 3
+        l = _unit3(light if light is not None else list(self.desc.ddepth), "light")
+        _lib.check(_lib.lib().brief_surface_shade(C.byref(self.desc), _lib.ptr(t), _lib.ptr(jac), ch, channel, sd, f3(*g), f3(*l), _lib.ptr(normal),
+                                                  _lib.ptr(shade), _lib.stream_ptr()))
+
+
+class _Bundle(_Lattice):
+    """the geometry of a ray view (a RayView with lo / hi set, its table and headlight on the device): brief_rays_*"""
+    slice_ok = False
+
+    def __init__(self, desc, table, light):
+        self.desc, self.flat = desc, _flat_view(desc)
+        self.rows, self.cols, self.depth = desc.rows, desc.cols, desc.depth
+        self.table, self.light = table, light
+
+    def clip(self, k0, cnt):
+        _lib.check(_lib.lib().brief_rays_clip(C.byref(self.desc), _lib.ptr(self.table), _lib.ptr(k0), _lib.ptr(cnt), _lib.stream_ptr()))
+
+    def coords(self, k0, off, s0, s1, r0, r1, lanes, coords):
+        _lib.check(_lib.lib().brief_rays_coords(C.byref(self.desc), _lib.ptr(self.table), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes,
+                                                _lib.ptr(coords), _lib.stream_ptr()))
+
+    def fold(self, k0, off, s0, s1, r0, r1, lanes, vals, kind, ch, m, hits, acc):
+        _lib.check(_lib.lib().brief_rays_fold(C.byref(self.desc), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(vals), kind, ch, m,
+                                              _lib.ptr(hits), _lib.ptr(acc), _lib.stream_ptr()))
+
+    def surface_fold(self, k0, off, s0, s1, r0, r1, lanes, vals, kind, ch, channel, level, sd, hits, first):
+        _lib.check(_lib.lib().brief_rays_surface_fold(C.byref(self.desc), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(vals), kind, ch,
+                                                      channel, level, sd, _lib.ptr(hits), _lib.ptr(first), _lib.stream_ptr()))
+
+    def surface_coords(self, t_lo, t_hi, mid, coords, pos):
+        _lib.check(_lib.lib().brief_rays_surface_coords(C.byref(self.desc), _lib.ptr(self.table), _lib.ptr(t_lo), _lib.ptr(t_hi), mid, _lib.ptr(coords),
+                                                        _lib.ptr(pos), _lib.stream_ptr()))
+
+    def surface_shade(self, t, jac, ch, channel, sd, g, light, normal, shade):
+        import torch
+        table = self.light                       # the per-ray headlight; a given light is one direction for every ray
+        if light is not None:
+            l = torch.from_numpy(_unit3(light, "light").astype(np.float32)).to(self.table.device)
+            table = l.expand(self.rows * self.cols, 3).contiguous()
+        f3 = C.c_float * 3
+        _lib.check(_lib.lib().brief_rays_surface_shade(C.byref(self.desc), _lib.ptr(t), _lib.ptr(jac), ch, channel, sd, f3(*g), _lib.ptr(table),
+                                                       _lib.ptr(normal), _lib.ptr(shade), _lib.stream_ptr()))
+
+
 def _march(phi, v, kind, dt, scale, vrange, chunk, fold, with_coords=False):
-    """the part every view shares: clip the rays of `v` (lo / hi set), scan, and evaluate the compacted sample list chunk by chunk with
+    """the part every view shares: clip the rays of `v` (a descriptor with lo / hi set, or a _Lattice / _Bundle: the two geometries
+    differ in the clip and the coords calls only), scan, and evaluate the compacted sample list chunk by chunk with
     the net's own forward entry, handing each chunk to fold(k0, off, s0, s1, r0, r1, lanes, vals); with_coords: the chunk's
     coordinates [n, 3] too, as the keyword `coords` (the shaded composite picks the samples it lights from them).
     Returns (k0, total, rays_hit)."""
     import torch
-    L, st = _lib.lib(), _lib.stream_ptr
+    geo = v if isinstance(v, _Lattice) else _Lattice(v)
     dev, ch = phi.params.device, int(phi.data_channel)
-    rays = v.rows * v.cols
+    rays = geo.rows * geo.cols
     k0, cnt = torch.empty(rays, dtype=torch.int32, device=dev), torch.empty(rays, dtype=torch.int32, device=dev)
-    _lib.check(L.brief_view_clip(C.byref(v), _lib.ptr(k0), _lib.ptr(cnt), st()))
+    geo.clip(k0, cnt)
     off = torch.zeros(rays + 1, dtype=torch.int64, device=dev)
     torch.cumsum(cnt, 0, dtype=torch.int64, out=off[1:])
     total, rays_hit = int(off[-1].item()), int((cnt > 0).sum().item())
@@ -222,7 +300,7 @@ def _march(phi, v, kind, dt, scale, vrange, chunk, fold, with_coords=False):
         vals = torch.empty((min(chunk, total), ch), dtype=dt, device=dev)
         for s0, s1, r0, r1 in zip(cuts[:-1], cuts[1:], r0s, r1s):
             n = s1 - s0
-            _lib.check(L.brief_view_coords(C.byref(v), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(coords), st()))
+            geo.coords(k0, off, s0, s1, r0, r1, lanes, coords)
             b = _lib.BatchDesc(coords.data_ptr(), None, None, None, 0, n, 0, 0, 0)
             _lib.check(phi._abi_forward(None, b, vals, kind, scale, vrange, n))
             if with_coords:
@@ -240,14 +318,19 @@ def render(phi, view, mode, lo, hi, out_kind, scale, vrange, chunk=None):
     Pixels whose ray has no inside sample (hits == 0) are 0.  Samples are evaluated in chunks of at most `chunk` (default
     mip.DEFAULT_CHUNK): the memory is one chunk of coordinates and values plus the accumulators, whatever the volume's size.
     stats = {rays, rays_hit, samples_inside, samples_evaluated}."""
-    import torch
-    from . import mip
     if mode not in MODES:
         raise ValueError("view mode %r is not one of %s" % (mode, " | ".join(MODES)))
     if out_kind not in ("u8", "u16"):
         raise ValueError("render folds the integer decode only: out_kind must be 'u8' or 'u16' (got %r)" % (out_kind,))
     if mode == "slice" and view.depth != 1:
         raise ValueError("mode 'slice' needs a view of one plane (depth 1); this one has %d samples per ray" % view.depth)
+    return _render(phi, lambda: _Lattice(_with_range(view, lo, hi)), mode, out_kind, scale, vrange, chunk)
+
+
+def _render(phi, geometry, mode, out_kind, scale, vrange, chunk):
+    """render and render_rays behind their own checks: geometry() makes the _Lattice / _Bundle once the net is known to be on a GPU"""
+    import torch
+    from . import mip
     if int(phi.coords_channel) != 3:
         raise ValueError("a view is defined for 3-D data only (the net takes %d coordinates)" % phi.coords_channel)
     phi._require_gpu()
@@ -255,9 +338,9 @@ def render(phi, view, mode, lo, hi, out_kind, scale, vrange, chunk=None):
     if chunk < 1:
         raise ValueError("chunk must be >= 1")
     L, st = _lib.lib(), _lib.stream_ptr
-    v = _with_range(view, lo, hi)
+    geo = geometry()
     dev, ch = phi.params.device, int(phi.data_channel)
-    rays = v.rows * v.cols
+    rays = geo.rows * geo.cols
     kind, dt = (_lib.OUT_U8, torch.uint8) if out_kind == "u8" else (_lib.OUT_U16, torch.uint16)
     m = _lib.VIEW_MODE[mode]
     hits = torch.zeros(rays, dtype=torch.int32, device=dev)
@@ -267,13 +350,12 @@ def render(phi, view, mode, lo, hi, out_kind, scale, vrange, chunk=None):
         acc = torch.full((rays, ch), 0x7FFFFFFF if mode == "min" else 0, dtype=torch.int32, device=dev)
 
     def fold(k0, off, s0, s1, r0, r1, lanes, vals):
-        _lib.check(L.brief_view_fold(C.byref(v), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(vals), kind, ch, m,
-                                     _lib.ptr(hits), _lib.ptr(acc), st()))
-    _, total, rays_hit = _march(phi, v, kind, dt, scale, vrange, chunk, fold)
-    image = torch.empty((v.rows, v.cols, ch), dtype=torch.float32 if mode == "mean" else dt, device=dev)
-    _lib.check(L.brief_view_finish(C.byref(v), kind, ch, m, _lib.ptr(hits), _lib.ptr(acc), _lib.ptr(image), st()))
+        geo.fold(k0, off, s0, s1, r0, r1, lanes, vals, kind, ch, m, hits, acc)
+    _, total, rays_hit = _march(phi, geo, kind, dt, scale, vrange, chunk, fold)
+    image = torch.empty((geo.rows, geo.cols, ch), dtype=torch.float32 if mode == "mean" else dt, device=dev)
+    _lib.check(L.brief_view_finish(C.byref(geo.flat), kind, ch, m, _lib.ptr(hits), _lib.ptr(acc), _lib.ptr(image), st()))
     stats = {"rays": rays, "rays_hit": rays_hit, "samples_inside": int(hits.sum(dtype=torch.int64).item()), "samples_evaluated": total}
-    return image, hits.view(v.rows, v.cols), stats
+    return image, hits.view(geo.rows, geo.cols), stats
 
 
 # ---- a view of a partition: the nearest block owns a sample (csrc/brief_view.h "a view of a PARTITION") -------------------------------
@@ -557,10 +639,16 @@ def render_surface(phi, view, level, lo, hi, out_kind, scale, vrange, channel=0,
         stats     render's keys, rays_surface (rays with a hit), rays_cut, refine_points (points the refinement evaluated)
     The march evaluates exactly what render evaluates, in chunks of `chunk`; a refinement round is one dense pass over rows * cols
     points (1 / depth of the march).  Every decision compares decoded integers: first, t_lo, t_hi do not depend on chunking or run."""
+    return _render_surface(phi, lambda: _Lattice(_with_range(view, lo, hi)), "render_surface", list(view.dims), level, lo, hi, out_kind, scale, vrange,
+                           channel, side, refine, shading, light, gscale, chunk)
+
+
+def _render_surface(phi, geometry, who, dims, level, lo, hi, out_kind, scale, vrange, channel, side, refine, shading, light, gscale, chunk):
+    """render_surface and render_surface_rays: geometry() makes the _Lattice / _Bundle once every refusal has passed"""
     import torch
     from . import gradient, mip
     if out_kind not in ("u8", "u16"):
-        raise ValueError("render_surface tests the integer decode only: out_kind must be 'u8' or 'u16' (got %r)" % (out_kind,))
+        raise ValueError("%s tests the integer decode only: out_kind must be 'u8' or 'u16' (got %r)" % (who, out_kind))
     if int(phi.coords_channel) != 3:
         raise ValueError("a view is defined for 3-D data only (the net takes %d coordinates)" % phi.coords_channel)
     ch = int(phi.data_channel)
@@ -574,17 +662,17 @@ def render_surface(phi, view, level, lo, hi, out_kind, scale, vrange, channel=0,
     if chunk < 1:
         raise ValueError("chunk must be >= 1")
     L, st = _lib.lib(), _lib.stream_ptr
-    v = _with_range(view, lo, hi)
-    dev, rays = phi.params.device, view.rows * view.cols
+    geo = geometry()
+    v = geo.flat
+    dev, rays = phi.params.device, geo.rows * geo.cols
     kind, dt = (_lib.OUT_U8, torch.uint8) if out_kind == "u8" else (_lib.OUT_U16, torch.uint16)
     sd = _lib.SURFACE_SIDE[side]
     hits = torch.zeros(rays, dtype=torch.int32, device=dev)
     first = torch.full((rays,), NO_HIT, dtype=torch.int32, device=dev)
 
     def fold(k0, off, s0, s1, r0, r1, lanes, vals):
-        _lib.check(L.brief_surface_fold(C.byref(v), _lib.ptr(k0), _lib.ptr(off), s0, s1, r0, r1, lanes, _lib.ptr(vals), kind, ch, channel, level,
-                                        sd, _lib.ptr(hits), _lib.ptr(first), st()))
-    k0, total, rays_hit = _march(phi, v, kind, dt, scale, vrange, chunk, fold)
+        geo.surface_fold(k0, off, s0, s1, r0, r1, lanes, vals, kind, ch, channel, level, sd, hits, first)
+    k0, total, rays_hit = _march(phi, geo, kind, dt, scale, vrange, chunk, fold)
     t_lo, t_hi = torch.empty(rays, dtype=torch.float32, device=dev), torch.empty(rays, dtype=torch.float32, device=dev)
     _lib.check(L.brief_surface_bracket(C.byref(v), _lib.ptr(k0), _lib.ptr(first), _lib.ptr(t_lo), _lib.ptr(t_hi), st()))
     hit = first != NO_HIT
@@ -595,27 +683,24 @@ def render_surface(phi, view, level, lo, hi, out_kind, scale, vrange, channel=0,
     if refine and rays_surface > rays_cut:
         vals = torch.empty((rays, ch), dtype=dt, device=dev)
         for _ in range(refine):
-            _lib.check(L.brief_surface_coords(C.byref(v), _lib.ptr(t_lo), _lib.ptr(t_hi), 1, _lib.ptr(coords), None, st()))
+            geo.surface_coords(t_lo, t_hi, 1, coords, None)
             for o in range(0, rays, mip.DEFAULT_CHUNK):            # (dense: rows * cols points, whatever `chunk` bounds the march to)
                 n = min(mip.DEFAULT_CHUNK, rays - o)
                 b = _lib.BatchDesc(coords[o:o + n].data_ptr(), None, None, None, 0, n, 0, 0, 0)
                 _lib.check(phi._abi_forward(None, b, vals[o:o + n], kind, scale, vrange, n))
             _lib.check(L.brief_surface_step(C.byref(v), _lib.ptr(vals), kind, ch, channel, level, sd, _lib.ptr(t_lo), _lib.ptr(t_hi), st()))
         refine_points = refine * rays
-    _lib.check(L.brief_surface_coords(C.byref(v), _lib.ptr(t_lo), _lib.ptr(t_hi), 0, _lib.ptr(coords), _lib.ptr(pos), st()))
+    geo.surface_coords(t_lo, t_hi, 0, coords, pos)
     normal = shade = None
     if shading:
-        g = np.asarray(gscale if gscale is not None else gradient.voxel_scale(list(view.dims), lo, hi, scale, vrange[0], vrange[1]), np.float64)
+        g = np.asarray(gscale if gscale is not None else gradient.voxel_scale(dims, lo, hi, scale, vrange[0], vrange[1]), np.float64)
         if g.shape != (3,) or not np.isfinite(g).all():
             raise ValueError("gscale must be three finite numbers in (z, y, x) order (got %r)" % (gscale,))
-        l = _unit3(light if light is not None else list(view.ddepth), "light")
         _, jac = phi.spatial_gradient(coords, want_value=False)
-        normal = torch.empty((view.rows, view.cols, 3), dtype=torch.float32, device=dev)
-        shade = torch.empty((view.rows, view.cols), dtype=torch.float32, device=dev)
-        f3 = C.c_float * 3
-        _lib.check(L.brief_surface_shade(C.byref(v), _lib.ptr(t_hi), _lib.ptr(jac), ch, channel, sd, f3(*g), f3(*l), _lib.ptr(normal),
-                                         _lib.ptr(shade), st()))
-    shape = (view.rows, view.cols)
+        normal = torch.empty((geo.rows, geo.cols, 3), dtype=torch.float32, device=dev)
+        shade = torch.empty((geo.rows, geo.cols), dtype=torch.float32, device=dev)
+        geo.surface_shade(t_hi, jac, ch, channel, sd, g, light, normal, shade)
+    shape = (geo.rows, geo.cols)
     stats = {"rays": rays, "rays_hit": rays_hit, "samples_inside": int(hits.sum(dtype=torch.int64).item()), "samples_evaluated": total,
              "rays_surface": rays_surface, "rays_cut": rays_cut, "refine_points": refine_points}
     return {"first": torch.where(hit, first, torch.full_like(first, -1)).view(shape), "t_lo": t_lo.view(shape), "t_hi": t_hi.view(shape),
@@ -814,6 +899,184 @@ def render_surface_partition(parts, view, level, out_kind, channel=0, side="abov
             "owner": owner.view(shape), "stats": stats}
 
 
+# ---- ray view: a perspective camera, or any table of rays (csrc/brief_rays.h, csrc/brief_rays.inc; DESIGN.md "Camera view") -----------
+CAMERA_MODES = ("max", "min", "mean")
+CAMERA_SCOPE = ("a camera renders the projections max | min | mean and the surface view: %s through a camera is out of scope (a follow-up; "
+                "every ray of a camera is sampled at one uniform spacing so that a composite needs no opacity correction later)")
+
+
+class RayView:
+    """a ray view: desc (_lib.RaysDesc: dims, lo / hi, rows, cols, depth, the clip box), rays float32 [rows, cols, 6] = (base z, y, x,
+    step z, y, x) per ray in voxel-index units, light float32 [rows, cols, 3] (the unit physical direction of every ray: a point light
+    at a camera's eye), and near / depth_spacing, the fp32 numbers that turn a depth t in samples into a physical distance along the
+    ray, distance = fl(near + fl(t * depth_spacing))"""
+
+    def __init__(self, desc, rays, light, near, depth_spacing):
+        self.desc, self.near, self.depth_spacing = desc, float(np.float32(near)), float(np.float32(depth_spacing))
+        self.rays = np.ascontiguousarray(rays, np.float32).reshape(desc.rows, desc.cols, 6)
+        self.light = np.ascontiguousarray(light, np.float32).reshape(desc.rows, desc.cols, 3)
+
+    rows, cols, depth = (property(lambda self, n=n: getattr(self.desc, n)) for n in ("rows", "cols", "depth"))
+
+
+def _rays_desc(dims, box_lo, box_hi, rows, cols, depth, lo=-1.0, hi=1.0):
+    d = _lib.RaysDesc()
+    for a in range(3):
+        d.dims[a], d.box_lo[a], d.box_hi[a] = int(dims[a]), box_lo[a], box_hi[a]
+    d.lo, d.hi = float(lo), float(hi)
+    d.rows, d.cols, d.depth = int(rows), int(cols), int(depth)
+    return d
+
+
+def _flat_view(desc):
+    """the brief_view_desc that carries a ray view's dims, lo / hi, box, rows, cols and depth, with zero steps: what brief_view_finish,
+    brief_surface_bracket and brief_surface_step read (brief_rays_view of csrc/brief_rays.h)"""
+    v = _lib.ViewDesc()
+    for a in range(3):
+        v.dims[a], v.box_lo[a], v.box_hi[a] = desc.dims[a], desc.box_lo[a], desc.box_hi[a]
+    v.lo, v.hi = desc.lo, desc.hi
+    v.rows, v.cols, v.depth = desc.rows, desc.cols, desc.depth
+    return v
+
+
+def make_camera(dims, eye, direction, up=None, fov=60.0, size=(256, 256), near=0.0, far=None, depth_spacing=1.0, voxel_size=(1, 1, 1), region=None):
+    """the RayView of a perspective camera at `eye` looking along `direction`, over the grid `dims` (3 spatial axes, (z, y, x)).
+    eye:           a voxel-index position, as make_view's centre; it may lie inside the volume (a fly-through).
+    direction, up: see frame(); PHYSICAL directions, voxel_size being a voxel's physical extent per axis.
+    fov:           the full opening angle over the rows, degrees, 0 < fov < 180; pixels are square.
+    size:          (rows, cols).  Pixel (i, j) looks along w = direction + u_i * row_dir + v_j * col_dir with u_i = (i - (rows - 1) / 2) * s,
+                   v_j = (j - (cols - 1) / 2) * s, s = 2 tan(fov / 2) / rows (the pixel pitch on the image plane at unit distance).
+    near, far, depth_spacing: physical distances from the eye.  Sample k of EVERY ray lies at near + k * depth_spacing along the ray's
+                   unit direction w / |w|: base = eye + near * unit / voxel_size, step = depth_spacing * unit / voxel_size.  far
+                   defaults to the largest distance from the eye to a corner of the clip box; depth = floor((far - near) /
+                   depth_spacing + 1e-9) + 1.
+    region:        the clip box (make_view's).
+    Everything is computed in float64 and rounded to fp32 once.  lo / hi of the descriptor are set by render_rays()."""
+    dims = [int(v) for v in dims]
+    if len(dims) != 3:
+        raise ValueError("a view is defined for 3-D data only (got a %d-D grid)" % len(dims))
+    if any(n < 2 for n in dims):
+        raise ValueError(ENVELOPE["min_axis"][1] % (dims,))
+    vs = _vec3(voxel_size, "voxel_size")
+    if (vs <= 0).any():
+        raise ValueError("voxel_size must be positive on every axis (got %r)" % (tuple(voxel_size),))
+    depth_spacing = _positive(depth_spacing, "depth_spacing")
+    e = _vec3(eye, "eye")
+    fov = float(fov)
+    if not 0.0 < fov < 180.0:
+        raise ValueError("fov must lie strictly between 0 and 180 degrees (got %r): it is the full opening angle over the rows" % (fov,))
+    near = float(near)
+    if not (math.isfinite(near) and near >= 0):
+        raise ValueError("near must be a finite distance >= 0 from the eye (got %r)" % (near,))
+    try:
+        rows, cols = (int(x) for x in size)
+    except (TypeError, ValueError):
+        raise ValueError("size must be (rows, cols) (got %r)" % (size,)) from None
+    if rows < 1 or cols < 1:
+        raise ValueError("size must be at least 1 x 1 (got %r)" % (size,))
+    if rows >= MAX_COUNT or cols >= MAX_COUNT:
+        raise ValueError("size %r is refused: sizes of 2^24 and above are not exact in a float" % (size,))
+    row_dir, col_dir, d = frame(direction, up)
+    start, stop, step = region_mod.normalize_region(dims, region if region is not None else (slice(None),) * 3, 1)
+    if any(s != 1 for s in step):
+        raise ValueError("the clip box of a view is a box, not a lattice: region steps other than 1 are refused (got %s)" % (step,))
+    box_lo, box_hi = np.array(start, np.float64), np.array(stop, np.float64) - 1.0
+    if far is None:
+        corners = np.array([[(box_lo, box_hi)[(i >> a) & 1][a] for a in range(3)] for i in range(8)])
+        far = max(float(np.linalg.norm((corners - e) * vs, axis=1).max()), near)
+    else:
+        far = float(far)
+        if not (math.isfinite(far) and far >= near):
+            raise ValueError("far must be a finite distance >= near = %r from the eye (got %r)" % (near, far))
+    depth = _count(far - near, depth_spacing, "depth")
+    s = 2.0 * math.tan(math.radians(fov) / 2.0) / rows
+    u = (np.arange(rows, dtype=np.float64) - (rows - 1) / 2.0) * s
+    w = (np.arange(cols, dtype=np.float64) - (cols - 1) / 2.0) * s
+    ray = d[None, None, :] + u[:, None, None] * row_dir[None, None, :] + w[None, :, None] * col_dir[None, None, :]
+    unit = ray / np.linalg.norm(ray, axis=2, keepdims=True)
+    table = np.concatenate([e + near * unit / vs, depth_spacing * unit / vs], axis=2)
+    return RayView(_rays_desc(dims, box_lo, box_hi, rows, cols, depth), table, unit, near, depth_spacing)
+
+
+def rays_from_view(view):
+    """the RayView of an orthographic view (a _lib.ViewDesc): base = the fp32 position of its sample (row, col, 0) as the device computes
+    it (sample_host), step = view.ddepth on every ray, light = ddepth normalised.  Through brief_rays_* it gives the orthographic
+    renderers' results bit for bit; it is also the pattern for a caller's own rays.  near = 0 and depth_spacing = 1: the distance of a
+    surface is its depth in samples."""
+    row, col = np.meshgrid(np.arange(view.rows), np.arange(view.cols), indexing="ij")
+    base = sample_host(view, row, col, np.zeros_like(row))[0]
+    dd = np.array(list(view.ddepth), np.float32)
+    table = np.concatenate([base, np.broadcast_to(dd, base.shape)], axis=1)
+    light = np.broadcast_to(_unit3(list(view.ddepth), "ddepth"), base.shape)
+    desc = _rays_desc(list(view.dims), list(view.box_lo), list(view.box_hi), view.rows, view.cols, view.depth, view.lo, view.hi)
+    return RayView(desc, table, light, 0.0, 1.0)
+
+
+def _rays_host(cam, row, col, third, dtype, entry):
+    row, col = (np.ascontiguousarray(x, np.int32).ravel() for x in (row, col))
+    third = np.ascontiguousarray(third, dtype).ravel()
+    n = len(row)
+    if len(col) != n or len(third) != n:
+        raise ValueError("row, col and the depth must have one entry per sample")
+    pos, coord, inside = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32), np.empty(n, np.uint8)
+    p = (lambda a: a.ctypes.data_as(C.c_void_p))
+    _lib.check(entry(C.byref(cam.desc), p(cam.rays), p(row), p(col), p(third), n, p(pos), p(coord), p(inside)))
+    return pos, coord, inside.astype(bool)
+
+
+def rays_sample_host(cam, row, col, k):
+    """sample_host for a RayView: (pos [n, 3], coord [n, 3] float32, inside [n] bool) of the samples (row, col, k) as the device computes
+    them, p_a = fl(base_a + fl(k * step_a)) (brief_rays_sample_host: the same header on the host CPU, no GPU call)"""
+    return _rays_host(cam, row, col, k, np.int32, _lib.lib().brief_rays_sample_host)
+
+
+def rays_sample_t_host(cam, row, col, t):
+    """rays_sample_host at real depths t (float32, 0 <= t <= depth - 1): the points the refinement of a surface evaluates
+    (brief_rays_sample_t_host); at an integer t it is rays_sample_host's sample k = t, bit for bit"""
+    return _rays_host(cam, row, col, t, np.float32, _lib.lib().brief_rays_sample_t_host)
+
+
+def rays_clip_host(cam):
+    """clip_host for a RayView: (k0 [rows, cols], cnt [rows, cols]) int32, the inside samples of every ray, on the host CPU"""
+    k0, cnt = np.empty((cam.rows, cam.cols), np.int32), np.empty((cam.rows, cam.cols), np.int32)
+    p = (lambda a: a.ctypes.data_as(C.c_void_p))
+    _lib.check(_lib.lib().brief_rays_clip_host(C.byref(cam.desc), p(cam.rays), p(k0), p(cnt)))
+    return k0, cnt
+
+
+def _bundle(cam, lo, hi, device):
+    import torch
+    desc = _lib.RaysDesc.from_buffer_copy(cam.desc)
+    desc.lo, desc.hi = float(lo), float(hi)
+    return _Bundle(desc, torch.from_numpy(cam.rays).to(device), torch.from_numpy(cam.light).to(device))
+
+
+def render_rays(phi, cam, mode, lo, hi, out_kind, scale, vrange, chunk=None):
+    """render through a RayView (make_camera, rays_from_view, or a caller's own table): the same contract, result and stats, behind
+    any net and precision the forward entry serves.  mode 'max' | 'min' | 'mean'; a slice is refused.  The march, the chunking and
+    the integer folds are render's; only the clip and the coordinates read the ray table, and the fold tests no sample again (the
+    clip's list is exact), so samples_evaluated == samples_inside."""
+    if mode not in CAMERA_MODES:
+        if mode == "slice":
+            raise ValueError(CAMERA_SCOPE % "mode 'slice'")
+        raise ValueError("view mode %r is not one of %s" % (mode, " | ".join(CAMERA_MODES)))
+    if out_kind not in ("u8", "u16"):
+        raise ValueError("render_rays folds the integer decode only: out_kind must be 'u8' or 'u16' (got %r)" % (out_kind,))
+    return _render(phi, lambda: _bundle(cam, lo, hi, phi.params.device), mode, out_kind, scale, vrange, chunk)
+
+
+def render_surface_rays(phi, cam, level, lo, hi, out_kind, scale, vrange, channel=0, side="above", refine=8, shading=True, light=None,
+                        gscale=None, chunk=None):
+    """render_surface through a RayView: its dict (first, t_lo, t_hi, t in samples along each ray, position, normal, shade, hits, stats)
+    plus distance float32 [rows, cols] = fl(near + fl(t * depth_spacing)), the physical distance of the hit from the eye along its
+    ray, NaN without a hit.  light=None is the per-ray headlight cam.light (a point light at the eye); a given light is one constant
+    direction for every ray.  Shading has render_surface's envelope, refused before any decode."""
+    out = _render_surface(phi, lambda: _bundle(cam, lo, hi, phi.params.device), "render_surface_rays", list(cam.desc.dims), level, lo, hi, out_kind,
+                          scale, vrange, channel, side, refine, shading, light, gscale, chunk)
+    out["distance"] = out["t"] * cam.depth_spacing + cam.near     # (two fp32 operations, each rounded on its own)
+    return out
+
+
 # ---- artefacts ------------------------------------------------------------------------------------------------------------------
 ENVELOPE = dict(
     no_error_bound="a view of an error-bounded artefact is refused: its corrections (error_bound %s) exist on the points of the "
@@ -826,14 +1089,19 @@ ENVELOPE = dict(
                  "range to sample"))
 
 
-def open_single(opt, module_path, sideinfos):
+CAMERA_DIVIDE_REFUSAL = ("a camera view of a DivideTask artefact is refused: a camera view of a partition is a follow-up (every block has its own "
+                         "net, and the rays of a camera are not parallel, so a block's window of rays is not a shadow of its cell); render an "
+                         "orthographic view with --view-owner nearest, or fit the volume as a SingleTask")
+
+
+def open_single(opt, module_path, sideinfos, refusal=DIVIDE_REFUSAL):
     """artefact.open_artefact for the view decodes, which exist for SingleTask artefacts only: the side info of a whole DivideTask job
     (it describes no net, so it cannot be opened) and blocks beside the module directory are refused by name"""
     from .io import load_yaml
     if isinstance(sideinfos, str):
         sideinfos = load_yaml(sideinfos)
     if "phi_features" not in sideinfos or os.path.isdir(os.path.join(os.path.dirname(str(module_path)), "sideinfos")):
-        raise ValueError(DIVIDE_REFUSAL)
+        raise ValueError(refusal)
     return artefact.open_artefact(opt, module_path, sideinfos)
 
 
@@ -1003,3 +1271,52 @@ def decompress_surface(art, direction, level, up=None, region=None, centre=None,
     res = {k: (x.cpu().numpy() if hasattr(x, "cpu") else x) for k, x in out.items()}
     res["depth"] = res["t"] * np.float32(depth_spacing)
     return res
+
+
+# ---- a camera on a stored artefact ------------------------------------------------------------------------------------------------------
+def open_single_camera(opt, module_path, sideinfos):
+    """open_single for the camera decodes: a DivideTask artefact is refused with the camera's own message"""
+    return open_single(opt, module_path, sideinfos, CAMERA_DIVIDE_REFUSAL)
+
+
+def decompress_camera(art, eye, direction, up=None, mode="max", fov=60.0, size=(256, 256), near=0.0, far=None, depth_spacing=1.0,
+                      voxel_size=(1, 1, 1), region=None, device="cuda", chunk=None, return_hits=False):
+    """a perspective view of a stored SingleTask artefact (art: open_single_camera's) as a numpy image [rows, cols, channels], without
+    decoding the volume: mode 'max' | 'min' (source dtype) or 'mean' (float32) folds every ray of the camera (make_camera's arguments)
+    over the clip box `region`.  The envelope and the handling of Decompress.postprocess are decompress_view's: a threshold and a clip
+    commute with max and min and act on the image; a mean with a postprocess other than the identity is refused.  A slice and a
+    composite through a camera are out of scope and refused by name.  return_hits: (image, hits [rows, cols] int32, stats)."""
+    if mode not in CAMERA_MODES:
+        if mode == "slice":
+            raise ValueError(CAMERA_SCOPE % "mode 'slice'")
+        raise ValueError("view mode %r is not one of %s" % (mode, " | ".join(CAMERA_MODES)))
+    check_envelope(art, mode)
+    cam = make_camera(art.dims, eye, direction, up, fov, size, near, far, depth_spacing, voxel_size, region)
+    image, hits, stats = render_rays(art.load_phi(device), cam, mode, art.lo, art.hi, art.out_kind, art.norm_range, art.vrange, chunk=chunk)
+    img = image.cpu().numpy()
+    if mode != "mean":
+        img = np.array(art.postprocess_local(img), copy=True)
+        img[hits.cpu().numpy() == 0] = 0                            # (a ray without a sample stays 0 whatever the clip's floor is)
+    return (img, hits.cpu().numpy(), stats) if return_hits else img
+
+
+def decompress_camera_surface(art, eye, direction, level, up=None, fov=60.0, size=(256, 256), near=0.0, far=None, depth_spacing=1.0,
+                              voxel_size=(1, 1, 1), region=None, channel=0, side="above", refine=8, shading=True, light=None, device="cuda",
+                              chunk=None):
+    """the isosurface of a stored SingleTask artefact seen through a perspective camera (make_camera's arguments): a dict of numpy
+    arrays, render_surface_rays' first, t_lo, t_hi, t, position, normal, shade, hits, stats and distance (float32, the physical
+    distance of the hit from the eye along its ray; NaN without a hit).  `level`, `side`, `refine` and the refusals are
+    decompress_surface's.  Normals are physical; light=None is a point light at the eye (every ray is lit along its own direction),
+    a given light is one physical direction the light travels."""
+    from . import gradient
+    check_envelope(art, "max")
+    check_surface(level, channel, side, refine, art.cout, art.dtype)
+    if shading:
+        why = gradient.refusal(art.phi_name, art.precision, art.phi_features)
+        if why is not None:
+            raise ValueError("normals and shading need the analytic Jacobian: %s; ask for shading=False" % why)
+    cam = make_camera(art.dims, eye, direction, up, fov, size, near, far, depth_spacing, voxel_size, region)
+    gscale = gradient.voxel_scale(art.dims, art.lo, art.hi, art.norm_range, art.vrange[0], art.vrange[1]) / _vec3(voxel_size, "voxel_size")
+    out = render_surface_rays(art.load_phi(device), cam, level, art.lo, art.hi, art.out_kind, art.norm_range, art.vrange, channel=channel, side=side,
+                              refine=refine, shading=shading, light=None if light is None else _unit3(light, "light"), gscale=gscale, chunk=chunk)
+    return {k: (x.cpu().numpy() if hasattr(x, "cpu") else x) for k, x in out.items()}

@@ -87,6 +87,19 @@ do not change, and the gradient is evaluated only at samples that emit and are n
 `--view`, and the optical depth in front of a sample is carried across the blocks of its ray, so the image is the composite of the
 whole volume's samples in depth order, bit for bit independent of the order of the blocks.  Blocks behind something partly opaque are
 evaluated a second time.  Without `--view-owner` a DivideTask artefact is refused; `--view-owner` on a SingleTask artefact is refused.
+
+    python decompress.py -p <run yaml> -c <.../compressed> --region :,:,: --view dz,dy,dx --view-eye z,y,x [--view-fov DEG] [--view-near T]
+        [--view-far T] [--view-size R,C] [--view-depth-spacing S] [--view-up uz,uy,ux] [--voxel-size sz,sy,sx]
+        [--view-mode max|min|mean | --view-surface LEVEL ...] -o out.tif|out.png|out.npy
+
+`--view-eye z,y,x` turns the view into a PERSPECTIVE CAMERA at that voxel-index position, looking along `--view`; the eye may lie inside
+the volume (a fly-through); a position whose first number is negative is attached with `=`, `--view-eye=-20,4,52`.  `--view-fov` is the full opening angle over the rows in degrees (default 60), `--view-size` the image
+(default 256,256), and every ray is sampled at the distances `--view-near` + k * `--view-depth-spacing` from the eye up to `--view-far`
+(default: the clip box's farthest corner).  `--view-mode max|min|mean` writes a projection, `--view-surface LEVEL` the isosurface with a
+point light at the eye (or along `--view-light`); the outputs are those of the orthographic forms, and the `.npy` of a surface holds the
+DISTANCE of the hit from the eye in the depth slot.  SingleTask artefacts; refused by name: a DivideTask or an error-bounded artefact,
+`--view-eye` without `--view`, `--view-fov` / `--view-near` / `--view-far` without `--view-eye`, and `--view-eye` with `--view-spacing`,
+`--view-offset`, `--view-mode slice`, `--view-composite...`, `--view-owner`, `--mip`, `--gradient`, `--hessian`, `--shape` or `--step`.
 """
 import argparse
 import os
@@ -143,9 +156,16 @@ def main(argv=None):
                     help="light the composite by the net's analytic gradient: emission x (KA + KD |n . l|), the ambient and the diffuse weight each in [0, 1]")
     ap.add_argument("--view-composite-light", default=None, metavar="lz,ly,lx",
                     help="the physical direction the light of --view-composite-shade travels (default: the view direction)")
+    ap.add_argument("--view-eye", default=None, metavar="z,y,x",
+                    help="a perspective camera at this voxel-index position looking along --view (it may lie inside the volume): --view-mode max|min|mean or --view-surface")
+    ap.add_argument("--view-fov", type=float, default=None, metavar="DEG", help="the camera's full opening angle over the rows, degrees (default 60)")
+    ap.add_argument("--view-near", type=float, default=None, metavar="T", help="the distance from the eye of every ray's first sample (default 0)")
+    ap.add_argument("--view-far", type=float, default=None, metavar="T", help="the distance from the eye of every ray's last sample (default: the clip box's farthest corner)")
     ap.add_argument("--voxel-size", default=None, metavar="sz,sy,sx", help="physical extent of a voxel per axis (default 1,1,1)")
     ap.add_argument("-o", required=True, help="output file (.tif / .tiff / .npy / .png / .jpg)")
     args = ap.parse_args(argv)
+    if any(v is not None for v in (args.view_eye, args.view_fov, args.view_near, args.view_far)):
+        _camera_refusals(args)        # every refusal by name, before the GPU path is imported
     if any(v is not None for v in (args.view_composite, args.view_composite_channel, args.view_background, args.view_composite_bits,
                                    args.view_composite_shade, args.view_composite_light)):
         _composite_refusals(args)     # every refusal by name, before the GPU path is imported
@@ -313,11 +333,90 @@ def _view_refusals(args):
         raise SystemExit("--view: " + DIVIDE_REFUSAL)
 
 
+def _camera_refusals(args):
+    if args.view_eye is None:
+        raise SystemExit("--view-fov / --view-near / --view-far describe the camera of a --view-eye: give the eye's position with --view-eye z,y,x")
+    if args.view is None:
+        raise SystemExit("--view-eye %s places a camera, and a camera looks along a direction: give it with --view dz,dy,dx" % args.view_eye)
+    lattice = "a camera has no pixel lattice in the volume (its image is set by --view-fov and --view-size)"
+    scope = "through a camera it is out of scope, a follow-up; ask for --view-mode max|min|mean or --view-surface LEVEL"
+    each = "each writes a result of its own; ask for one of them"
+    composite = any(v is not None for v in (args.view_composite, args.view_composite_channel, args.view_background, args.view_composite_bits,
+                                            args.view_composite_shade, args.view_composite_light))
+    for flag, on, why in (("--view-spacing", args.view_spacing != 1.0, lattice), ("--view-offset", args.view_offset is not None, lattice),
+                          ("--view-mode slice", args.view_mode == "slice", "a slice is a plane of parallel rays; " + scope),
+                          ("--view-composite", composite, "a composite is defined for the orthographic view; " + scope),
+                          ("--view-owner", args.view_owner is not None, "a camera view of a partition is a follow-up"),
+                          ("--mip", args.mip, each), ("--gradient", args.gradient is not None, each), ("--hessian", args.hessian is not None, each),
+                          ("--shape", args.shape is not None, "a camera samples the fitted grid along its own rays"),
+                          ("--step %d" % args.step, args.step != 1, "a camera samples the fitted grid along its own rays")):
+        if on:
+            raise SystemExit("--view-eye with %s: %s" % (flag, why))
+    _floats(args.view_eye, 3, "--view-eye")
+    if os.path.isdir(_paths(args.c)[2]):
+        from brief_pytorch_amd.view import CAMERA_DIVIDE_REFUSAL
+        raise SystemExit("--view-eye: " + CAMERA_DIVIDE_REFUSAL)
+
+
+def _camera(args, opt, region):
+    """--view dz,dy,dx --view-eye z,y,x: a projection (--view-mode max|min|mean) or the isosurface (--view-surface LEVEL) through a camera"""
+    import numpy as np
+    import torch
+    from brief_pytorch_amd import gradient, view
+    from brief_pytorch_amd.tool import save_img
+    module, side_path, _ = _paths(args.c)
+    npy = os.path.splitext(args.o)[1].lower() == ".npy"
+    kw = dict(up=_floats(args.view_up, 3, "--view-up") if args.view_up is not None else None, region=region,
+              fov=60.0 if args.view_fov is None else args.view_fov, near=0.0 if args.view_near is None else args.view_near, far=args.view_far,
+              depth_spacing=args.view_depth_spacing,
+              size=[int(x) for x in _floats(args.view_size, 2, "--view-size")] if args.view_size is not None else (256, 256),
+              voxel_size=_floats(args.voxel_size, 3, "--voxel-size") if args.voxel_size is not None else (1, 1, 1))
+    eye, direction = _floats(args.view_eye, 3, "--view-eye"), _floats(args.view, 3, "--view")
+    t0 = time.perf_counter()
+    try:
+        art = view.open_single_camera(opt, module, side_path)
+        if args.view_surface is None:
+            data, hits, stats = view.decompress_camera(art, eye, direction, mode=args.view_mode, return_hits=True, **kw)
+        else:
+            why = gradient.refusal(art.phi_name, art.precision, art.phi_features)
+            if why is not None and not npy:
+                raise ValueError("a shaded image needs the analytic Jacobian: %s; write the distance with -o <file>.npy" % why)
+            res = view.decompress_camera_surface(
+                art, eye, direction, args.view_surface, channel=args.view_channel or 0, side=args.view_surface_side or "above",
+                refine=8 if args.view_refine is None else args.view_refine, shading=why is None,
+                light=_floats(args.view_light, 3, "--view-light") if args.view_light is not None else None, **kw)
+            stats = res["stats"]
+    except ValueError as e:                                       # a refusal (artefact kind, dtype, normalisation, level, net, geometry, region)
+        raise SystemExit("--view-eye: %s" % e)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    if args.view_surface is None:
+        what = "view (%s)" % args.view_mode
+    else:
+        what = "surface view (level %d, %s: %d rays hit the surface, %d cut by the clip box, %d refinement points)" % (
+            args.view_surface, args.view_surface_side or "above", stats["rays_surface"], stats["rays_cut"], stats["refine_points"])
+        if not npy:
+            data = np.floor(255.0 * res["shade"].astype(np.float64) + 0.5).astype(np.uint8)[..., None]
+        elif res["shade"] is None:
+            data = res["distance"]
+        else:                                                     # (the orthographic layout, the distance from the eye in the depth slot)
+            data = np.concatenate([res["distance"][..., None], res["normal"], res["shade"][..., None]], axis=-1).astype(np.float32)
+    if npy:
+        np.save(args.o, data)
+    else:
+        save_img(args.o, data)
+    print("SingleTask camera %s at eye %s along %s of region %s: %s, dtype %s, %d of %d rays hit, %d samples evaluated, decoded in %.3f s -> %s" % (
+        what, args.view_eye, args.view, args.region, tuple(data.shape), data.dtype, stats["rays_hit"], stats["rays"], stats["samples_evaluated"], dt, args.o))
+    return 0
+
+
 def _view(args, opt, region, divide):
     import numpy as np
     import torch
     from brief_pytorch_amd.framework import NFGR, decompress_divide_view
     from brief_pytorch_amd.tool import save_img
+    if args.view_eye is not None:
+        return _camera(args, opt, region)
     if args.view_surface is not None:
         return _surface(args, opt, region, divide)
     if args.view_composite is not None:

@@ -887,6 +887,64 @@ int brief_siren_hess_forward(const brief_siren_desc *d, const float *packed, con
 int brief_siren_hess_forward_box(const brief_siren_desc *d, const float *packed, const brief_grid_box *box, int64_t offset, int64_t n,
                                  float *value, float *jac, float *hess, void *stream);
 
+/* ---- ray view: a view whose rays come from a table, e.g. a perspective camera (csrc/brief_rays.inc, csrc/brief_rays.h) -------------
+ * A ray view is rows x cols rays with `depth` samples each.  Ray r = row * cols + col is six floats of a DEVICE table,
+ * rays[r] = (base_z, base_y, base_x, dd_z, dd_y, dd_x), in voxel-index units of the fitted grid `dims`: the orthographic view's
+ * arithmetic with a foot and a step per ray, so the bundle may fan out from a point.
+ *     position    p_a(r, k) = fl(base_a[r] + fl((float)k * dd_a[r]))                                (fp32, nothing contracted)
+ *     real depth  p_a(r, t) = fl(base_a[r] + fl(t * dd_a[r]))
+ *     inside, coordinate: the view entries' rules on the descriptor's clip box, dims and lo / hi.
+ * A table filled from an orthographic view (base = its sample (row, col, 0), dd = its ddepth) reproduces that view bit for bit.
+ *   brief_rays_clip            k0[r], cnt[r]: the inside samples of ray r are exactly k0 <= k < k0 + cnt (every p_a is monotone in k
+ *                              along a ray, whatever its direction: one interval, found by bisection on the ray's own position; a
+ *                              zero step component is legal).  0 <= k0 <= k0 + cnt <= depth whatever the table holds, NaN included;
+ *   (caller)                   off = exclusive scan of cnt, the compacted ray-major sample list, as for brief_view_coords;
+ *   brief_rays_coords          coords[s - s0][3] for the samples s0 <= s < s1 of the list;
+ *   (caller)                   vals[s - s0][channels] = the forward entry on coords, out_kind BRIEF_OUT_U8 | BRIEF_OUT_U16;
+ *   brief_rays_fold            brief_view_fold's fold for BRIEF_VIEW_MAX / _MIN / _MEAN (_SLICE is refused), GEOMETRY-FREE: the list of
+ *                              brief_rays_clip is exact, so no sample is tested again, the table is not read, and hits[r] grows by the
+ *                              samples of [s0, s1) that belong to ray r.  hits and acc as brief_view_fold's; the finish is
+ *                              brief_view_finish;
+ *   brief_rays_surface_fold    brief_surface_fold's first-hit fold over the same walk, likewise geometry-free; the bracket and the step
+ *                              are brief_surface_bracket / brief_surface_step;
+ *   brief_rays_surface_coords  brief_surface_coords' rule (dense, midpoint or t_hi, box_lo and NaN without a hit) at the ray's real depth;
+ *   brief_rays_surface_shade   brief_surface_shade's arithmetic with a light per ray: light is a DEVICE table [rays][3] of unit
+ *                              directions the light travels (a point light at a camera's eye: the rays' own directions); gscale
+ *                              stays a HOST pointer to three floats.
+ * brief_view_finish, brief_surface_bracket and brief_surface_step read rows x cols of their descriptor only: call them with a
+ * brief_view_desc that carries the ray view's dims, lo / hi, box, rows, cols and depth, with origin and steps zero.
+ * The walk (`lanes`, [r0, r1), one owner per pixel, no atomics, integer folds: exact, independent of chunking, `lanes` and the run)
+ * is the view entries'.  Every device entry only enqueues on `stream`.  The device table is trusted: a bad one may give a wrong
+ * image, never an access outside a buffer or an unbounded loop.
+ * brief_rays_sample_host / _sample_t_host / _clip_host evaluate the same header on the host CPU without any GPU call: every buffer,
+ * the table included, is host memory, and a table entry that is not finite is refused.
+ * Limits (BRIEF_ERR_INVALID with a message naming the limit, before any launch): those of the view and surface entries (rows, cols,
+ * depth 1 .. 2^24 - 1; dims 2 .. 2^31 - 1; lo / hi and the box finite, 0 <= box_lo <= box_hi <= dims - 1; at most 2^40 rays; lanes a
+ * power of two 1 .. 64; channels 1 .. 4; no null buffer, pos of brief_rays_surface_coords excepted). */
+typedef struct {
+    int64_t dims[3];
+    float lo, hi;                            /* coordinate range of the fitted grid */
+    int32_t rows, cols, depth, reserved;
+    float box_lo[3], box_hi[3];              /* inclusive clip box */
+} brief_rays_desc;
+int brief_rays_clip(const brief_rays_desc *desc, const float *rays, int32_t *k0, int32_t *cnt, void *stream);
+int brief_rays_coords(const brief_rays_desc *desc, const float *rays, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1, int64_t r0,
+                      int64_t r1, int32_t lanes, float *coords, void *stream);
+int brief_rays_fold(const brief_rays_desc *desc, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1, int64_t r0, int64_t r1,
+                    int32_t lanes, const void *vals, int elem_kind, int32_t channels, int32_t mode, int32_t *hits, void *acc, void *stream);
+int brief_rays_surface_fold(const brief_rays_desc *desc, const int32_t *k0, const int64_t *off, int64_t s0, int64_t s1, int64_t r0, int64_t r1,
+                            int32_t lanes, const void *vals, int elem_kind, int32_t channels, int32_t channel, int32_t level, int32_t side,
+                            int32_t *hits, int32_t *first, void *stream);
+int brief_rays_surface_coords(const brief_rays_desc *desc, const float *rays, const float *t_lo, const float *t_hi, int32_t midpoint, float *coords,
+                              float *pos, void *stream);
+int brief_rays_surface_shade(const brief_rays_desc *desc, const float *t, const float *jac, int32_t channels, int32_t channel, int32_t side,
+                             const float *gscale, const float *light, float *normal, float *shade, void *stream);
+int brief_rays_sample_host(const brief_rays_desc *desc, const float *rays, const int32_t *row, const int32_t *col, const int32_t *k, int64_t n,
+                           float *pos, float *coord, uint8_t *inside);
+int brief_rays_sample_t_host(const brief_rays_desc *desc, const float *rays, const int32_t *row, const int32_t *col, const float *t, int64_t n,
+                             float *pos, float *coord, uint8_t *inside);
+int brief_rays_clip_host(const brief_rays_desc *desc, const float *rays, int32_t *k0, int32_t *cnt);
+
 #ifdef __cplusplus
 }
 #endif
